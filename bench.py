@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- Mpixels/s of fused Cook-Torrance evaluation on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5] [--size S] [--batch B] [--no-cpu-baseline]
-                  [--layout arena|separate] [--settle L] [--cpu-budget SECONDS]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5] [--size S] [--batch B] [--full] [--dump-outputs DIR]
+                  [--no-cpu-baseline] [--layout arena|separate] [--settle L] [--cpu-budget SECONDS]
 
 `--config` selects the workload by SURVEY.md 8d's numbering (= BASELINE.json configs[config - 1]); a "step" is one pass of
 the hot path over this rank's batch = ONE launch of the fused kernel through the C ABI, inputs already resident in HBM:
@@ -26,20 +26,24 @@ runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-add
 bench.py ...` as a child and exits with its code.  Started under torch.distributed.run already (RANK in the
 environment), the script is a rank.
 
-Timing protocol.  Two timed regions, both K steps bracketed by barrier + synchronize, MAX over ranks:
-  cold    W warm-up launches from whatever state the GPU was in, then K timed steps -- the literal
-          "W warm-up, K steps" protocol -> `ms_per_step_cold`, `value_cold`;
-  steady  `--settle` further untimed launches (default: 300 for config 2, else what fills ~40 ms) so that power
-          management has settled the clocks (tools/transient_probe.py), then K timed steps -> `ms_per_step`, `value`:
-          the sustained rate.
-  slope   2K more steps, timed the same way: (wall(2K) - wall(K)) / K is the per-step time without the fixed cost of entering and
-          leaving a region (~80 us: 4 us per step of a 20-step region) -> `ms_per_step_slope`, beside the literal `ms_per_step`.
+Timing protocol.  A plain run times ONE region of K steps, bracketed by barrier + synchronize, MAX over ranks:
+  steady  W warm-up launches, then `--settle` further untimed launches (default: 300 for config 2, else what fills ~40 ms,
+          sized by one event-timed launch) so that power management has settled the clocks (tools/transient_probe.py), then
+          K timed steps -> `ms_per_step`, `value`: the sustained rate.
+`--full` adds, timed the same way:
+  cold    K timed steps right behind the W warm-up launches, ahead of the settle -- the literal "W warm-up, K steps"
+          protocol -> `ms_per_step_cold`, `value_cold`;
+  slope   2K more steps behind the steady region: (wall(2K) - wall(K)) / K is the per-step time without the fixed cost of entering
+          and leaving a region (~80 us: 4 us per step of a 20-step region) -> `ms_per_step_slope`, beside the literal `ms_per_step`.
 `warmup` echoes the argument; `launches_before_value` says how many launches really preceded the region `value` is taken from.
-Rank 0 prints ONE JSON line (contract in the task statement).  Extra objects:
+`--dump-outputs DIR` writes what the last timed step computed -- the image a caller of the timed path receives -- to DIR/result.npy
+(float32; an output above 32 MB: a fixed, seeded sample of its rows, see output_sample).  The inputs are seeded: two runs with the
+same arguments get the same inputs, so two builds can be compared output for output.
+Rank 0 prints ONE JSON line (contract in the task statement).  Extra objects (`roofline` in every run, the others with `--full`):
   roofline     -- achieved algorithmic HBM GB/s of the kernel (bytes per pixel x this rank's pixels per launch / average
                   launch duration from HIP events on the launch stream over the STEADY region -- the K steps `value` is quoted on;
                   rounds 2-4 averaged the cold region in, which alone moved `frac` by 4 %: profiles/history/r05_driver_line_ab.md) vs 8 TB/s;
-                  for N > 1 the slowest rank's.  Config 2 also runs the BARE access pattern of the kernel (tools/boxcal.hip: the same
+                  for N > 1 the slowest rank's.  With --full, config 2 also runs the BARE access pattern of the kernel (tools/boxcal.hip: the same
                   planes, the same bytes per lane, no arithmetic) on the same buffers right behind the steady region:
                   `box_pattern_us`, `kernel_over_box_pattern` -- a slow line with a ratio near 1 is a slow box, not a slow binary
   roofline_valu-- config 5 only: the launch is VALU-bound; vector instructions issued per second against the chip's issue rate
@@ -344,6 +348,25 @@ def load_boxcal():
     return lib
 
 
+def output_sample(t, limit_bytes=32 << 20, seed=0):
+    """`t` as float32 on the host.  Larger than `limit_bytes`: a fixed, seeded sample of it -- t viewed as rows of its last
+    dimension, `limit_bytes` worth of those rows drawn by torch.randperm under `seed`, kept whole and in ascending order."""
+    t = t.detach().float()
+    rows = t.reshape(-1, t.shape[-1])
+    if rows.numel() * 4 <= limit_bytes:
+        return t.cpu().numpy()
+    k = max(1, limit_bytes // (4 * rows.shape[1]))
+    pick = torch.randperm(rows.shape[0], generator=torch.Generator().manual_seed(seed))[:k].sort().values
+    return rows[pick.to(rows.device)].cpu().numpy()
+
+
+def dump_outputs(dirname, result):
+    """--dump-outputs: what the timed path computed in its last step, as DIR/result.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "result.npy"), output_sample(result))
+
+
 SHARE_GPU = os.environ.get("PBR_BENCH_SHARE_GPU") == "1"     # test hook: N ranks on fewer GPUs (rank r on device r mod count), the
                                                               # small collectives over gloo -- exercises the N > 1 code path on a 1-GPU box
 
@@ -385,9 +408,10 @@ def timed_region(plans, steps, stream, barrier, offset=0):
 def run_config1(args, real_stdout):
     """BASELINE.json configs[0] on the GPU: ONE 256x256 BasecolorMetallicMaterial, point light, through the reference-shaped callable
     `CookTorranceBRDF.__call__` (examples/example_brdf.py:14-23) -- where the cost is the host layer and the launch, not the kernel.
-    Legs (median of `--steps` repeats of 200 calls each): device-resident material, eager and captured into a HIP graph; CPU-resident
-    material (the reference's default: upload, evaluate, image back), eager; the bare plan launch; the kernel by HIP events; and the CPU
-    oracle's time for the same call on this host (34.4 ms on the survey's 8 cores)."""
+    Legs (median of `--steps` repeats of 200 calls each): device-resident material, eager -- the headline, and all a plain run times --
+    and with --full: captured into a HIP graph; CPU-resident material (the reference's default: upload, evaluate, image back), eager;
+    the bare plan launch; the kernel by HIP events; and the CPU oracle's time for the same call on this host (34.4 ms on
+    the survey's 8 cores)."""
     import statistics
     from pypbr_amd import functional as F
     from pypbr_amd.materials import BasecolorMetallicMaterial
@@ -413,7 +437,7 @@ def run_config1(args, real_stdout):
         for _ in range(reps):
             t0 = time.perf_counter()
             for _ in range(calls):
-                fn()
+                out = fn()
                 if sync_each:
                     torch.cuda.synchronize()
             t1 = time.perf_counter()
@@ -421,16 +445,32 @@ def run_config1(args, real_stdout):
             t2 = time.perf_counter()
             issue.append((t1 - t0) / calls * 1e6)
             drained.append((t2 - t0) / calls * 1e6)
-        return round(statistics.median(issue), 2), round(statistics.median(drained), 2)
+        return round(statistics.median(issue), 2), round(statistics.median(drained), 2), out
 
-    eager_issue, eager = per_call(lambda: brdf(on_dev, view, light, inten, 1.0))
-    _, eager_sync = per_call(lambda: brdf(on_dev, view, light, inten, 1.0), sync_each=True)          # a caller that looks at every image
-    _, cpu_resident = per_call(lambda: brdf(on_cpu, view, light, inten, 1.0))                        # returns a host tensor: synchronous by nature
+    eager_issue, eager, last_out = per_call(lambda: brdf(on_dev, view, light, inten, 1.0))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_out)
     store = on_dev._raw
     plan = F.plan_cook_torrance(store["albedo"], store["normal"], store["roughness"], store["metallic"], view_dir=VIEW, light=[0.1, 0.1, 1.0],
                                 light_intensity=[1.0, 1.0, 1.0], light_type="point", light_size=1.0)
+    line = {
+        "metric": "Mpixels/s Cook-Torrance eval, BASELINE.json configs[0] (one 256x256 material through CookTorranceBRDF.__call__)",
+        "value": round(S * S / eager, 3), "unit": "Mpixels/s", "n_gpus": 1, "steps": reps, "warmup": 20,
+        "ms_per_step": round(eager * 1e-3, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"Single {S}x{S} BasecolorMetallicMaterial, point light, CookTorranceBRDF.__call__ on a device-resident material, eager "
+                               "(BASELINE.json configs[0]; examples/example_brdf.py path)", "config": 1, "kernel": plan.kernel_name,
+                   "pixels_per_step": S * S, "bytes_per_pixel": plan.bytes_per_pixel, "lights": 1, "map_dtype": "f32",
+                   "timing": f"a step = one call; medians over {reps} repeats of {calls} back-to-back calls, GPU drained at the end of each repeat"},
+    }
+    from pypbr_amd import _native
+    line["build"] = _native.build_stamp()
+    if not args.full:
+        os.write(real_stdout, (json.dumps(line) + "\n").encode())
+        return
+    _, eager_sync, _ = per_call(lambda: brdf(on_dev, view, light, inten, 1.0), sync_each=True)       # a caller that looks at every image
+    _, cpu_resident, _ = per_call(lambda: brdf(on_cpu, view, light, inten, 1.0))                     # returns a host tensor: synchronous by nature
     stream = torch.cuda.current_stream(dev).cuda_stream
-    plan_issue, plan_drained = per_call(lambda: plan.launch(stream))
+    plan_issue, plan_drained, _ = per_call(lambda: plan.launch(stream))
     _, kernel_ms = timed_region([plan], 2000, stream, lambda: None)
     # the same call captured into a HIP graph (a render loop over a fixed material: replay costs one graph launch)
     side = torch.cuda.Stream(dev)
@@ -442,32 +482,21 @@ def run_config1(args, real_stdout):
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         captured_out = brdf(on_dev, view, light, inten, 1.0)
-    graph_issue, graph_drained = per_call(graph.replay)
+    graph_issue, graph_drained, _ = per_call(graph.replay)
     eager_out = brdf(on_dev, view, light, inten, 1.0)
     graph.replay()
     torch.cuda.synchronize()
     assert torch.equal(captured_out, eager_out)
-    line = {
-        "metric": "Mpixels/s Cook-Torrance eval, BASELINE.json configs[0] (one 256x256 material through CookTorranceBRDF.__call__)",
-        "value": round(S * S / eager, 3), "unit": "Mpixels/s", "n_gpus": 1, "steps": reps, "warmup": 20,
-        "ms_per_step": round(eager * 1e-3, 5), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"Single {S}x{S} BasecolorMetallicMaterial, point light, CookTorranceBRDF.__call__ on a device-resident material, eager "
-                               "(BASELINE.json configs[0]; examples/example_brdf.py path)", "config": 1, "kernel": plan.kernel_name,
-                   "pixels_per_step": S * S, "bytes_per_pixel": plan.bytes_per_pixel, "lights": 1, "map_dtype": "f32",
-                   "timing": f"a step = one call; medians over {reps} repeats of {calls} back-to-back calls, GPU drained at the end of each repeat"},
-        "latency_us": {
-            "eager_device_resident": eager, "eager_device_resident_host_issue": eager_issue, "eager_device_resident_sync_every_call": eager_sync,
-            "graph_replay_device_resident": graph_drained, "graph_replay_host_issue": graph_issue,
-            "eager_cpu_resident_upload_evaluate_download": cpu_resident,
-            "plan_launch": plan_drained, "plan_launch_host_issue": plan_issue, "kernel_hip_events": round(kernel_ms * 1e3, 2),
-            "eager_over_graph": round(eager / graph_drained, 2),
-            "note": "host layer = eager - plan_launch; launch = plan_launch - kernel; the kernel itself is launch-latency-sized at 256^2"},
-        "roofline": {"bound": "hbm", "achieved": round(plan.bytes_per_pixel * S * S / (kernel_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(plan.bytes_per_pixel * S * S / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
-                     "kernel_us": round(kernel_ms * 1e3, 2), "note": "2.9 MB per launch: 0.36 us at peak -- this configuration measures latency, not bandwidth"},
-    }
-    from pypbr_amd import _native
-    line["build"] = _native.build_stamp()
+    line["latency_us"] = {
+        "eager_device_resident": eager, "eager_device_resident_host_issue": eager_issue, "eager_device_resident_sync_every_call": eager_sync,
+        "graph_replay_device_resident": graph_drained, "graph_replay_host_issue": graph_issue,
+        "eager_cpu_resident_upload_evaluate_download": cpu_resident,
+        "plan_launch": plan_drained, "plan_launch_host_issue": plan_issue, "kernel_hip_events": round(kernel_ms * 1e3, 2),
+        "eager_over_graph": round(eager / graph_drained, 2),
+        "note": "host layer = eager - plan_launch; launch = plan_launch - kernel; the kernel itself is launch-latency-sized at 256^2"}
+    line["roofline"] = {"bound": "hbm", "achieved": round(plan.bytes_per_pixel * S * S / (kernel_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(plan.bytes_per_pixel * S * S / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
+                        "kernel_us": round(kernel_ms * 1e3, 2), "note": "2.9 MB per launch: 0.36 us at peak -- this configuration measures latency, not bandwidth"}
     if not args.no_cpu_baseline:
         _oracle_path()
         import torch_oracle as O
@@ -509,7 +538,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--size", type=int, default=None, help="override the configuration's map edge (tests)")
     ap.add_argument("--batch", type=int, default=None, help="override the configuration's batch (tests; configs 3-5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the checker's legs (cpu_baseline and parity)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: cold and slope regions, box calibration, the configurations' second kernels, "
+                         "the light-block broadcast latency, an RCCL group of one, roofline_valu and the checker's legs (parity, cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/result.npy (float32, a seeded sample of rows above 32 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the checker's legs (cpu_baseline and parity)")
     ap.add_argument("--settle", type=int, default=None, help="untimed clock-settle launches between the cold and the steady timed region")
     ap.add_argument("--layout", choices=("separate", "arena"), default="arena",
                     help="config 2.  arena (default): the material's maps and result in one allocation, as Material.to(device) lays "
@@ -580,7 +614,7 @@ def main():
         else:
             dist.init_process_group("nccl", device_id=device)
         backend = dist.get_backend()
-    late_rccl = world == 1 and not distributed and not args.no_rccl       # a single rank started plainly: see form_group_of_one below
+    late_rccl = args.full and world == 1 and not distributed and not args.no_rccl       # a single rank started plainly: see below
 
     def barrier(always=False):
         # a group of ONE has nobody to wait for: the timed regions of an N = 1 run contain no collective at all
@@ -598,7 +632,7 @@ def main():
             broadcast_light_block(params if rank == 0 else None, device=device, src=0)
             lat.append((time.perf_counter() - t0) * 1e6)
         return sorted(lat)[len(lat) // 2]
-    bcast_us = broadcast_latency() if distributed else None
+    bcast_us = broadcast_latency() if distributed and args.full else None
 
     plans, map_sets = [], []
     share_plan = None
@@ -635,7 +669,7 @@ def main():
         plans.append(plan)
         map_sets.append([a, n, r, m])
         global_pixels = cfg["batch"] * S * S
-        if world == 1 and cfg["batch"] % 8 == 0 and cfg["batch"] >= 16:
+        if args.full and world == 1 and cfg["batch"] % 8 == 0 and cfg["batch"] >= 16:
             # beside the N = 1 point of the strong-scaling curve: the share one GPU of an 8-GPU node gets (its first B/8 materials)
             k = cfg["batch"] // 8
             share_plan = F.plan_cook_torrance(a[:k], n[:k], r[:k], m[:k], view_dir=VIEW, light=cfg["light"], light_intensity=cfg["intensity"],
@@ -645,22 +679,31 @@ def main():
     local_pixels = (shard.batch_stop - shard.batch_start) * (shard.row_stop - shard.row_start) * S
     stream = torch.cuda.current_stream(device).cuda_stream
 
-    # ---- cold: W warm-up launches, K timed steps (the literal protocol)
     for i in range(warmup):
         plans[i % len(plans)].launch(stream)
-    cold_s, cold_kernel_ms = timed_region(plans, steps, stream, barrier, offset=warmup)
+    probe = 0
+    if args.full:
+        # ---- cold: K timed steps right behind the W warm-up launches (the literal protocol)
+        cold_s, cold_kernel_ms = timed_region(plans, steps, stream, barrier, offset=warmup)
+        launch_ms = cold_kernel_ms
+    elif args.settle is None and args.config != 2:
+        probe = 1                                  # one event-timed launch sizes the settle below
+        _, launch_ms = timed_region(plans, probe, stream, barrier, offset=warmup)
     # ---- steady: clock settle (from an idle GPU the first ~20 launches run at boost clocks, the next ~150 up to 25 %
     # slower while power management reins them in, steady from launch ~300 of the 0.115 ms kernel on: tools/transient_probe.py)
-    settle = args.settle if args.settle is not None else (300 if args.config == 2 else max(2, int(math.ceil(40.0 / max(cold_kernel_ms, 1e-3)))))
+    settle = args.settle if args.settle is not None else (300 if args.config == 2 else max(2, int(math.ceil(40.0 / max(launch_ms, 1e-3)))))
     for i in range(settle):
         plans[i % len(plans)].launch(stream)
     elapsed, kernel_ms = timed_region(plans, steps, stream, barrier)
-    # ---- slope: 2K more steps; (wall(2K) - wall(K)) / K is a step without the region's fixed entry / exit cost
-    elapsed2k, kernel2k_ms = timed_region(plans, 2 * steps, stream, barrier)
+    if args.dump_outputs and rank == 0:            # the last of the K steps launched plans[(K - 1) % len(plans)]
+        dump_outputs(args.dump_outputs, plans[(steps - 1) % len(plans)].result)
+    if args.full:
+        # ---- slope: 2K more steps; (wall(2K) - wall(K)) / K is a step without the region's fixed entry / exit cost
+        elapsed2k, kernel2k_ms = timed_region(plans, 2 * steps, stream, barrier)
 
     extras = {}
     box_ms = None
-    if args.config == 2 and cfg["dtype"] == torch.float32:
+    if args.full and args.config == 2 and cfg["dtype"] == torch.float32:
         boxlib = load_boxcal()
         if boxlib is not None:                     # the bare access pattern on the same buffers, same rotation, same protocol
             boxes = [BoxPattern(boxlib, ms, pl.out) for ms, pl in zip(map_sets, plans)]
@@ -676,7 +719,7 @@ def main():
                                         "hbm_GBps_algorithmic": round(bpp * k * S * S / share_ms / 1e6, 1),
                                         "note": "the first B/8 materials of this very batch, same buffers: what one GPU of an 8-GPU node evaluates per step"}
         plans[0].launch(stream)                    # the parity leg reads the full result: write it again
-    if args.config == 3:
+    if args.full and args.config == 3:
         # the other setting of upstream's F6 flag (specular decoded once), same maps, same protocol
         alt = F.plan_cook_torrance(*map_sets[0], view_dir=params["view_dir"], light=params["light"], light_intensity=params["light_intensity"],
                                    light_type=cfg["light_type"], light_size=params["light_size"], y_offset=shard.row_start, height_total=S,
@@ -687,7 +730,7 @@ def main():
         plans[0].launch(stream)
 
     if late_rccl:
-        # `python bench.py` as the driver types it for N = 1: an RCCL group of ONE formed in this process AFTER the timed regions -- with
+        # `python bench.py --full` for N = 1 started plainly: an RCCL group of ONE formed in this process AFTER the timed regions -- with
         # RCCL initialised before them the same launches measured 1.0-1.3 % slower (five alternating pairs, round 4) -- so that the
         # line has still been through init_process_group("nccl"), the light-block broadcast, a barrier and the all-reduce / all-gather
         # of the N > 1 path below, and says so (`per_rank.backend`, `ranks_seen`).  Never fatal: without RCCL the line stands as measured.
@@ -706,13 +749,15 @@ def main():
     ranks_seen = dist.get_world_size() if distributed else 1
 
     per_rank_us, per_rank_px = [kernel_ms * 1e3], [local_pixels]
-    per_rank_all = [0.5 * (kernel_ms + cold_kernel_ms) * 1e3]
+    per_rank_all = [0.5 * (kernel_ms + cold_kernel_ms) * 1e3] if args.full else list(per_rank_us)
     shards = [tuple(shard)]
     if distributed:
-        t = torch.tensor([elapsed, cold_s, elapsed2k], device=coll, dtype=torch.float64)
+        t = torch.tensor([elapsed, cold_s, elapsed2k] if args.full else [elapsed], device=coll, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, cold_s, elapsed2k = float(t[0].item()), float(t[1].item()), float(t[2].item())
-        mine = torch.tensor([kernel_ms * 1e3, 0.5 * (kernel_ms + cold_kernel_ms) * 1e3, float(local_pixels)] + [float(v) for v in shard],
+        elapsed = float(t[0].item())
+        if args.full:
+            cold_s, elapsed2k = float(t[1].item()), float(t[2].item())
+        mine = torch.tensor([kernel_ms * 1e3, per_rank_all[0], float(local_pixels)] + [float(v) for v in shard],
                             device=coll, dtype=torch.float64)
         gathered = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
@@ -721,7 +766,8 @@ def main():
         per_rank_px = [int(g[2].item()) for g in gathered]
         shards = [tuple(int(v.item()) for v in g[3:7]) for g in gathered]
 
-    assert bool(torch.isfinite(plans[0].result).all())
+    if args.full:
+        assert bool(torch.isfinite(plans[0].result).all())
 
     if rank == 0:
         value = global_pixels * steps / elapsed / 1e6
@@ -729,17 +775,15 @@ def main():
         kernel_all_ms = per_rank_all[slow] * 1e-3                     # is quoted on -- took longest; (kernel_all: cold + steady, rounds 2-4's basis)
         achieved = bpp * per_rank_px[slow] / (per_rank_us[slow] * 1e-6) / 1e9
         traffic, traffic_run = recorded_traffic(kernel) if args.config == 2 and S == 4096 else (None, None)
+        ahead = f"{steps} cold-timed" if args.full else f"{probe} settle-sizing"
+        launches_before = warmup + (steps if args.full else probe) + settle
         line = {
             "metric": "Mpixels/s Cook-Torrance eval, 4K maps" if args.config == 2 else
                       f"Mpixels/s Cook-Torrance eval, BASELINE.json configs[{args.config - 1}]",
             "value": round(value, 1), "unit": "Mpixels/s", "n_gpus": world, "steps": steps, "warmup": warmup,
             "ms_per_step": round(elapsed / steps * 1e3, 5), "higher_is_better": True, "scaling": cfg["scaling"],
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "ms_per_step_cold": round(cold_s / steps * 1e3, 5),
-            "ms_per_step_slope": round((elapsed2k - elapsed) / steps * 1e3, 5),
-            "value_slope": round(global_pixels * steps / max(elapsed2k - elapsed, 1e-9) / 1e6, 1),
-            "launches_before_value": warmup + steps + settle,
-            "value_cold": round(global_pixels * steps / cold_s / 1e6, 1),
+            "launches_before_value": launches_before,
             "config": {"workload": cfg["name"].format(S=S, B=cfg["batch"]), "config": args.config,
                        "kernel": kernel, "global_batch": world if args.config == 2 else cfg["batch"], "map_size": [S, S],
                        "pixels_per_step": global_pixels, "bytes_per_pixel": bpp, "lights": len(cfg["light"]),
@@ -747,16 +791,12 @@ def main():
                        "parallelism": (f"material-sharded x{world}: " + ("one material per rank (weak)" if args.config == 2 else
                                        "pypbr_amd.distributed.partition over the batch, every rank generates and owns its slice (strong)"))
                                       + (" (TEST HOOK: ranks share GPUs, collectives over gloo)" if SHARE_GPU else ""),
-                       "timing": f"value/ms_per_step: wall time of {steps} steps after {warmup} warm-up + {steps} cold-timed + "
-                                 f"{settle} clock-settle launches = {warmup + steps + settle} launches (sustained rate; `warmup` echoes the argument); "
-                                 f"value_cold/ms_per_step_cold: the {steps} steps right after the {warmup} warm-up launches; "
-                                 f"value_slope/ms_per_step_slope: (wall of {2 * steps} further steps - wall of the {steps}) / {steps}, i.e. "
-                                 f"without the ~{max(0.0, (2 * elapsed - elapsed2k)) * 1e6:.0f} us a region costs to enter and leave",
+                       "timing": f"value/ms_per_step: wall time of {steps} steps after {warmup} warm-up + {ahead} + {settle} clock-settle "
+                                 f"launches = {launches_before} launches (sustained rate; `warmup` echoes the argument)",
                        "clock_settle_launches": settle},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_run,
                          "kernel_us": round(per_rank_us[slow], 2), "kernel_us_steady": round(per_rank_us[slow], 2),
-                         "kernel_us_cold_and_steady": round(kernel_all_ms * 1e3, 2),
                          "basis": "HIP events on the launch stream around the steady region's launches (the region `value` is quoted on)",
                          "pixels_per_launch": per_rank_px[slow], "rank": slow},
             "per_rank": {"kernel_us": [round(u, 2) for u in per_rank_us], "pixels_per_launch": per_rank_px,
@@ -767,6 +807,16 @@ def main():
             line["config"]["layout"] = ("arena: the 8 map planes of a material and its 3 result planes in one allocation "
                                         "(pypbr_amd.functional.pack_maps, what Material.to(device) does)" if args.layout == "arena" else
                                         "separate: albedo, normal, roughness, metallic and the result as five tensors wherever torch's allocator put them")
+        if args.full:
+            line.update({"ms_per_step_cold": round(cold_s / steps * 1e3, 5),
+                         "ms_per_step_slope": round((elapsed2k - elapsed) / steps * 1e3, 5),
+                         "value_slope": round(global_pixels * steps / max(elapsed2k - elapsed, 1e-9) / 1e6, 1),
+                         "value_cold": round(global_pixels * steps / cold_s / 1e6, 1)})
+            line["config"]["timing"] += (f"; value_cold/ms_per_step_cold: the {steps} steps right after the {warmup} warm-up launches; "
+                                         f"value_slope/ms_per_step_slope: (wall of {2 * steps} further steps - wall of the {steps}) / {steps}, i.e. "
+                                         f"without the ~{max(0.0, (2 * elapsed - elapsed2k)) * 1e6:.0f} us a region costs to enter and leave")
+            line["roofline"]["kernel_us_cold_and_steady"] = round(kernel_all_ms * 1e3, 2)
+        if args.full and args.config == 2:
             line["roofline"]["kernel_us_cold"] = round(cold_kernel_ms * 1e3, 2)
             line["roofline"]["kernel_us_2k_region"] = round(kernel2k_ms * 1e3, 2)
             if box_ms is not None:
@@ -775,7 +825,7 @@ def main():
                 line["roofline"]["box_pattern_us"] = round(box_ms * 1e3, 2)
                 line["roofline"]["box_pattern_frac"] = round(bpp * per_rank_px[0] / (box_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
                 line["roofline"]["kernel_over_box_pattern"] = round(per_rank_us[0] / (box_ms * 1e3), 4)
-        if len(cfg["light"]) > 1:
+        if args.full and len(cfg["light"]) > 1:
             L = len(cfg["light"])
             per_pl, valu_src, clock = recorded_valu()
             evals = per_rank_px[slow] * L / (kernel_all_ms * 1e-3) / 1e9
@@ -794,7 +844,7 @@ def main():
         line.update(extras)
         from pypbr_amd import _native
         line["build"] = _native.build_stamp()          # the commit, the library's sha256, the sources it was built from (stale = not these)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["parity"] = parity_of_timed_output(cfg, plans[0].out, map_sets[0], shard, 8 if S >= 2048 and len(cfg["light"]) == 1 else 4)
             if world == 1:
                 line["cpu_baseline"] = cpu_baseline(cfg, args.cpu_budget)

@@ -100,6 +100,11 @@ def render(mat, light_key, view=VIEW0, inten=INT0, return_srgb=True, dtype=torch
     return out
 
 
+def cpu_model():
+    with open("/proc/cpuinfo") as f:
+        return next((l.split(":", 1)[1].strip() for l in f if l.lower().startswith("model name")), "unknown")
+
+
 def sha12(t):
     return hashlib.sha1(np.ascontiguousarray(t).tobytes()).hexdigest()[:12]
 
@@ -464,6 +469,28 @@ def edge_set(manifest):
     manifest["sets"]["edge"] = {k: _entry(v) for k, v in d.items() if v.dtype.kind == "f"}
 
 
+def fresh_set(manifest):
+    """Seeds none of the other sets use (4242, 45x70, unnormalised normals in [-1, 1)), both workflows, a point light of size 2 and a
+    directional light, sRGB and linear out: the reference's outputs, so that tests/test_oracle_pin.py needs no reference tree."""
+    g = torch.Generator().manual_seed(4242)
+    H, W = 45, 70
+    a, n = torch.rand(3, H, W, generator=g), torch.rand(3, H, W, generator=g) * 2 - 1
+    r, m, s = torch.rand(1, H, W, generator=g), torch.rand(1, H, W, generator=g), torch.rand(3, H, W, generator=g)
+    view, inten = torch.tensor([0.3, 0.1, 0.9]), torch.tensor([1.5, 1.0, 0.5])
+    d = {"in_albedo": a, "in_normal": n, "in_roughness": r, "in_metallic": m, "in_specular": s}
+    for ltype, light, size in (("point", torch.tensor([0.4, -0.3, 0.7]), 2.0), ("directional", torch.tensor([-0.2, 0.5, 1.0]), None)):
+        brdf = CookTorranceBRDF(light_type=ltype)
+        for srgb in (True, False):
+            cs = "srgb" if srgb else "lin"
+            d[f"out_metallic_{ltype}_{cs}"] = brdf(BasecolorMetallicMaterial(albedo=a, normal=n, roughness=r, metallic=m),
+                                                   view, light, inten, size, return_srgb=srgb)
+            d[f"out_specular_{ltype}_{cs}"] = brdf(DiffuseSpecularMaterial(albedo=a, normal=n, roughness=r, specular=s),
+                                                   view, light, inten, size, return_srgb=srgb)
+    d = {k: v.numpy() for k, v in d.items()}
+    np.savez_compressed(os.path.join(GOLDEN, "fresh.npz"), **d)
+    manifest["sets"]["fresh"] = {k: _entry(v) for k, v in d.items()}
+
+
 def only(name, fn):
     """`python oracle/gen_golden.py --only <set>`: adds one fixture file and its MANIFEST entries without touching the others
     (they are byte-for-byte what earlier rounds committed)."""
@@ -507,6 +534,7 @@ def main():
         "reference": "giuvecchio/PyPBR at /root/reference (imported, unmodified)",
         "torch": torch.__version__,
         "aten_threads": torch.get_num_threads(),
+        "aten_cpu_model": cpu_model(),
         "lights": LIGHTS, "view0": VIEW0, "intensity0": INT0, "view1": VIEW1, "intensity1": INT1,
         "sets": {},
     }
@@ -525,6 +553,7 @@ def main():
     example_blend_set(manifest)
     grad_param_set(manifest)
     edge_set(manifest)
+    fresh_set(manifest)
     with open(os.path.join(GOLDEN, "MANIFEST.json"), "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     tot = sum(os.path.getsize(os.path.join(GOLDEN, f)) for f in os.listdir(GOLDEN))
@@ -539,5 +568,7 @@ if __name__ == "__main__":
         only_grad_params()
     elif sys.argv[1:3] == ["--only", "edge"]:
         only("edge", edge_set)
+    elif sys.argv[1:3] == ["--only", "fresh"]:
+        only("fresh", fresh_set)
     else:
         main()

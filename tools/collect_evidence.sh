@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-timeout 400 python3 "$R/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 400 python3 "$R/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cat "$OUT/bench.json"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
     python3 "$R/bench.py" --no-cpu-baseline > "$OUT/trace.log" 2>&1

@@ -32,10 +32,10 @@ headline)
     ;;
 configs)
     cd /tmp
-    timeout 300 python3 "$R/bench.py" --config 1 > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err"
+    timeout 300 python3 "$R/bench.py" --full --config 1 > "$OUT/bench_c1.json" 2> "$OUT/bench_c1.err"
     echo "config 1 done: $(head -c 300 "$OUT/bench_c1.json")"
     for c in 3 4 5; do
-        timeout 300 python3 "$R/bench.py" --config $c > "$OUT/bench_c$c.json" 2> "$OUT/bench_c$c.err"
+        timeout 300 python3 "$R/bench.py" --full --config $c > "$OUT/bench_c$c.json" 2> "$OUT/bench_c$c.err"
         timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_c$c" -o run -- \
             python3 "$R/bench.py" --config $c --no-cpu-baseline > "$OUT/trace_c$c.log" 2>&1
         echo "config $c done: $(head -c 300 "$OUT/bench_c$c.json")"

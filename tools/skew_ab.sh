@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-for i in 1 2; do for sk in 0 4352; do PBR_PLANE_SKEW_BYTES=$sk python3 bench.py --no-cpu-baseline --steps 300 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('skew $sk', d['value'], d['value_cold'], d['roofline']['kernel_us_steady'], d['roofline']['kernel_us_cold'])"; done; done
+for i in 1 2; do for sk in 0 4352; do PBR_PLANE_SKEW_BYTES=$sk python3 bench.py --full --no-cpu-baseline --steps 300 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('skew $sk', d['value'], d['value_cold'], d['roofline']['kernel_us_steady'], d['roofline']['kernel_us_cold'])"; done; done
 python3 - <<'PY'
 import torch, sys, os
 sys.path.insert(0,'.')
