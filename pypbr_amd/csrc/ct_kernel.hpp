@@ -74,7 +74,8 @@ struct KArgs {
     int32_t fold_log2, fold_reps;   // tiled maps: rows visited in bands of (1 << fold_log2) source rows, all fold_reps vertical repeats of a band back to back (0 = off)
     FastDiv div_reps;        // band visit / fold_reps
     int32_t xpose;           // 8-pixel lanes, fp32 result: exchange the lanes' 16-byte pieces through LDS before storing
-    int32_t sbase;           // every tile lies inside one material and every plane is < 4 GiB: scalar plane addresses (plane_at)
+    int32_t sbase;           // every tile lies inside one material and every lane offset the launch forms is < 2^30 elements: scalar plane addresses (plane_at);
+                             // repeat kernels: offsets into the first repeat of source rows [0, map_h) -- map_h * out_W and map_h * map_w, also for thin bands
     FastDiv div_h;           // row / H
     FastDiv div_tx;          // tile / tiles_x
     int32_t tiled;           // maps are (map_h, map_w) and repeat over the (H_total, W) output (MaterialBase.tile)
@@ -827,7 +828,7 @@ __device__ __forceinline__ void repeat_forward_body(const KArgs &a, Prepare &&pr
 #pragma unroll
     for (int g = 0; g < NG; ++g) material_terms<WF, VEC, R>(t, g, V, pt[g]);
 
-    const uint32_t lane_out = (uint32_t)(p.y * a.out_W + p.x);              // inside the first repeat; < 2^30 when p.sb (fill_args)
+    const uint32_t lane_out = (uint32_t)p.y * (uint32_t)a.out_W + (uint32_t)p.x;   // inside the first repeat; < map_h * out_W < 2^30 when p.sb (fill_repeat_args)
     // `out` holds the rows [y_offset, y_offset + H_total) of the tiled image (all of it, or a multi-GPU shard's band): a repeat whose
     // row falls outside is skipped; the others land y_offset rows higher.  (rep may be negative; rep + the lane's part never is.)
     auto in_band = [&](int ry) { const int yy = p.y + ry * PH - a.y_offset; return yy >= 0 && yy < a.H_total; };

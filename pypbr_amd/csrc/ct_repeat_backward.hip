@@ -73,7 +73,10 @@ static int fill_repeat_backward(const pbr_render_desc *d, KArgs &k) {
     k.y_offset = d->y_offset; k.H_total = d->height;     // `upstream` holds the rows [y_offset, y_offset + height) of the tiled image
     k.map_h = d->map_height; k.win_y0 = thin ? d->y_offset % d->map_height : 0;
     k.o_cs = (int64_t)d->map_height * d->map_width; k.o_bs = 3 * k.o_cs;      // the gradient planes: dense, map-sized
-    if ((int64_t)d->height * d->width >= (1ll << 30)) k.sbase = 0;           // the lane's offset inside the output's first repeat must fit 32 bits of bytes
+    // Scalar plane addresses need every lane offset below 2^30 elements: the upstream's p.y * out_W + p.x inside the first repeat, the texels'
+    // and gradients' p.y * map_w + p.x, with p.y a SOURCE row -- anywhere in [0, map_h) for a thin band (fill_args saw only the band's rows).
+    const int64_t rows = thin ? d->map_height : d->height;
+    if (rows * d->width >= (1ll << 30) || (int64_t)d->map_height * d->map_width >= (1ll << 30)) k.sbase = 0;
     return PBR_OK;
 }
 

@@ -185,7 +185,7 @@ __device__ __forceinline__ void repeat_backward_body(const KArgs &a, const BArgs
     // Positions k = ry * rep_x + rx in pbr_fold_gradient's order; (ry, rx) are wave-uniform (scalar plane addresses need that), whether
     // a repeat's row lies inside the band `gout` holds -- rows [y_offset, y_offset + H_total) of the tiled image -- is the lane's own test.
     const int n_pos = a.rep_y * a.rep_x;
-    const uint32_t lane_out = (uint32_t)(p.y * a.out_W + p.x);                  // inside the first repeat; < 2^30 when p.sb (launch_repeat_backward)
+    const uint32_t lane_out = (uint32_t)p.y * (uint32_t)a.out_W + (uint32_t)p.x;   // inside the first repeat; < map_h * out_W < 2^30 when p.sb (fill_repeat_backward)
     auto in_band = [&](int ry) { const int yy = p.y + ry * PH - a.y_offset; return yy >= 0 && yy < a.H_total; };
     auto load_upstream = [&](int k, float (&go)[3][VEC]) {
         const int ry = k / a.rep_x, rx = k - ry * a.rep_x;

@@ -55,7 +55,11 @@ void fill_repeat_args(const pbr_render_desc *d, KArgs &k) {
     k.out_W = d->width; k.out_Ht = d->height_total;
     k.y_offset = d->y_offset; k.H_total = d->height;     // the rows [y_offset, y_offset + H_total) of the tiled image are what `out` holds (KArgs: out_Ht)
     k.map_h = d->map_height; k.win_y0 = thin ? d->y_offset % d->map_height : 0;
-    if (plane >= (1ll << 30)) k.sbase = 0;               // the lane's offset inside the result's first repeat must fit 32 bits of bytes
+    // Scalar plane addresses need every lane offset below 2^30 elements (32 bits of bytes): the result's is p.y * out_W + p.x inside
+    // the first repeat, the texels' p.y * map_w + p.x, with p.y a SOURCE row -- anywhere in [0, map_h) for a thin band's cyclic window
+    // (fill_args above saw only the band's rows), below the band's height otherwise (a band of at least a period holds map_h rows).
+    const int64_t rows = thin ? d->map_height : d->height;
+    if (rows * d->width >= (1ll << 30) || (int64_t)d->map_height * d->map_width >= (1ll << 30)) k.sbase = 0;
 }
 
 }  // namespace pbr
