@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as TF
 
 import torch_oracle as O
+from test_gpu_write_guards import Guards
 
 pytestmark = pytest.mark.gpu
 
@@ -168,7 +169,8 @@ def test_resize_gradient_forms_agree_with_float64_autograd(shape, size, antialia
     g = torch.Generator().manual_seed(14)
     (h, w), (ho, wo) = shape, size
     gout = (torch.rand(3, ho, wo, generator=g) - 0.5).cuda()
-    ws = torch.empty(max(1, lib.pbr_resize_backward_workspace_bytes(3, h, w, ho, wo) // 4), device="cuda")
+    gd = Guards()                                       # the workspace: exactly the queried bytes, inside a guard band
+    ws = gd.workspace(lib.pbr_resize_backward_workspace_bytes(3, h, w, ho, wo))
     stream = torch.cuda.current_stream().cuda_stream
     got = {}
     try:
@@ -177,6 +179,7 @@ def test_resize_gradient_forms_agree_with_float64_autograd(shape, size, antialia
             gin = torch.full((3, h, w), float("nan"), device="cuda")
             N.check(lib.pbr_resize_bilinear_backward(gout.data_ptr(), gin.data_ptr(), 3, h, w, ho, wo, int(antialias), ws.data_ptr(), stream))
             got[up2] = gin
+            gd.check(up2)
     finally:
         lib.pbr_set_tuning(N.TUNE_RESIZE_UP2, 1)
     x = torch.zeros(1, 3, h, w, dtype=torch.float64, requires_grad=True)
@@ -202,7 +205,8 @@ def test_gradient_of_an_upscale_in_registers(shape, size):
     g = torch.Generator().manual_seed(15)
     (h, w), (ho, wo) = shape, size
     gout = (torch.rand(3, ho, wo, generator=g) - 0.5).cuda()
-    ws = torch.empty(max(1, lib.pbr_resize_backward_workspace_bytes(3, h, w, ho, wo) // 4), device="cuda")
+    gd = Guards()                                       # the workspace: exactly the queried bytes, inside a guard band
+    ws = gd.workspace(lib.pbr_resize_backward_workspace_bytes(3, h, w, ho, wo))
     stream = torch.cuda.current_stream().cuda_stream
     got = {}
     try:
@@ -211,6 +215,7 @@ def test_gradient_of_an_upscale_in_registers(shape, size):
             gin = torch.full((3, h, w), float("nan"), device="cuda")
             N.check(lib.pbr_resize_bilinear_backward(gout.data_ptr(), gin.data_ptr(), 3, h, w, ho, wo, 1, ws.data_ptr(), stream))
             got[up2] = gin
+            gd.check(up2)
     finally:
         lib.pbr_set_tuning(N.TUNE_RESIZE_UP2, 1)
     x = torch.zeros(1, 3, h, w, dtype=torch.float64, requires_grad=True)

@@ -9,6 +9,7 @@ import torch
 import blend_oracle as BO
 import torch_oracle as O
 from test_gpu_blend_backward import _check, _material
+from test_gpu_write_guards import Guards
 
 pytestmark = pytest.mark.gpu
 
@@ -420,11 +421,12 @@ def test_row_walk_downscale_equals_the_strip_kernel_and_aten():
     def run(x, ho, wo, knob):
         planes, hi, wi = x.shape
         out = torch.full((planes, ho, wo), float("nan"), device="cuda")
-        ws = torch.empty(max(1, lib.pbr_resize_workspace_bytes(planes, hi, wo) // 4), device="cuda")
+        gd = Guards()                                   # the workspace: exactly the queried bytes, inside a guard band
+        ws = gd.workspace(lib.pbr_resize_workspace_bytes(planes, hi, wo))
         lib.pbr_set_tuning(N.TUNE_RESIZE_UP2, knob)
         form = lib.pbr_resize_form(x.data_ptr(), out.data_ptr(), planes, hi, wi, ho, wo, 1, ws.data_ptr())
         N.check(lib.pbr_resize_bilinear(x.data_ptr(), out.data_ptr(), planes, hi, wi, ho, wo, 1, ws.data_ptr(), stream))
-        torch.cuda.synchronize()
+        gd.check((planes, hi, wi, ho, wo, knob))
         return out, form
 
     shapes = [(1, 64, 64, 40, 40), (3, 512, 512, 341, 341), (2, 1024, 1024, 100, 100), (1, 1000, 1024, 333, 700), (3, 256, 2048, 77, 1365),
@@ -470,7 +472,7 @@ def test_row_walk_downscale_equals_the_strip_kernel_and_aten():
                                     (torch.rand(1, 512, 512, generator=g).cuda(), 128, 128, 1, N.RESIZE_BAND_WALK), (torch.rand(1, 2048, 512, generator=g).cuda(), 2047, 100, 1, N.RESIZE_STRIP), (torch.rand(1, 2048, 2048, generator=g).cuda(), 64, 64, 1, N.RESIZE_TWO_PASS)):
             planes, hi, wi = x.shape
             out = torch.empty(planes, ho, wo, device="cuda")
-            ws = torch.empty(max(1, lib.pbr_resize_workspace_bytes(planes, hi, wo) // 4), device="cuda")
+            ws = Guards().workspace(lib.pbr_resize_workspace_bytes(planes, hi, wo))
             lib.pbr_set_tuning(N.TUNE_RESIZE_UP2, 2)
             assert lib.pbr_resize_form(x.data_ptr(), out.data_ptr(), planes, hi, wi, ho, wo, aa, ws.data_ptr()) == want, (hi, wi, ho, wo, aa)
     finally:
