@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PBR_HIP_ABI_VERSION 8      /* 8: pbr_cook_torrance_blend_backward over tiled maps (map-sized gradients), pbr_blend_backward_serves; 7: folded gradients of tiled maps (pbr_cook_torrance_backward_folded), the loss step over tiled maps, 12 schedule knobs (was 23); 6: pbr_render_desc.tuning (per-call schedule knobs; pbr_set_tuning demoted to a process-global test hook); 5: pbr_render_desc.device_params (view / light / intensity read from device memory); 4: light_size follows Python truthiness, gradients of the map ops */
+#define PBR_HIP_ABI_VERSION 9      /* 9: the normal-map operations (pbr_normal_from_height, pbr_normal_transform and their gradients); 8: pbr_cook_torrance_blend_backward over tiled maps (map-sized gradients), pbr_blend_backward_serves; 7: folded gradients of tiled maps (pbr_cook_torrance_backward_folded), the loss step over tiled maps, 12 schedule knobs (was 23); 6: pbr_render_desc.tuning (per-call schedule knobs; pbr_set_tuning demoted to a process-global test hook); 5: pbr_render_desc.device_params (view / light / intensity read from device memory); 4: light_size follows Python truthiness, gradients of the map ops */
 #define PBR_MAX_LIGHTS 16
 
 /* ---- status codes (negative = caller error, positive = HIP runtime error code + 1000) */
@@ -372,6 +372,44 @@ int pbr_fold_gradient_typed(const void *src, void *dst, int32_t batch, int32_t c
  */
 int pbr_decode_normal(const void *src, void *dst, int32_t channels, int64_t pixels, int dtype,
                       void *workspace, void *stream);
+
+/*
+ * The normal-map operations of pypbr/utils/functions.py:69-177 and pypbr/materials/base.py:673-729 on the device.  Height
+ * [batch][1][height][width], normals [batch][3][height][width]; rows dense, strides in ELEMENTS (batch_stride between images,
+ * plane_stride between the x / y / z planes), any non-negative values.  Forwards: `dtype` PBR_F32 | PBR_F16 storage, fp32 arithmetic
+ * in the reference's rounding order (IEEE sqrt and division).  Backwards: fp32.  No workspace; a bad shape, stride or dtype returns
+ * PBR_ERR_SHAPE / PBR_ERR_DTYPE before anything is launched.
+ *
+ * pbr_normal_from_height: utils.compute_normal_from_height, functions.py:123-177 (and MaterialBase.compute_normal_from_height,
+ * base.py:708-729).  Zero padding at every image's border (the images of a batch never see each other):
+ *   gx = h(y,x-1) - h(y,x+1), gy = h(y-1,x) - h(y+1,x), a = -(gx scale), b = -(gy scale) (OpenGL, directx 0) | +(gy scale) (DirectX),
+ *   n = (a, b, 1) / |(a, b, 1)|.  No clamps: a NaN height gives NaN exactly where the reference's does.
+ */
+int pbr_normal_from_height(const void *height, int64_t height_batch_stride, void *normal, int64_t normal_batch_stride,
+                           int64_t normal_plane_stride, int32_t batch, int32_t height_px, int32_t width, float scale, int32_t directx,
+                           int dtype, void *stream);
+/* Gradient of pbr_normal_from_height w.r.t. the height (what autograd derives from functions.py:146-175): g_v = (g_n - n (n . g_n)) / |v|
+ * per pixel, then the transposed stencil of (g_a, g_b).  fp32; `height` is the forward's input. */
+int pbr_normal_from_height_backward(const void *height, int64_t height_batch_stride, const void *grad_normal, int64_t grad_batch_stride,
+                                    int64_t grad_plane_stride, void *grad_height, int64_t grad_height_batch_stride, int32_t batch,
+                                    int32_t height_px, int32_t width, float scale, int32_t directx, void *stream);
+/*
+ * The per-pixel transforms: (x, y) <- M (x, y) with M = [[m00, m01], [m10, m11]], z kept, then, when `renormalize`, F.normalize
+ * (v / max(|v|, 1e-12)).  `pixels` = height * width per image; `dst == src` is allowed (the in-place utilities).
+ *   utils.rotate_normals, functions.py:69-108:                    M = R(angle), renormalised
+ *   utils.invert_normal, functions.py:111-120 (base.py:673-687): M = diag(1, -1), not renormalised (an exact negation)
+ *   MaterialBase.adjust_normal_strength, base.py:689-706:         M = f I, renormalised
+ * A diagonal M scales x and y by one multiplication each, as the reference's in-place products do.
+ */
+int pbr_normal_transform(const void *src, int64_t src_batch_stride, int64_t src_plane_stride, void *dst, int64_t dst_batch_stride,
+                         int64_t dst_plane_stride, int32_t batch, int64_t pixels, float m00, float m01, float m10, float m11,
+                         int32_t renormalize, int dtype, void *stream);
+/* Gradient of pbr_normal_transform w.r.t. its source: g_v = renormalize ? (g - n (n . g)) / |v| : g, g_xy = M^T g_v_xy, g_z = g_v_z.
+ * fp32; `src` is the forward's input (not its result). */
+int pbr_normal_transform_backward(const void *src, int64_t src_batch_stride, int64_t src_plane_stride, const void *grad_out,
+                                  int64_t grad_batch_stride, int64_t grad_plane_stride, void *grad_in, int64_t grad_in_batch_stride,
+                                  int64_t grad_in_plane_stride, int32_t batch, int64_t pixels, float m00, float m01, float m10, float m11,
+                                  int32_t renormalize, void *stream);
 
 /*
  * MaterialBase._to_tensor for PIL images, base.py:143-164, on the device: an image's own samples -- uint8 (`bits` 8; torchvision's

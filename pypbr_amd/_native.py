@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PBR_HIP_LIB") or os.path.join(_HERE, "libpbr_hip.so")   # env override: A/B of two builds
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 RESIZE_TWO_PASS, RESIZE_STRIP, RESIZE_TWO_TAP, RESIZE_BAND_WALK, RESIZE_ROW_WALK = range(5)      # pbr_resize_form
 MAX_LIGHTS = 16
 
@@ -42,6 +42,7 @@ EXPORTS = (
     "pbr_blend_sigmoid_mask_backward", "pbr_cook_torrance_blend_backward", "pbr_fold_gradient_typed",
     "pbr_mse_step_workspace_bytes", "pbr_cook_torrance_mse_step", "pbr_scale_by_device_scalar", "pbr_scale_list_by_device_scalar", "pbr_device_params_bytes", "pbr_prepare_device_params", "pbr_tuning_init", "pbr_build_id", "pbr_unpack_image",
     "pbr_backward_folded_workspace_bytes", "pbr_cook_torrance_backward_folded",
+    "pbr_normal_from_height", "pbr_normal_from_height_backward", "pbr_normal_transform", "pbr_normal_transform_backward",
 )
 
 
@@ -185,6 +186,13 @@ def lib():
     L.pbr_decode_normal_backward.argtypes = [vp, vp, vp, i32, i64, vp, vp]
     L.pbr_unpack_image.argtypes = [vp, i32, i32, i32, i32, i64, i64, i64, vp, i32, vp]
     L.pbr_unpack_image.restype = ctypes.c_int
+    f32 = ctypes.c_float
+    L.pbr_normal_from_height.argtypes = [vp, i64, vp, i64, i64, i32, i32, i32, f32, i32, ctypes.c_int, vp]
+    L.pbr_normal_from_height_backward.argtypes = [vp, i64, vp, i64, i64, vp, i64, i32, i32, i32, f32, i32, vp]
+    L.pbr_normal_transform.argtypes = [vp, i64, i64, vp, i64, i64, i32, i64, f32, f32, f32, f32, i32, ctypes.c_int, vp]
+    L.pbr_normal_transform_backward.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i64, f32, f32, f32, f32, i32, vp]
+    for name in ("pbr_normal_from_height", "pbr_normal_from_height_backward", "pbr_normal_transform", "pbr_normal_transform_backward"):
+        getattr(L, name).restype = ctypes.c_int
     L.pbr_decode_normal_backward.restype = ctypes.c_int
     for name in ("pbr_srgb_to_linear", "pbr_linear_to_srgb", "pbr_metallic_to_specular",
                  "pbr_specular_to_metallic", "pbr_decode_normal", "pbr_abi_version", "pbr_set_tuning",

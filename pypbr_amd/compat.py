@@ -5,9 +5,12 @@ pypbr_amd modules, so that e.g. examples/example_brdf.py's
     from pypbr.models import CookTorranceBRDF
     from pypbr.io import load_material_from_folder
 
-resolve to the MI355X implementation.  Only the Cook-Torrance path and the calls either side of it
-(load, blend, resize, tile) exist here; everything else of PyPBR (transforms, authoring utilities,
-...) is out of scope and raises ImportError/AttributeError as an absent module would."""
+resolve to the MI355X implementation.  The Cook-Torrance path and the calls either side of it
+(load, blend, resize, tile) exist here, and so do the normal-map operations: `pypbr.utils.compute_normal_from_height`,
+`rotate_normals`, `invert_normal` and the material methods `compute_normal_from_height`,
+`adjust_normal_strength`, `invert_normal` resolve through the aliases above.  Everything else of PyPBR
+(transforms, compute_height_from_normal, crop / rotate / flips / roll, saving, ...) is out of scope and raises
+ImportError/AttributeError as an absent module would."""
 import sys
 import types
 

@@ -361,6 +361,69 @@ Tensor resize_backward(const Tensor &grad_out, int64_t h_in, int64_t w_in, bool 
     return gin;
 }
 
+// utils.compute_normal_from_height (functions.py:123-177): height (H,W) | (1,H,W) -> (3,H,W), (B,1,H,W) -> (B,3,H,W)
+Tensor height_as_batch(const Tensor &height, const char *what) {
+    TORCH_CHECK(height.is_cuda(), what, " needs a tensor on a ROCm device; there is no CPU path");
+    TORCH_CHECK_VALUE(height.dim() >= 2 && height.dim() <= 4, what, ": height must be (H,W), (1,H,W) or (B,1,H,W)");
+    TORCH_CHECK_VALUE(height.dim() == 2 || height.size(-3) == 1, what, ": height map must have 1 channel");
+    Tensor h = height.contiguous();
+    while (h.dim() < 4) h = h.unsqueeze(0);
+    return h;
+}
+
+Tensor normal_from_height(const Tensor &height, double scale, bool directx) {
+    const Tensor h = height_as_batch(height, "pbr_hip::normal_from_height");
+    const c10::DeviceGuard guard(h.device());
+    const int64_t B = h.size(0), H = h.size(2), W = h.size(3);
+    Tensor out = at::empty({B, 3, H, W}, h.options());
+    check_status(pbr_normal_from_height(h.data_ptr(), h.stride(0), out.data_ptr(), out.stride(0), out.stride(1), (int32_t)B, (int32_t)H, (int32_t)W,
+                                        (float)scale, directx ? 1 : 0, dtype_code(h, "height"), current_stream(h)), "pbr_hip::normal_from_height");
+    return height.dim() == 4 ? out : out.squeeze(0);
+}
+
+Tensor normal_from_height_backward(const Tensor &height, const Tensor &grad_normal, double scale, bool directx) {
+    const Tensor h = height_as_batch(height, "pbr_hip::normal_from_height_backward").to(at::kFloat);
+    const c10::DeviceGuard guard(h.device());
+    const int64_t B = h.size(0), H = h.size(2), W = h.size(3);
+    const Tensor g = grad_normal.to(at::kFloat).contiguous().reshape({B, 3, H, W});
+    Tensor gh = at::empty({B, 1, H, W}, h.options());
+    check_status(pbr_normal_from_height_backward(h.data_ptr(), h.stride(0), g.data_ptr(), g.stride(0), g.stride(1), gh.data_ptr(), gh.stride(0),
+                                                 (int32_t)B, (int32_t)H, (int32_t)W, (float)scale, directx ? 1 : 0, current_stream(h)),
+                 "pbr_hip::normal_from_height_backward");
+    return gh.reshape(height.sizes());
+}
+
+// rotate_normals / invert_normal / adjust_normal_strength (functions.py:69-120, base.py:689-706): (3,H,W) | (B,3,H,W)
+Tensor normal_as_batch(const Tensor &normal, const char *what) {
+    TORCH_CHECK(normal.is_cuda(), what, " needs a tensor on a ROCm device; there is no CPU path");
+    TORCH_CHECK_VALUE((normal.dim() == 3 || normal.dim() == 4) && normal.size(-3) == 3, what, ": normal map must be (3,H,W) or (B,3,H,W)");
+    Tensor n = normal.contiguous();
+    return n.dim() == 4 ? n : n.unsqueeze(0);
+}
+
+Tensor normal_transform(const Tensor &normal, double m00, double m01, double m10, double m11, bool renormalize) {
+    const Tensor n = normal_as_batch(normal, "pbr_hip::normal_transform");
+    const c10::DeviceGuard guard(n.device());
+    const int64_t B = n.size(0), P = n.size(2) * n.size(3);
+    Tensor out = at::empty_like(n);
+    check_status(pbr_normal_transform(n.data_ptr(), n.stride(0), n.stride(1), out.data_ptr(), out.stride(0), out.stride(1), (int32_t)B, P,
+                                      (float)m00, (float)m01, (float)m10, (float)m11, renormalize ? 1 : 0, dtype_code(n, "normal"),
+                                      current_stream(n)), "pbr_hip::normal_transform");
+    return normal.dim() == 4 ? out : out.squeeze(0);
+}
+
+Tensor normal_transform_backward(const Tensor &normal, const Tensor &grad_out, double m00, double m01, double m10, double m11, bool renormalize) {
+    const Tensor n = normal_as_batch(normal, "pbr_hip::normal_transform_backward").to(at::kFloat);
+    const c10::DeviceGuard guard(n.device());
+    const int64_t B = n.size(0), P = n.size(2) * n.size(3);
+    const Tensor g = grad_out.to(at::kFloat).contiguous().reshape(n.sizes());
+    Tensor gi = at::empty_like(n);
+    check_status(pbr_normal_transform_backward(n.data_ptr(), n.stride(0), n.stride(1), g.data_ptr(), g.stride(0), g.stride(1), gi.data_ptr(),
+                                               gi.stride(0), gi.stride(1), (int32_t)B, P, (float)m00, (float)m01, (float)m10, (float)m11,
+                                               renormalize ? 1 : 0, current_stream(n)), "pbr_hip::normal_transform_backward");
+    return gi.reshape(normal.sizes());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(pbr_hip, m) {
@@ -385,6 +448,10 @@ TORCH_LIBRARY(pbr_hip, m) {
           "bool albedo_is_srgb) -> (Tensor, Tensor)");
     m.def("resize(Tensor texture, int h_out, int w_out, bool antialias) -> Tensor");
     m.def("resize_backward(Tensor grad_out, int h_in, int w_in, bool antialias) -> Tensor");
+    m.def("normal_from_height(Tensor height, float scale, bool directx) -> Tensor");
+    m.def("normal_from_height_backward(Tensor height, Tensor grad_normal, float scale, bool directx) -> Tensor");
+    m.def("normal_transform(Tensor normal, float m00, float m01, float m10, float m11, bool renormalize) -> Tensor");
+    m.def("normal_transform_backward(Tensor normal, Tensor grad_out, float m00, float m01, float m10, float m11, bool renormalize) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(pbr_hip, CUDA, m) {       // the CUDA dispatch key is the HIP device on a ROCm build of torch
@@ -400,4 +467,8 @@ TORCH_LIBRARY_IMPL(pbr_hip, CUDA, m) {       // the CUDA dispatch key is the HIP
     m.impl("diffuse_specular_to_basecolor_metallic_backward", &diffuse_specular_to_basecolor_metallic_backward);
     m.impl("resize", &resize);
     m.impl("resize_backward", &resize_backward);
+    m.impl("normal_from_height", &normal_from_height);
+    m.impl("normal_from_height_backward", &normal_from_height_backward);
+    m.impl("normal_transform", &normal_transform);
+    m.impl("normal_transform_backward", &normal_transform_backward);
 }

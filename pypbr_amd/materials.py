@@ -458,6 +458,47 @@ class MaterialBase:
             self.albedo_is_srgb = True
         return self
 
+    # -- normal-map operations (base.py:673-729), returning self; csrc/normal_ops.hip.  The new normal map is stored as it comes out of the
+    # kernel, never through _settle / _process_normal_map (upstream writes _maps["normal"] directly: a flat height's (0, 0, 1) has no
+    # negative value, and the "already signed?" decode would turn it into (-1, -1, 1) / sqrt(3)); it stays on the compute device.
+    def invert_normal(self):
+        """base.py:673-687: y of the normal map negated (no renormalisation) and normal_convention swapped -- the swap happens
+        with no normal map too."""
+        self.materialize_blend()
+        if self._raw.get("normal") is not None:
+            n = self._resident(keep=True)["normal"]
+            in_place = not (n.requires_grad and torch.is_grad_enabled()) and F_._rows_dense(n) is n    # as upstream's utils.invert_normal
+            self._raw["normal"] = F_.transform_normals(n, ((1.0, 0.0), (0.0, -1.0)), False, out=n if in_place else None)
+        self.normal_convention = (NormalConvention.DIRECTX if self.normal_convention == NormalConvention.OPENGL
+                                  else NormalConvention.OPENGL)
+        return self
+
+    def adjust_normal_strength(self, strength_factor: float):
+        """base.py:689-706: x and y of the normal map times `strength_factor`, renormalised.  The map is replaced by a new tensor
+        (upstream also scales the old tensor in place first: INTEGRATION.md, numerical differences)."""
+        self.materialize_blend()
+        if self._raw.get("normal") is not None:
+            f = float(strength_factor)
+            self._raw["normal"] = F_.transform_normals(self._resident(keep=True)["normal"], ((f, 0.0), (0.0, f)), True)
+        return self
+
+    def compute_normal_from_height(self, scale: float = 1.0):
+        """base.py:708-729: the normal map computed from the height map in this material's normal_convention.  A pending lazy blend
+        and a pending tile(n, lazy=True) are carried out first: upstream tiles and then differentiates, so the pixels along a seam
+        see the neighbouring tile.  A height that requires grad keeps its graph."""
+        directx = F_._directx(self.normal_convention)           # argument errors before any device work
+        self.materialize_blend()
+        if self._raw.get("height") is None:
+            raise ValueError("Height map is required to compute normals.")
+        height = self._raw["height"]
+        if height.dim() == 3 and height.shape[0] != 1:
+            raise ValueError("Height map must have 1 channel, got %d" % height.shape[0])
+        self.materialize_tile()
+        maps = self._resident(keep=True)                        # samples of a PNG become upstream's floats (8 / 16 bit) on the way
+        self._raw["normal"] = F_.normal_from_height(maps["height"], scale, "directx" if directx else "opengl")
+        self.__dict__["_raw_normal"] = False
+        return self
+
     # -- the two calls around the BRDF in examples/example_brdf.py:11 (SURVEY.md 8f, N1)
     def resize(self, size, antialias: bool = True):
         """Resize every map (base.py:490-504): bilinear, antialiased by default; in place, returns self.  All float32 (C,H,W) maps

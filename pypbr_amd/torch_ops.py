@@ -133,6 +133,34 @@ def _register():
         return torch.ops.pbr_hip.resize_backward(grad_out, h, w, antialias), None, None, None
     lib.register_autograd("pbr_hip::resize", resize_backward, setup_context=resize_setup)
 
+    # the normal-map operations (functions.py:69-177, base.py:673-729): fp32 gradients through their backward operators
+    def _normals_of(height):
+        return height.new_empty((3,) + tuple(height.shape[-2:]) if height.dim() < 4 else (height.shape[0], 3) + tuple(height.shape[-2:]))
+    lib.register_fake("pbr_hip::normal_from_height")(lambda height, scale, directx: _normals_of(height))
+    lib.register_fake("pbr_hip::normal_from_height_backward")(
+        lambda height, grad_normal, scale, directx: height.new_empty(height.shape, dtype=torch.float32))
+    lib.register_fake("pbr_hip::normal_transform")(lambda normal, m00, m01, m10, m11, renormalize: torch.empty_like(normal))
+    lib.register_fake("pbr_hip::normal_transform_backward")(
+        lambda normal, grad_out, m00, m01, m10, m11, renormalize: torch.empty_like(normal, dtype=torch.float32))
+
+    def nfh_setup(ctx, inputs, output):
+        ctx.save_for_backward(inputs[0])
+        ctx.args = tuple(inputs[1:])
+
+    def nfh_backward(ctx, grad_out):
+        (height,) = ctx.saved_tensors
+        return torch.ops.pbr_hip.normal_from_height_backward(height, grad_out, *ctx.args).to(height.dtype), None, None
+    lib.register_autograd("pbr_hip::normal_from_height", nfh_backward, setup_context=nfh_setup)
+
+    def transform_setup(ctx, inputs, output):
+        ctx.save_for_backward(inputs[0])
+        ctx.args = tuple(inputs[1:])
+
+    def transform_backward(ctx, grad_out):
+        (normal,) = ctx.saved_tensors
+        return (torch.ops.pbr_hip.normal_transform_backward(normal, grad_out, *ctx.args).to(normal.dtype),) + (None,) * 5
+    lib.register_autograd("pbr_hip::normal_transform", transform_backward, setup_context=transform_setup)
+
     names = ("albedo", "normal", "roughness", "metallic", "specular", "view_dir", "lights", "intensities")
 
     def setup_context(ctx, inputs, output):
