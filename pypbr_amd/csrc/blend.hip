@@ -191,16 +191,6 @@ __global__ __launch_bounds__(256) void gradient_mask_kernel(float *__restrict__ 
     }
 }
 
-static inline unsigned blend_grid(int64_t items) {
-    const int64_t blocks = (items + 255) / 256, cap = 256 * 16;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
-static inline int blend_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
-}
-
 }  // namespace pbr
 
 extern "C" {
@@ -213,12 +203,11 @@ int pbr_blend_maps(const void *map1, const void *map2, const void *mask, void *o
     if (is_normal && channels != 3) return PBR_ERR_CHANNELS;
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto a = static_cast<const float *>(map1), b = static_cast<const float *>(map2), m = static_cast<const float *>(mask);
-    const int vec_ok = pixels % 4 == 0 && ((reinterpret_cast<uintptr_t>(map1) | reinterpret_cast<uintptr_t>(map2) | reinterpret_cast<uintptr_t>(mask) |
-                                            reinterpret_cast<uintptr_t>(out)) & 15u) == 0;
+    const int vec_ok = pixels % 4 == 0 && is_aligned(map1, 16) && is_aligned(map2, 16) && is_aligned(mask, 16) && is_aligned(out, 16);
     const StreamShape sh = stream_shape((size_t)(vec_ok ? pixels / 4 : pixels), is_normal ? kShapeBlendNormal : kShapeBlend);
     if (is_normal) hipLaunchKernelGGL(blend_kernel<true>, dim3(sh.grid), dim3(sh.block), sh.lds, s, a, b, m, static_cast<float *>(out), 3, pixels, vec_ok);
     else hipLaunchKernelGGL(blend_kernel<false>, dim3(sh.grid), dim3(sh.block), sh.lds, s, a, b, m, static_cast<float *>(out), (int)channels, pixels, vec_ok);
-    return blend_status();
+    return launch_status();
 }
 
 int pbr_blend_sigmoid_mask(const void *prop1, const void *prop2, void *mask, int64_t n, float shift, float blend_width,
@@ -230,7 +219,7 @@ int pbr_blend_sigmoid_mask(const void *prop1, const void *prop2, void *mask, int
     hipLaunchKernelGGL(sigmoid_mask_kernel, dim3(sh.grid), dim3(sh.block), sh.lds, static_cast<hipStream_t>(stream),
                        static_cast<const float *>(prop1), static_cast<const float *>(prop2), static_cast<float *>(mask), n,
                        shift, 1.0f / (blend_width + 1e-6f));
-    return blend_status();
+    return launch_status();
 }
 
 int pbr_blend_sigmoid_mask_backward(const void *mask, const void *grad_out, void *g_prop1, void *g_prop2, int64_t n, float blend_width,
@@ -239,19 +228,19 @@ int pbr_blend_sigmoid_mask_backward(const void *mask, const void *grad_out, void
     if (!mask || !grad_out) return PBR_ERR_NULL_MAP;
     if (n < 1) return PBR_ERR_SHAPE;
     if (!g_prop1 && !g_prop2) return PBR_OK;
-    hipLaunchKernelGGL(sigmoid_mask_backward_kernel, dim3(blend_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(sigmoid_mask_backward_kernel, dim3(stream_grid(n, 16)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const float *>(mask), static_cast<const float *>(grad_out), static_cast<float *>(g_prop1),
                        static_cast<float *>(g_prop2), n, 1.0f / (blend_width + 1e-6f));
-    return blend_status();
+    return launch_status();
 }
 
 int pbr_blend_gradient_mask(void *mask, int32_t height, int32_t width, int vertical, void *stream) {
     using namespace pbr;
     if (!mask) return PBR_ERR_NULL_MAP;
     if (height < 1 || width < 1) return PBR_ERR_SHAPE;
-    hipLaunchKernelGGL(gradient_mask_kernel, dim3(blend_grid((int64_t)height * width)), dim3(256), 0,
+    hipLaunchKernelGGL(gradient_mask_kernel, dim3(stream_grid((int64_t)height * width, 16)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), static_cast<float *>(mask), (int)height, (int)width, vertical);
-    return blend_status();
+    return launch_status();
 }
 
 int pbr_blend_maps_backward(const void *map1, const void *map2, const void *mask, const void *grad_out, void *g_map1, void *g_map2,
@@ -260,15 +249,14 @@ int pbr_blend_maps_backward(const void *map1, const void *map2, const void *mask
     if (!map1 || !map2 || !mask || !grad_out) return PBR_ERR_NULL_MAP;
     if (channels < 1 || pixels < 1) return PBR_ERR_SHAPE;
     if (is_normal && channels != 3) return PBR_ERR_CHANNELS;
-    const int64_t blocks = (pixels + 255) / 256;
-    const dim3 grid((unsigned)(blocks > 256 * 16 ? 256 * 16 : blocks));
+    const dim3 grid(stream_grid(pixels, 16));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const float *a = static_cast<const float *>(map1), *b = static_cast<const float *>(map2), *k = static_cast<const float *>(mask);
     const float *g = static_cast<const float *>(grad_out);
     float *ga = static_cast<float *>(g_map1), *gb = static_cast<float *>(g_map2), *gk = static_cast<float *>(g_mask);
     bool vec = pixels % 4 == 0;
     for (const void *p : {map1, map2, mask, grad_out, (const void *)g_map1, (const void *)g_map2, (const void *)g_mask})
-        if (p && (reinterpret_cast<uintptr_t>(p) & 15u)) vec = false;
+        if (p && !is_aligned(p, 16)) vec = false;
     if (vec) {
         const StreamShape sh = stream_shape((size_t)(pixels / 4), kShapeBlendBwd);
         if (is_normal) hipLaunchKernelGGL((blend_backward_kernel<true, 4>), dim3(sh.grid), dim3(sh.block), sh.lds, s, a, b, k, g, ga, gb, gk, (int)channels, pixels, accumulate_mask);
@@ -278,8 +266,7 @@ int pbr_blend_maps_backward(const void *map1, const void *map2, const void *mask
     } else {
         hipLaunchKernelGGL((blend_backward_kernel<false, 1>), grid, dim3(256), 0, s, a, b, k, g, ga, gb, gk, (int)channels, pixels, accumulate_mask);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -82,16 +82,7 @@ static KernelEntry pick_kernel(const pbr_render_desc *d, int vec) {
     }
     std::snprintf(name, sizeof(name), "ct_%s_%s_%s_%s_v%d%s", point ? "point" : "directional", wf_names[d->workflow],
                   idt == PBR_F32 ? "f32" : "f16", odt == PBR_F32 ? "f32" : "f16", vec, multi ? "_multi" : "");
-    KernelFn fn = nullptr;
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: fn = pick_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC>(idt, odt, vec, multi); break;
-        case 1: fn = pick_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR>(idt, odt, vec, multi); break;
-        case 2: fn = pick_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED>(idt, odt, vec, multi); break;
-        case 3: fn = pick_types<PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC>(idt, odt, vec, multi); break;
-        case 4: fn = pick_types<PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR>(idt, odt, vec, multi); break;
-        default: fn = pick_types<PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED>(idt, odt, vec, multi); break;
-    }
-    return KernelEntry{fn, name};
+    return KernelEntry{with_light_workflow(d, [&](auto L, auto W) -> KernelFn { return pick_types<L(), W()>(idt, odt, vec, multi); }), name};
 }
 
 }  // namespace pbr
@@ -143,8 +134,7 @@ int pbr_cook_torrance(const pbr_render_desc *d, void *stream) {
         const KernelEntry e = pick_kernel(d, 4);
         hipLaunchKernelGGL(e.fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), g_lds_bytes >= 0 ? (size_t)g_lds_bytes : 0,
                            static_cast<hipStream_t>(stream), k);
-        const hipError_t err = hipGetLastError();
-        return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+        return launch_status();
     }
     const int nb = batch_group(d, vec);
     if (nb) {                        // lane_pos' material index is the group of nb consecutive materials; 2 pixels per lane
@@ -166,8 +156,7 @@ int pbr_cook_torrance(const pbr_render_desc *d, void *stream) {
     if (k.xpose) lds = std::max(lds, (size_t)kXposeLdsPerWave << (k.bt_log2 - 6));     // the kernel's piece exchange needs this much
     hipLaunchKernelGGL(e.fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), lds,
                        static_cast<hipStream_t>(stream), k);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+    return launch_status();
 }
 
 int pbr_cook_torrance_autotune(const pbr_render_desc *d, void *stream, int32_t *schedule) {
@@ -179,7 +168,9 @@ int pbr_cook_torrance_autotune(const pbr_render_desc *d, void *stream, int32_t *
     float best[2] = {3.4e38f, 3.4e38f};
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return 1000 + (int)hipGetLastError();
+    hipError_t created = hipEventCreate(&e0);
+    if (created == hipSuccess) created = hipEventCreate(&e1);
+    if (created != hipSuccess) return call_status(created);
     pbr_render_desc t = *d;
     int err = PBR_OK;
     const int reps = 4;
@@ -193,7 +184,7 @@ int pbr_cook_torrance_autotune(const pbr_render_desc *d, void *stream, int32_t *
             if (he == hipSuccess) he = hipEventSynchronize(e1);
             float ms = 0.0f;
             if (he == hipSuccess) he = hipEventElapsedTime(&ms, e0, e1);
-            if (he != hipSuccess) { err = 1000 + (int)he; break; }
+            if (he != hipSuccess) { err = hip_code(he); break; }
             if (ms < best[c]) best[c] = ms;
         }
     }
@@ -248,8 +239,7 @@ int pbr_prepare_device_params(const pbr_render_desc *d, const void *view_dir, co
     hipLaunchKernelGGL(prepare_device_params_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), static_cast<const float *>(view_dir),
                        static_cast<const float *>(lights), static_cast<const float *>(intensities), (int)intensity_rows, (int)d->n_lights,
                        (int)d->light_type, hp, static_cast<DevParams *>(block));
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -26,32 +26,17 @@ static BwdFn pick_bwd_variant(int vec, bool multi) {
 
 template <bool PG>
 static BwdFn pick_bwd(const pbr_render_desc *d, int vec) {
-    const bool multi = d->n_lights > 1, point = d->light_type == PBR_LIGHT_POINT, half_maps = d->map_dtype == PBR_F16;
-#define PBR_BWD(L, W) return half_maps ? pick_bwd_variant<L, W, __half, PG>(vec, multi) : pick_bwd_variant<L, W, float, PG>(vec, multi)
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: PBR_BWD(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC);
-        case 1: PBR_BWD(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR);
-        case 2: PBR_BWD(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED);
-        case 3: PBR_BWD(PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC);
-        case 4: PBR_BWD(PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR);
-        default: PBR_BWD(PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED);
-    }
-#undef PBR_BWD
+    const bool multi = d->n_lights > 1, half_maps = d->map_dtype == PBR_F16;
+    return with_light_workflow(d, [&](auto L, auto W) -> BwdFn {
+        return half_maps ? pick_bwd_variant<L(), W(), __half, PG>(vec, multi) : pick_bwd_variant<L(), W(), float, PG>(vec, multi);
+    });
 }
 
 using BwdStreamFn = void (*)(const KArgs, const BArgs, int, int);
 static BwdStreamFn pick_bwd_stream(const pbr_render_desc *d, bool full) {
-    const bool point = d->light_type == PBR_LIGHT_POINT;
-#define PBR_BWDS(L, W) return full ? cook_torrance_backward_stream_kernel<L, W, true> : cook_torrance_backward_stream_kernel<L, W, false>
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: PBR_BWDS(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC);
-        case 1: PBR_BWDS(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR);
-        case 2: PBR_BWDS(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED);
-        case 3: PBR_BWDS(PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC);
-        case 4: PBR_BWDS(PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR);
-        default: PBR_BWDS(PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED);
-    }
-#undef PBR_BWDS
+    return with_light_workflow(d, [&](auto L, auto W) -> BwdStreamFn {
+        return full ? cook_torrance_backward_stream_kernel<L(), W(), true> : cook_torrance_backward_stream_kernel<L(), W(), false>;
+    });
 }
 
 // Rounds of the streamed backward kernel (ct_backward.hpp: its grid is rounds x the waves the chip holds at once), or 0 when
@@ -61,12 +46,12 @@ int stream_run(const pbr_render_desc *d, const void *grad_out, void *const g[5])
     if (g_bwd_run == 0 || d->map_dtype != PBR_F16 || d->n_lights != 1 || is_tiled(d) || d->width % 128) return 0;
     if ((int64_t)d->height * d->width >= (1ll << 30) || d->batch > 65535) return 0;
     auto ok = [](const pbr_map &m) {
-        return !m.data || ((reinterpret_cast<uintptr_t>(m.data) & 3u) == 0 && m.batch_stride % 2 == 0 && m.channel_stride % 2 == 0);
+        return !m.data || (is_aligned(m.data, 4) && m.batch_stride % 2 == 0 && m.channel_stride % 2 == 0);
     };
     if (!ok(d->albedo) || !ok(d->normal) || !ok(d->roughness) || !ok(d->metallic) || !ok(d->specular)) return 0;
-    if (reinterpret_cast<uintptr_t>(grad_out) & 3u) return 0;
+    if (!is_aligned(grad_out, 4)) return 0;
     for (int i = 0; i < 5; ++i)
-        if (reinterpret_cast<uintptr_t>(g[i]) & 3u) return 0;
+        if (!is_aligned(g[i], 4)) return 0;
     return g_bwd_run > 0 ? g_bwd_run : 4;          // 4096^2: 1 round 144-146 us, 2: 140-141, 4: 137-139, 6: 138, 8: 139-140 (tools/bwd_stream_ab.sh)
 }
 
@@ -119,16 +104,13 @@ static int launch_backward(const pbr_render_desc *d, const void *grad_out, void 
         const bool full = d->albedo_is_srgb && d->return_srgb && d->normal.data && g_albedo && g_normal && g_roughness &&
                           (spec ? (g_specular && d->specular_is_srgb) : (g_metallic && (d->workflow == PBR_WORKFLOW_METALLIC || d->specular_is_srgb)));
         // one-wave workgroups, kStreamWavesPerSimd of them per SIMD: the grid covers the chip `rounds` times, split over the materials
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-        const int64_t slots = (int64_t)cus * 4 * kStreamWavesPerSimd * rounds;
+        const int64_t slots = (int64_t)resident_cus() * 4 * kStreamWavesPerSimd * rounds;
         int64_t per_material = (slots + d->batch - 1) / d->batch;
         if (per_material > tiles) per_material = tiles;
         if (per_material < 1) per_material = 1;
         hipLaunchKernelGGL(pick_bwd_stream(d, full), dim3((unsigned)per_material, (unsigned)d->batch, 1), dim3(64, 1, 1), 0,
                                static_cast<hipStream_t>(stream), k, b, tiles, n_stores);
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+        return launch_status();
     }
     // Light / view adjoints: a workgroup adds its waves' sums into LDS with atomics -- with ONE wave per workgroup the
     // order of additions is fixed and the result deterministic run to run (the rows are added in fp64 in a fixed order).
@@ -140,25 +122,22 @@ static int launch_backward(const pbr_render_desc *d, const void *grad_out, void 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const BwdFn fn = g_params ? pick_bwd<true>(d, vec) : pick_bwd<false>(d, vec);
     hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), 0, st, k, b);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return 1000 + (int)err;
-    if (g_params) {
-        ParamFinishArgs f;
-        std::memset(&f, 0, sizeof(f));
-        const int n_param = 3 + 6 * d->n_lights;
-        double *stage = reinterpret_cast<double *>(static_cast<char *>(workspace) + stage_offset_bytes(d));
-        hipLaunchKernelGGL(param_grad_stage_kernel, dim3(kParamStageRows), dim3(256), 0, st, static_cast<const float *>(workspace), stage,
-                           (int)k.n_tiles, n_param);
-        f.stage = stage; f.out = static_cast<float *>(g_params);
-        f.n_rows = kParamStageRows; f.n_lights = d->n_lights; f.light_type = d->light_type;
-        f.dev = k.dev;
-        for (int c = 0; c < 3; ++c) f.view[c] = d->view_dir[c];
-        for (int i = 0; i < d->n_lights; ++i)
-            for (int c = 0; c < 3; ++c) f.lights[i][c] = d->lights[i][c];
-        hipLaunchKernelGGL(param_grad_finish_kernel, dim3(1u + 2u * (unsigned)d->n_lights), dim3(256), 0, st, f);
-        err = hipGetLastError();
-    }
-    return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+    const int e = launch_status();
+    if (e != PBR_OK || !g_params) return e;
+    ParamFinishArgs f;
+    std::memset(&f, 0, sizeof(f));
+    const int n_param = 3 + 6 * d->n_lights;
+    double *stage = reinterpret_cast<double *>(static_cast<char *>(workspace) + stage_offset_bytes(d));
+    hipLaunchKernelGGL(param_grad_stage_kernel, dim3(kParamStageRows), dim3(256), 0, st, static_cast<const float *>(workspace), stage,
+                       (int)k.n_tiles, n_param);
+    f.stage = stage; f.out = static_cast<float *>(g_params);
+    f.n_rows = kParamStageRows; f.n_lights = d->n_lights; f.light_type = d->light_type;
+    f.dev = k.dev;
+    for (int c = 0; c < 3; ++c) f.view[c] = d->view_dir[c];
+    for (int i = 0; i < d->n_lights; ++i)
+        for (int c = 0; c < 3; ++c) f.lights[i][c] = d->lights[i][c];
+    hipLaunchKernelGGL(param_grad_finish_kernel, dim3(1u + 2u * (unsigned)d->n_lights), dim3(256), 0, st, f);
+    return launch_status();
 }
 
 }  // namespace pbr

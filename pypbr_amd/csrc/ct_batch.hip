@@ -16,16 +16,7 @@ static KernelFn batch_types(int in_dt, int out_dt, int nb) {
 }
 
 KernelFn pick_batch_kernel(const pbr_render_desc *d, int nb) {
-    const bool point = d->light_type == PBR_LIGHT_POINT;
-    const int idt = d->map_dtype, odt = d->out_dtype;
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: return batch_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC>(idt, odt, nb);
-        case 1: return batch_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR>(idt, odt, nb);
-        case 2: return batch_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED>(idt, odt, nb);
-        case 3: return batch_types<PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC>(idt, odt, nb);
-        case 4: return batch_types<PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR>(idt, odt, nb);
-        default: return batch_types<PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED>(idt, odt, nb);
-    }
+    return with_light_workflow(d, [&](auto L, auto W) -> KernelFn { return batch_types<L(), W()>(d->map_dtype, d->out_dtype, nb); });
 }
 
 }  // namespace pbr

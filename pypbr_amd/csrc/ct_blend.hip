@@ -43,14 +43,13 @@ static int check_blend(const pbr_render_desc *d, const pbr_blend_desc *bl, const
 static int launch_normal_sign(const pbr_render_desc *d, const pbr_blend_desc *bl, void *workspace, hipStream_t st) {
     const bool tiled = is_tiled(d);
     const int64_t P = tiled ? (int64_t)d->map_height * d->map_width : (int64_t)d->height * d->width;
-    const int64_t total = P * d->batch, blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(blend_normal_sign_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, st,
+    const int64_t total = P * d->batch;
+    hipLaunchKernelGGL(blend_normal_sign_kernel, dim3(stream_grid(total, 16)), dim3(256), 0, st,
                        static_cast<const float *>(d->normal.data), static_cast<const float *>(bl->normal.data),
                        static_cast<const float *>(bl->mask.data), d->normal.batch_stride, d->normal.channel_stride,
                        bl->normal.batch_stride, bl->normal.channel_stride, bl->mask.batch_stride, P, total,
                        static_cast<int *>(workspace));
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+    return launch_status();
 }
 
 static void fill_blend(const pbr_blend_desc *bl, const void *workspace, KBlend &b) {
@@ -86,7 +85,7 @@ int pbr_cook_torrance_blend_backward(const pbr_render_desc *d, const pbr_blend_d
         fill_blend(bl, workspace, kb);
         hipStream_t tst = static_cast<hipStream_t>(stream);
         if (bl->sign_mode == PBR_BLEND_SIGN_COMPUTE) {
-            if (hipMemsetAsync(workspace, 0, sizeof(int) * (size_t)d->batch, tst) != hipSuccess) return 1000 + (int)hipGetLastError();
+            if (const int mrc = call_status(hipMemsetAsync(workspace, 0, sizeof(int) * (size_t)d->batch, tst))) return mrc;
             const int src = launch_normal_sign(d, bl, workspace, tst);
             if (src != PBR_OK) return src;
         }
@@ -108,7 +107,7 @@ int pbr_cook_torrance_blend_backward(const pbr_render_desc *d, const pbr_blend_d
     fill_blend(bl, workspace, b);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (bl->sign_mode == PBR_BLEND_SIGN_COMPUTE) {            // the same map-global decision the forward launch took (base.py:212)
-        if (hipMemsetAsync(workspace, 0, sizeof(int) * (size_t)d->batch, st) != hipSuccess) return 1000 + (int)hipGetLastError();
+        if (const int mrc = call_status(hipMemsetAsync(workspace, 0, sizeof(int) * (size_t)d->batch, st))) return mrc;
         const int src = launch_normal_sign(d, bl, workspace, st);
         if (src != PBR_OK) return src;
     }
@@ -117,23 +116,14 @@ int pbr_cook_torrance_blend_backward(const pbr_render_desc *d, const pbr_blend_d
                       spec ? g_material1->specular : nullptr, nullptr};
     const BBlend g2 = {g_material2->albedo, g_material2->normal, g_material2->roughness, spec ? nullptr : g_material2->metallic,
                        spec ? g_material2->specular : nullptr, static_cast<float *>(g_mask)};
-    const bool multi = d->n_lights > 1, point = d->light_type == PBR_LIGHT_POINT;
-    void (*fn)(const KArgs, const KBlend, const BArgs, const BBlend) = nullptr;
-#define PBR_BLEND_BWD(L, W)                                                                                                              \
-    fn = vec == 2 ? (multi ? cook_torrance_blend_backward_kernel<L, W, 2, true> : cook_torrance_blend_backward_kernel<L, W, 2, false>)   \
-                  : (multi ? cook_torrance_blend_backward_kernel<L, W, 1, true> : cook_torrance_blend_backward_kernel<L, W, 1, false>)
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: PBR_BLEND_BWD(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC); break;
-        case 1: PBR_BLEND_BWD(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR); break;
-        case 2: PBR_BLEND_BWD(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED); break;
-        case 3: PBR_BLEND_BWD(PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC); break;
-        case 4: PBR_BLEND_BWD(PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR); break;
-        default: PBR_BLEND_BWD(PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED); break;
-    }
-#undef PBR_BLEND_BWD
+    const bool multi = d->n_lights > 1;
+    using BlendBwdFn = void (*)(const KArgs, const KBlend, const BArgs, const BBlend);
+    const BlendBwdFn fn = with_light_workflow(d, [&](auto L, auto W) -> BlendBwdFn {
+        if (vec == 2) return multi ? cook_torrance_blend_backward_kernel<L(), W(), 2, true> : cook_torrance_blend_backward_kernel<L(), W(), 2, false>;
+        return multi ? cook_torrance_blend_backward_kernel<L(), W(), 1, true> : cook_torrance_blend_backward_kernel<L(), W(), 1, false>;
+    });
     hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, g1, g2);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+    return launch_status();
 }
 
 int pbr_blend_backward_serves(const pbr_render_desc *d) {
@@ -170,47 +160,29 @@ int pbr_cook_torrance_blend(const pbr_render_desc *d, const pbr_blend_desc *bl, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (bl->sign_mode == PBR_BLEND_SIGN_COMPUTE) {
         // pass 1: one flag per material -- does the blended normal map have a negative component?  (base.py:212)
-        if (hipMemsetAsync(workspace, 0, sizeof(int) * (size_t)d->batch, st) != hipSuccess) return 1000 + (int)hipGetLastError();
+        if (const int mrc = call_status(hipMemsetAsync(workspace, 0, sizeof(int) * (size_t)d->batch, st))) return mrc;
         const int src = launch_normal_sign(d, bl, workspace, st);
         if (src != PBR_OK) return src;
     }
     // pass 2: blend + evaluate
-    const bool multi = d->n_lights > 1, point = d->light_type == PBR_LIGHT_POINT;
+    const bool multi = d->n_lights > 1;
+    using BlendFn = void (*)(const KArgs, const KBlend);
     if (walk) {
-        void (*wfn)(const KArgs, const KBlend) = nullptr;
-#define PBR_BLEND_WALK(L, W) wfn = multi ? cook_torrance_repeat_blend_kernel<L, W, true> : cook_torrance_repeat_blend_kernel<L, W, false>
-        switch ((point ? 3 : 0) + d->workflow) {
-            case 0: PBR_BLEND_WALK(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC); break;
-            case 1: PBR_BLEND_WALK(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR); break;
-            case 2: PBR_BLEND_WALK(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED); break;
-            case 3: PBR_BLEND_WALK(PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC); break;
-            case 4: PBR_BLEND_WALK(PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR); break;
-            default: PBR_BLEND_WALK(PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED); break;
-        }
-#undef PBR_BLEND_WALK
+        const BlendFn wfn = with_light_workflow(d, [&](auto L, auto W) -> BlendFn {
+            return multi ? cook_torrance_repeat_blend_kernel<L(), W(), true> : cook_torrance_repeat_blend_kernel<L(), W(), false>;
+        });
         hipLaunchKernelGGL(wfn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), 0, st, k, b);
-        const hipError_t werr = hipGetLastError();
-        return werr == hipSuccess ? PBR_OK : 1000 + (int)werr;
+        return launch_status();
     }
-    void (*fn)(const KArgs, const KBlend) = nullptr;
-#define PBR_BLEND(L, W)                                                                                              \
-    fn = vec == 4 ? (multi ? cook_torrance_blend_kernel<L, W, 4, true> : cook_torrance_blend_kernel<L, W, 4, false>) \
-                  : (multi ? cook_torrance_blend_kernel<L, W, 1, true> : cook_torrance_blend_kernel<L, W, 1, false>)
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: PBR_BLEND(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC); break;
-        case 1: PBR_BLEND(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR); break;
-        case 2: PBR_BLEND(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED); break;
-        case 3: PBR_BLEND(PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC); break;
-        case 4: PBR_BLEND(PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR); break;
-        default: PBR_BLEND(PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED); break;
-    }
-#undef PBR_BLEND
+    const BlendFn fn = with_light_workflow(d, [&](auto L, auto W) -> BlendFn {
+        if (vec == 4) return multi ? cook_torrance_blend_kernel<L(), W(), 4, true> : cook_torrance_blend_kernel<L(), W(), 4, false>;
+        return multi ? cook_torrance_blend_kernel<L(), W(), 1, true> : cook_torrance_blend_kernel<L(), W(), 1, false>;
+    });
     // occupancy governor (see g_lds_bytes): the 17-stream one-light blend streams fastest with 10 waves per CU --
     // 4096^2: 255 us uncapped, 236 / 232 / 234 / 233 / 248 us at 11 / 10 / 9 / 8 / 6 (tools/blend_probe.py)
     const size_t lds = g_lds_bytes >= 0 ? (size_t)g_lds_bytes : (multi ? 0 : 16384);
     hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), lds, st, k, b);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
-// ct_launch.hpp -- host side shared by the launchers (cook_torrance.hip, ct_backward.hip, ct_blend.hip): descriptor
-// validation, the 16-byte-path test, the workgroup-order rule and the translation of a pbr_render_desc into the
-// kernel-argument block.  Tuning knobs live in cook_torrance.hip (pbr_set_tuning).
+// ct_launch.hpp -- host side shared by the launchers of the render kernels (cook_torrance.hip, ct_batch.hip, ct_tiled.hip,
+// ct_backward.hip, ct_repeat_backward.hip, ct_blend.hip, ct_loss.hip): descriptor validation, the light x workflow dispatch
+// (with_light_workflow), the 16-byte-path test, the workgroup-order rule and the translation of a pbr_render_desc into the
+// kernel-argument block.  Launch status, alignment test and CU count: launch_util.hpp (through stream_shape.hpp).  Tuning knobs
+// live in cook_torrance.hip (pbr_set_tuning).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +10,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "../../include/pbr_hip.h"
 #include "ct_kernel.hpp"
@@ -93,6 +96,27 @@ inline int validate(const pbr_render_desc *d) {
     return PBR_OK;
 }
 
+// The one light x workflow dispatch: f(integral_constant<int, LIGHT>, integral_constant<int, WF>) for the descriptor's pair; every
+// kernel family is instantiated for exactly these six.  (validate() rejects every other value; an unlisted one lands on point /
+// converted, as it always has.)
+template <typename F>
+inline auto with_light_workflow(const pbr_render_desc *d, F &&f) {
+    using Dir = std::integral_constant<int, PBR_LIGHT_DIRECTIONAL>;
+    using Point = std::integral_constant<int, PBR_LIGHT_POINT>;
+    using Metallic = std::integral_constant<int, PBR_WORKFLOW_METALLIC>;
+    using Specular = std::integral_constant<int, PBR_WORKFLOW_SPECULAR>;
+    using Converted = std::integral_constant<int, PBR_WORKFLOW_CONVERTED>;
+    const bool point = d->light_type == PBR_LIGHT_POINT;
+    switch ((point ? 3 : 0) + d->workflow) {
+        case 0: return f(Dir{}, Metallic{});
+        case 1: return f(Dir{}, Specular{});
+        case 2: return f(Dir{}, Converted{});
+        case 3: return f(Point{}, Metallic{});
+        case 4: return f(Point{}, Specular{});
+        default: return f(Point{}, Converted{});
+    }
+}
+
 inline bool is_tiled(const pbr_render_desc *d) {
     return d->map_height > 0 && (d->map_height != d->height_total || d->map_width != d->width);
 }
@@ -111,11 +135,10 @@ inline int pick_vec(const pbr_render_desc *d) {
     if (d->map_dtype == PBR_F16 && d->width % 8 == 0 && (!tiled || d->map_width % 8 == 0) && d->n_lights == 1 && g_f16_vec == 8 &&
         g_max_vec >= 8) {
         auto ok16 = [&](const pbr_map &m, bool three) {
-            return !m.data || ((reinterpret_cast<uintptr_t>(m.data) & 15u) == 0 && m.batch_stride % 8 == 0 &&
-                               (!three || m.channel_stride % 8 == 0));
+            return !m.data || (is_aligned(m.data, 16) && m.batch_stride % 8 == 0 && (!three || m.channel_stride % 8 == 0));
         };
         if (ok16(d->albedo, true) && ok16(d->normal, true) && ok16(d->roughness, false) && ok16(d->metallic, false) &&
-            ok16(d->specular, true) && (reinterpret_cast<uintptr_t>(d->out) & 15u) == 0 && d->out_batch_stride % 8 == 0 &&
+            ok16(d->specular, true) && is_aligned(d->out, 16) && d->out_batch_stride % 8 == 0 &&
             d->out_channel_stride % 8 == 0)
             return 8;
     }
@@ -241,7 +264,7 @@ inline int fill_result_nan(const pbr_render_desc *d, hipStream_t st) {
             hipError_t e;
             if (d->out_dtype == PBR_F32) e = hipMemsetD32Async((hipDeviceptr_t)(static_cast<float *>(d->out) + b * bs + c * cs), 0x7fc00000, (size_t)plane, st);
             else e = hipMemsetD16Async((hipDeviceptr_t)(static_cast<uint16_t *>(d->out) + b * bs + c * cs), 0x7e00, (size_t)plane, st);
-            if (e != hipSuccess) return 1000 + (int)e;
+            if (e != hipSuccess) return hip_code(e);
         }
     return PBR_OK;
 }

@@ -153,17 +153,9 @@ static MseFn pick_mse(bool half_maps, int vec, bool multi) {
 
 using MseStreamFn = void (*)(const KArgs, const BArgs, int, int, float, float *);
 static MseStreamFn pick_mse_stream(const pbr_render_desc *d, bool full) {
-    const bool point = d->light_type == PBR_LIGHT_POINT;
-#define PBR_MSES(L, W) return full ? cook_torrance_mse_stream_kernel<L, W, true> : cook_torrance_mse_stream_kernel<L, W, false>
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: PBR_MSES(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC);
-        case 1: PBR_MSES(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR);
-        case 2: PBR_MSES(PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED);
-        case 3: PBR_MSES(PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC);
-        case 4: PBR_MSES(PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR);
-        default: PBR_MSES(PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED);
-    }
-#undef PBR_MSES
+    return with_light_workflow(d, [&](auto L, auto W) -> MseStreamFn {
+        return full ? cook_torrance_mse_stream_kernel<L(), W(), true> : cook_torrance_mse_stream_kernel<L(), W(), false>;
+    });
 }
 int stream_run(const pbr_render_desc *d, const void *grad_out, void *const g[5]);      // ct_backward.hip: rounds of the streamed form, 0 = does not qualify
 
@@ -181,6 +173,22 @@ static int64_t mse_tiles(const pbr_render_desc *d, int vec) {
     KArgs k;
     fill_args(d, vec, k, 6);
     return k.n_tiles;
+}
+
+// The step kernel's partial sums -> *loss = their sum / count (fp64, fixed order): one workgroup for few partials, else the stage sums and
+// their sum.  Where the stage sums go does not depend on n_partials: the stage block sits behind the partials of the LARGEST
+// decomposition of the descriptor -- mse_tiles(d, 1), or repeat_backward_tiles(d) for tiled maps -- which is what
+// pbr_mse_step_workspace_bytes reserves.  `stage_offset_tiles()` returns that count; it is asked only when the stage block is used.
+template <typename StageTiles>
+static int finish_mse(float *partials, int64_t n_partials, StageTiles &&stage_offset_tiles, double count, float *loss, hipStream_t st) {
+    if (n_partials <= kMseSmall) {
+        hipLaunchKernelGGL(mse_reduce_small_kernel, dim3(1), dim3(256), 0, st, partials, (int)n_partials, 1.0 / count, loss);
+    } else {
+        double *stage = reinterpret_cast<double *>(reinterpret_cast<char *>(partials) + mse_stage_offset((size_t)stage_offset_tiles()));
+        hipLaunchKernelGGL(mse_stage_kernel, dim3(kMseStageGroups), dim3(256), 0, st, partials, (int)n_partials, stage);
+        hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, st, stage, 1.0 / count, loss);
+    }
+    return launch_status();
 }
 
 }  // namespace pbr
@@ -209,6 +217,7 @@ int pbr_cook_torrance_mse_step(const pbr_render_desc *d, const void *target, voi
     KArgs k;
     const double count = 3.0 * (double)d->batch * (double)d->height * (double)d->width;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    float *const partials = static_cast<float *>(workspace);      // one per workgroup of the step kernel; the stage sums behind them (finish_mse)
     if (is_tiled(d)) {
         // MaterialBase.tile fused (base.py:524-537): the repeat-inner kernel walks the maps, compares every repeat with the target and leaves
         // MAP-sized gradients (ct_repeat_backward.hpp); launches it does not serve are the caller's to split (render, loss, folded backward)
@@ -216,18 +225,11 @@ int pbr_cook_torrance_mse_step(const pbr_render_desc *d, const void *target, voi
         const int64_t tiles = repeat_backward_tiles(d);
         if (tiles < 0) return PBR_ERR_SHAPE;
         const int e = launch_repeat_backward(d, target, g_albedo, g_normal, g_roughness, g_metallic, g_specular, true, (float)(2.0 / count),
-                                             static_cast<float *>(workspace), st);
+                                             partials, st);
         if (e != PBR_OK) return e;
-        if (tiles <= kMseSmall) {
-            hipLaunchKernelGGL(mse_reduce_small_kernel, dim3(1), dim3(256), 0, st, static_cast<const float *>(workspace), (int)tiles, 1.0 / count, static_cast<float *>(loss));
-        } else {
-            double *stage = reinterpret_cast<double *>(static_cast<char *>(workspace) + mse_stage_offset((size_t)tiles));
-            hipLaunchKernelGGL(mse_stage_kernel, dim3(kMseStageGroups), dim3(256), 0, st, static_cast<const float *>(workspace), (int)tiles, stage);
-            hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, st, stage, 1.0 / count, static_cast<float *>(loss));
-        }
-        const hipError_t err = hipGetLastError();
-        return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+        return finish_mse(partials, tiles, [&] { return tiles; }, count, static_cast<float *>(loss), st);      // (tiles = repeat_backward_tiles(d))
     }
+    const auto largest = [&] { return mse_tiles(d, 1); };      // one pixel per lane: the most workgroups any launch of this descriptor has
     void *const gs[5] = {g_albedo, g_normal, g_roughness, g_metallic, g_specular};
     if (const int rounds = g_mse_stream ? stream_run(d, target, gs) : 0) {      // fp16 maps, one light: the streamed form
         fill_args(d, 2, k, 6);
@@ -240,54 +242,26 @@ int pbr_cook_torrance_mse_step(const pbr_render_desc *d, const void *target, voi
         // every run-time flag on and every gradient wanted: the instantiation without flag branches (as in ct_backward.hip)
         const bool full = d->albedo_is_srgb && d->return_srgb && d->normal.data && g_albedo && g_normal && g_roughness &&
                           (spec ? (g_specular && d->specular_is_srgb) : (g_metallic && (d->workflow == PBR_WORKFLOW_METALLIC || d->specular_is_srgb)));
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
         // (the allocator is ALLOWED two waves per SIMD and lands on 138-167 VGPRs: three fit, and the grid is sized for three)
-        int64_t per_material = ((int64_t)cus * 4 * kStreamWavesPerSimd * rounds + d->batch - 1) / d->batch;
+        int64_t per_material = ((int64_t)resident_cus() * 4 * kStreamWavesPerSimd * rounds + d->batch - 1) / d->batch;
         if (per_material > tiles) per_material = tiles;
         if (per_material < 1) per_material = 1;
         const int64_t n_partials = per_material * d->batch;             // <= tiles * batch <= the workgroups of the one-tile form
         hipLaunchKernelGGL(pick_mse_stream(d, full), dim3((unsigned)per_material, (unsigned)d->batch, 1), dim3(64, 1, 1), 0, st, k, b, tiles, n_stores,
-                           (float)(2.0 / count), static_cast<float *>(workspace));
-        hipError_t err = hipGetLastError();
-        if (err != hipSuccess) return 1000 + (int)err;
-        if (n_partials <= kMseSmall) {
-            hipLaunchKernelGGL(mse_reduce_small_kernel, dim3(1), dim3(256), 0, st, static_cast<const float *>(workspace), (int)n_partials, 1.0 / count, static_cast<float *>(loss));
-        } else {
-            double *stage = reinterpret_cast<double *>(static_cast<char *>(workspace) + mse_stage_offset((size_t)mse_tiles(d, 1)));
-            hipLaunchKernelGGL(mse_stage_kernel, dim3(kMseStageGroups), dim3(256), 0, st, static_cast<const float *>(workspace), (int)n_partials, stage);
-            hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, st, stage, 1.0 / count, static_cast<float *>(loss));
-        }
-        err = hipGetLastError();
-        return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+                           (float)(2.0 / count), partials);
+        const int e = launch_status();
+        return e != PBR_OK ? e : finish_mse(partials, n_partials, largest, count, static_cast<float *>(loss), st);
     }
     fill_args(d, vec, k, 6);                                  // one-wave workgroups: one partial sum per workgroup, no LDS reduction
     if (k.n_tiles < 0) return PBR_ERR_SHAPE;
     k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;     // target and gradient planes are contiguous
     const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
-    const bool multi = d->n_lights > 1, point = d->light_type == PBR_LIGHT_POINT, half_maps = d->map_dtype == PBR_F16;
-    MseFn fn = nullptr;
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: fn = pick_mse<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC>(half_maps, vec, multi); break;
-        case 1: fn = pick_mse<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR>(half_maps, vec, multi); break;
-        case 2: fn = pick_mse<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED>(half_maps, vec, multi); break;
-        case 3: fn = pick_mse<PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC>(half_maps, vec, multi); break;
-        case 4: fn = pick_mse<PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR>(half_maps, vec, multi); break;
-        default: fn = pick_mse<PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED>(half_maps, vec, multi); break;
-    }
+    const bool multi = d->n_lights > 1, half_maps = d->map_dtype == PBR_F16;
+    const MseFn fn = with_light_workflow(d, [&](auto L, auto W) -> MseFn { return pick_mse<L(), W()>(half_maps, vec, multi); });
     hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(target),
-                       (float)(2.0 / count), static_cast<float *>(workspace));
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return 1000 + (int)err;
-    if (k.n_tiles <= kMseSmall) {
-        hipLaunchKernelGGL(mse_reduce_small_kernel, dim3(1), dim3(256), 0, st, static_cast<const float *>(workspace), (int)k.n_tiles, 1.0 / count, static_cast<float *>(loss));
-    } else {
-        double *stage = reinterpret_cast<double *>(static_cast<char *>(workspace) + mse_stage_offset((size_t)mse_tiles(d, 1)));
-        hipLaunchKernelGGL(mse_stage_kernel, dim3(kMseStageGroups), dim3(256), 0, st, static_cast<const float *>(workspace), (int)k.n_tiles, stage);
-        hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, st, stage, 1.0 / count, static_cast<float *>(loss));
-    }
-    err = hipGetLastError();
-    return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+                       (float)(2.0 / count), partials);
+    const int e = launch_status();
+    return e != PBR_OK ? e : finish_mse(partials, k.n_tiles, largest, count, static_cast<float *>(loss), st);
 }
 
 int pbr_scale_by_device_scalar(void *data, size_t n, int dtype, const void *scalar, void *stream) {
@@ -295,13 +269,11 @@ int pbr_scale_by_device_scalar(void *data, size_t n, int dtype, const void *scal
     if (!data || !scalar) return PBR_ERR_NULL_MAP;
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
     if (n == 0) return PBR_OK;
-    const size_t blocks = (n + 255) / 256;
-    const unsigned grid = (unsigned)(blocks > 2048 ? 2048 : blocks);
+    const unsigned grid = stream_grid(n);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (dtype == PBR_F32) hipLaunchKernelGGL((scale_by_device_scalar_kernel<float>), dim3(grid), dim3(256), 0, st, static_cast<float *>(data), n, static_cast<const float *>(scalar));
     else hipLaunchKernelGGL((scale_by_device_scalar_kernel<_Float16>), dim3(grid), dim3(256), 0, st, static_cast<_Float16 *>(data), n, static_cast<const float *>(scalar));
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+    return launch_status();
 }
 
 int pbr_scale_list_by_device_scalar(void *const *data, const size_t *n, int count, int dtype, const void *scalar, void *stream) {
@@ -317,13 +289,11 @@ int pbr_scale_list_by_device_scalar(void *const *data, const size_t *n, int coun
         most = n[j] > most ? n[j] : most;
     }
     if (most == 0) return PBR_OK;
-    const size_t blocks = (most + 255) / 256;
-    const unsigned grid = (unsigned)(blocks > 2048 ? 2048 : blocks);
+    const unsigned grid = stream_grid(most);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (dtype == PBR_F32) hipLaunchKernelGGL((scale_list_kernel<float>), dim3(grid), dim3(256), 0, st, l, static_cast<const float *>(scalar));
     else hipLaunchKernelGGL((scale_list_kernel<_Float16>), dim3(grid), dim3(256), 0, st, l, static_cast<const float *>(scalar));
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? PBR_OK : 1000 + (int)err;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -16,15 +16,8 @@ static RepBwdFn repeat_bwd_types(bool half_maps, bool loss, bool multi) {
 }
 
 static RepBwdFn pick_repeat_bwd(const pbr_render_desc *d, bool loss) {
-    const bool point = d->light_type == PBR_LIGHT_POINT, half_maps = d->map_dtype == PBR_F16, multi = d->n_lights > 1;
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: return repeat_bwd_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC>(half_maps, loss, multi);
-        case 1: return repeat_bwd_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR>(half_maps, loss, multi);
-        case 2: return repeat_bwd_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED>(half_maps, loss, multi);
-        case 3: return repeat_bwd_types<PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC>(half_maps, loss, multi);
-        case 4: return repeat_bwd_types<PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR>(half_maps, loss, multi);
-        default: return repeat_bwd_types<PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED>(half_maps, loss, multi);
-    }
+    const bool half_maps = d->map_dtype == PBR_F16, multi = d->n_lights > 1;
+    return with_light_workflow(d, [&](auto L, auto W) -> RepBwdFn { return repeat_bwd_types<L(), W()>(half_maps, loss, multi); });
 }
 
 // The launches the repeat-inner backward serves: what the forward's repeat-inner kernel serves (map rows a whole number of
@@ -90,8 +83,7 @@ int launch_repeat_backward(const pbr_render_desc *d, const void *upstream, void 
     const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
     const RBArgs rb = {static_cast<const float *>(upstream), (int64_t)d->height * d->width, scale, partials};
     hipLaunchKernelGGL(pick_repeat_bwd(d, loss), dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, rb);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+    return launch_status();
 }
 
 // pbr_cook_torrance_blend_backward over TILED maps (round 6): what the one-kernel folded backward serves, with one light, fp32 maps.
@@ -106,20 +98,11 @@ int launch_repeat_blend_backward(const pbr_render_desc *d, const void *kblend, c
     if (rc != PBR_OK) return rc;
     k.sbase = 0;                                          // (the second material and the mask are addressed per lane, as in the untiled blend backward)
     const RBArgs rb = {static_cast<const float *>(grad_out), (int64_t)d->height * d->width, 0.0f, nullptr};
-    void (*fn)(const KArgs, const KBlend, const BArgs, const BBlend, const RBArgs) = nullptr;
-    const bool point = d->light_type == PBR_LIGHT_POINT;
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: fn = cook_torrance_repeat_blend_backward_kernel<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC>; break;
-        case 1: fn = cook_torrance_repeat_blend_backward_kernel<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR>; break;
-        case 2: fn = cook_torrance_repeat_blend_backward_kernel<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED>; break;
-        case 3: fn = cook_torrance_repeat_blend_backward_kernel<PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC>; break;
-        case 4: fn = cook_torrance_repeat_blend_backward_kernel<PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR>; break;
-        default: fn = cook_torrance_repeat_blend_backward_kernel<PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED>; break;
-    }
+    using Fn = void (*)(const KArgs, const KBlend, const BArgs, const BBlend, const RBArgs);
+    const Fn fn = with_light_workflow(d, [](auto L, auto W) -> Fn { return cook_torrance_repeat_blend_backward_kernel<L(), W()>; });
     hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, *static_cast<const KBlend *>(kblend), *static_cast<const BArgs *>(g1),
                        *static_cast<const BBlend *>(g2), rb);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+    return launch_status();
 }
 
 static size_t folded_fallback_bytes(const pbr_render_desc *d) {
@@ -157,8 +140,10 @@ int pbr_cook_torrance_backward_folded(const pbr_render_desc *d, const void *grad
             void *const bufs[5] = {g_albedo, d->normal.data ? g_normal : nullptr, g_roughness, d->workflow == PBR_WORKFLOW_SPECULAR ? nullptr : g_metallic,
                                    d->workflow == PBR_WORKFLOW_SPECULAR ? g_specular : nullptr};
             const int chans[5] = {3, 3, 1, 1, 3};
-            for (int i = 0; i < 5; ++i)
-                if (bufs[i] && hipMemsetAsync(bufs[i], 0, chans[i] * plane, st) != hipSuccess) return 1000 + (int)hipGetLastError();
+            for (int i = 0; i < 5; ++i) {
+                const int mrc = bufs[i] ? call_status(hipMemsetAsync(bufs[i], 0, chans[i] * plane, st)) : PBR_OK;
+                if (mrc != PBR_OK) return mrc;
+            }
         }
         return launch_repeat_backward(d, grad_out, g_albedo, g_normal, g_roughness, g_metallic, g_specular, false, 0.0f, nullptr, st);
     }

@@ -21,17 +21,8 @@ static KernelFn repeat_types(int in_dt, int out_dt, bool multi) {
 }
 
 KernelFn pick_repeat_kernel(const pbr_render_desc *d) {
-    const bool point = d->light_type == PBR_LIGHT_POINT;
-    const int idt = d->map_dtype, odt = d->out_dtype;
     const bool multi = d->n_lights > 1;
-    switch ((point ? 3 : 0) + d->workflow) {
-        case 0: return repeat_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_METALLIC>(idt, odt, multi);
-        case 1: return repeat_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_SPECULAR>(idt, odt, multi);
-        case 2: return repeat_types<PBR_LIGHT_DIRECTIONAL, PBR_WORKFLOW_CONVERTED>(idt, odt, multi);
-        case 3: return repeat_types<PBR_LIGHT_POINT, PBR_WORKFLOW_METALLIC>(idt, odt, multi);
-        case 4: return repeat_types<PBR_LIGHT_POINT, PBR_WORKFLOW_SPECULAR>(idt, odt, multi);
-        default: return repeat_types<PBR_LIGHT_POINT, PBR_WORKFLOW_CONVERTED>(idt, odt, multi);
-    }
+    return with_light_workflow(d, [&](auto L, auto W) -> KernelFn { return repeat_types<L(), W()>(d->map_dtype, d->out_dtype, multi); });
 }
 
 // The kernel's argument block: the grid of an UNTILED launch over the source maps (rows = B * map_height, W = map_width), the

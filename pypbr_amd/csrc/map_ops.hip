@@ -19,16 +19,7 @@
 
 namespace pbr {
 
-template <typename T> struct Elem;
-template <> struct Elem<float> {
-    static __device__ __forceinline__ float ld(const void *p, size_t i) { return static_cast<const float *>(p)[i]; }
-    static __device__ __forceinline__ void st(void *p, size_t i, float v) { static_cast<float *>(p)[i] = v; }
-};
-template <> struct Elem<__half> {
-    static __device__ __forceinline__ float ld(const void *p, size_t i) { return (float)static_cast<const _Float16 *>(p)[i]; }
-    static __device__ __forceinline__ void st(void *p, size_t i, float v) { static_cast<_Float16 *>(p)[i] = (_Float16)v; }
-};
-
+// (one element: Elem<T>, launch_util.hpp)
 // 4 elements per lane when everything is 16-byte (fp32) / 8-byte (fp16) aligned.
 template <typename T> struct Quad;
 template <> struct Quad<float> {
@@ -514,19 +505,6 @@ __global__ __launch_bounds__(256) void specular_to_metallic_backward_kernel(cons
 }
 
 
-static inline unsigned stream_grid(size_t work_items) {
-    const size_t blocks = (work_items + 255) / 256;
-    const size_t cap = 256 * 8;                                     // 256 CUs x 8 blocks, grid-stride beyond
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
-static inline int hip_status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
-}
-
-static inline bool is_aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 template <typename T>
 static int fold_launch(const void *src, void *dst, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t ny, int32_t nx,
                        int fold_batch, void *stream) {
@@ -535,11 +513,11 @@ static int fold_launch(const void *src, void *dst, int32_t batch, int32_t channe
         const StreamShape sh = stream_shape(items / 4, kShapeFold);
         hipLaunchKernelGGL((fold_gradient_quad_kernel<T>), dim3(sh.grid), dim3(sh.block), sh.lds, static_cast<hipStream_t>(stream),
                            src, dst, (int)batch, (int)channels, (int)h, (int)w, (int)ny, (int)nx, fold_batch);
-        return hip_status();
+        return launch_status();
     }
     hipLaunchKernelGGL((fold_gradient_kernel<T>), dim3(stream_grid(items)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        src, dst, (int)batch, (int)channels, (int)h, (int)w, (int)ny, (int)nx, fold_batch);
-    return hip_status();
+    return launch_status();
 }
 
 }  // namespace pbr
@@ -562,7 +540,7 @@ static int colour_launch(const void *src, void *dst, size_t n, int dtype, void *
         if (to_linear) hipLaunchKernelGGL((colour_kernel<__half, true>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, dst, n, vec_ok);
         else hipLaunchKernelGGL((colour_kernel<__half, false>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, dst, n, vec_ok);
     }
-    return hip_status();
+    return launch_status();
 }
 
 int pbr_srgb_to_linear(const void *src, void *dst, size_t n, int dtype, void *stream) {
@@ -588,7 +566,7 @@ int pbr_metallic_to_specular(const void *albedo, const void *metallic, void *dif
         hipLaunchKernelGGL((metallic_to_specular_kernel<float>), dim3(sh.grid), dim3(sh.block), sh.lds, s, albedo, metallic, diffuse, specular, (int)batch, pixels, albedo_is_srgb, vec_ok);
     else
         hipLaunchKernelGGL((metallic_to_specular_kernel<__half>), dim3(sh.grid), dim3(sh.block), sh.lds, s, albedo, metallic, diffuse, specular, (int)batch, pixels, albedo_is_srgb, vec_ok);
-    return hip_status();
+    return launch_status();
 }
 
 int pbr_specular_to_metallic(const void *diffuse, const void *specular, void *basecolor, void *metallic,
@@ -605,7 +583,7 @@ int pbr_specular_to_metallic(const void *diffuse, const void *specular, void *ba
         hipLaunchKernelGGL((specular_to_metallic_kernel<float>), dim3(sh.grid), dim3(sh.block), sh.lds, s, diffuse, specular, basecolor, metallic, n, albedo_is_srgb, vec_ok);
     else
         hipLaunchKernelGGL((specular_to_metallic_kernel<__half>), dim3(sh.grid), dim3(sh.block), sh.lds, s, diffuse, specular, basecolor, metallic, n, albedo_is_srgb, vec_ok);
-    return hip_status();
+    return launch_status();
 }
 
 
@@ -625,7 +603,7 @@ static int colour_backward_launch(const void *src, const void *gout, void *gin, 
         if (to_linear) hipLaunchKernelGGL((colour_backward_kernel<__half, true>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, gout, gin, n, vec_ok);
         else hipLaunchKernelGGL((colour_backward_kernel<__half, false>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, gout, gin, n, vec_ok);
     }
-    return hip_status();
+    return launch_status();
 }
 
 int pbr_srgb_to_linear_backward(const void *src, const void *grad_out, void *grad_in, size_t n, int dtype, void *stream) {
@@ -655,7 +633,7 @@ int pbr_metallic_to_specular_backward(const void *albedo, const void *metallic, 
     if (dtype == PBR_F32) { if (vec) PBR_M2S_BWD(float, true); else PBR_M2S_BWD(float, false); }
     else { if (vec) PBR_M2S_BWD(__half, true); else PBR_M2S_BWD(__half, false); }
 #undef PBR_M2S_BWD
-    return hip_status();
+    return launch_status();
 }
 
 int pbr_specular_to_metallic_backward(const void *diffuse, const void *specular, const void *g_basecolor, const void *g_metallic,
@@ -675,7 +653,7 @@ int pbr_specular_to_metallic_backward(const void *diffuse, const void *specular,
     else
         hipLaunchKernelGGL((specular_to_metallic_backward_kernel<__half>), dim3(sh.grid), dim3(sh.block), sh.lds, s, diffuse, specular, g_basecolor, g_metallic,
                            g_diffuse, g_specular, n, albedo_is_srgb, vec_ok);
-    return hip_status();
+    return launch_status();
 }
 
 int pbr_fold_gradient_typed(const void *src, void *dst, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t ny,
@@ -704,7 +682,7 @@ int pbr_decode_normal(const void *src, void *dst, int32_t channels, int64_t pixe
     const unsigned grid = stream_grid((size_t)pixels);
     const size_t esz = dtype == PBR_F32 ? 4 : 2, n = (size_t)pixels * 3;
     if (channels == 2) {
-        if (hipMemsetAsync(flag, 0, sizeof(int), s) != hipSuccess) return hip_status();
+        if (const int mrc = call_status(hipMemsetAsync(flag, 0, sizeof(int), s))) return mrc;
     } else if (dtype == PBR_F32) {                                          // the probe writes the flag, 0 or 1
         hipLaunchKernelGGL((normal_probe_kernel<float>), dim3(1), dim3(256), 0, s, src, n, flag);
     } else {
@@ -721,7 +699,7 @@ int pbr_decode_normal(const void *src, void *dst, int32_t channels, int64_t pixe
             hipLaunchKernelGGL((decode_normal_speculative_kernel<__half>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
             hipLaunchKernelGGL((keep_normal_kernel<__half>), dim3(fix_grid), dim3(256), 0, s, src, dst, n, flag, vec_ok);
         }
-        return hip_status();
+        return launch_status();
     }
     if (dtype == PBR_F32) {
         if (channels == 3) {
@@ -738,7 +716,7 @@ int pbr_decode_normal(const void *src, void *dst, int32_t channels, int64_t pixe
             hipLaunchKernelGGL((decode_normal_kernel<__half, 2>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
         }
     }
-    return hip_status();
+    return launch_status();
 }
 
 int pbr_decode_normal_backward(const void *src, const void *grad_out, void *grad_in, int32_t channels, int64_t pixels,
@@ -761,7 +739,7 @@ int pbr_decode_normal_backward(const void *src, const void *grad_out, void *grad
     } else {
         hipLaunchKernelGGL((decode_normal_backward_kernel<2, 1>), dim3(grid), dim3(256), 0, s, a, g, gi, pixels, flag);
     }
-    return hip_status();
+    return launch_status();
 }
 
 int pbr_abi_version(void) { return PBR_HIP_ABI_VERSION; }

@@ -21,16 +21,6 @@
 namespace pbr {
 namespace {
 
-template <typename T> struct Elem;
-template <> struct Elem<float> {
-    static __device__ __forceinline__ float ld(const void *p, int64_t i) { return static_cast<const float *>(p)[i]; }
-    static __device__ __forceinline__ void st(void *p, int64_t i, float v) { static_cast<float *>(p)[i] = v; }
-};
-template <> struct Elem<__half> {
-    static __device__ __forceinline__ float ld(const void *p, int64_t i) { return (float)static_cast<const _Float16 *>(p)[i]; }
-    static __device__ __forceinline__ void st(void *p, int64_t i, float v) { static_cast<_Float16 *>(p)[i] = (_Float16)v; }
-};
-
 // V consecutive elements at element offset i (V = 4: 16-byte fp32 / 8-byte fp16 accesses; the caller checked the alignment)
 template <typename T, int V> struct Vec;
 template <typename T> struct Vec<T, 1> {
@@ -293,13 +283,6 @@ __global__ __launch_bounds__(256) void normal_transform_backward_kernel(const fl
     Vec<float, V>::st(grad_in, io + 2 * gi_ps, gz);
 }
 
-int status() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
-}
-
-bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // Rows per wave of the stencil walks: enough waves to fill the chip (about 16 per CU), at least 8 rows so that the two halo rows
 // stay a small share of the height reads, at most 64.
 int walk_rows(int64_t strips, int64_t batch, int H) {
@@ -326,7 +309,7 @@ int pbr_normal_from_height(const void *height, int64_t height_batch_stride, void
         return PBR_ERR_SHAPE;
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
     const size_t esz = dtype == PBR_F32 ? 4 : 2;
-    const bool vec = width % 4 == 0 && aligned(height, 4 * esz) && aligned(normal, 4 * esz) && height_batch_stride % 4 == 0 &&
+    const bool vec = width % 4 == 0 && is_aligned(height, 4 * esz) && is_aligned(normal, 4 * esz) && height_batch_stride % 4 == 0 &&
                      normal_batch_stride % 4 == 0 && normal_plane_stride % 4 == 0;
     const int V = vec ? 4 : 1, units = width / V;
     const int64_t strips = (units + 63) / 64, groups = (strips + 3) / 4;
@@ -340,7 +323,7 @@ int pbr_normal_from_height(const void *height, int64_t height_batch_stride, void
     if (dtype == PBR_F32) { if (vec) PBR_NFH(float, 4); else PBR_NFH(float, 1); }
     else { if (vec) PBR_NFH(__half, 4); else PBR_NFH(__half, 1); }
 #undef PBR_NFH
-    return status();
+    return launch_status();
 }
 
 int pbr_normal_from_height_backward(const void *height, int64_t height_batch_stride, const void *grad_normal, int64_t grad_batch_stride,
@@ -351,7 +334,7 @@ int pbr_normal_from_height_backward(const void *height, int64_t height_batch_str
     if (!stencil_shape_ok(batch, height_px, width) || height_batch_stride < 0 || grad_batch_stride < 0 || grad_plane_stride < 0 ||
         grad_height_batch_stride < 0)
         return PBR_ERR_SHAPE;
-    const bool vec = width % 4 == 0 && aligned(height, 16) && aligned(grad_normal, 16) && aligned(grad_height, 16) &&
+    const bool vec = width % 4 == 0 && is_aligned(height, 16) && is_aligned(grad_normal, 16) && is_aligned(grad_height, 16) &&
                      height_batch_stride % 4 == 0 && grad_batch_stride % 4 == 0 && grad_plane_stride % 4 == 0 && grad_height_batch_stride % 4 == 0;
     const int V = vec ? 4 : 1, units = width / V;
     const int64_t strips = (units + 61) / 62, groups = (strips + 3) / 4;
@@ -366,7 +349,7 @@ int pbr_normal_from_height_backward(const void *height, int64_t height_batch_str
                                            bands, (int)groups, scale, (int)(directx != 0))
     if (vec) PBR_NFH_BWD(4); else PBR_NFH_BWD(1);
 #undef PBR_NFH_BWD
-    return status();
+    return launch_status();
 }
 
 int pbr_normal_transform(const void *src, int64_t src_batch_stride, int64_t src_plane_stride, void *dst, int64_t dst_batch_stride,
@@ -378,7 +361,7 @@ int pbr_normal_transform(const void *src, int64_t src_batch_stride, int64_t src_
         return PBR_ERR_SHAPE;
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
     const size_t esz = dtype == PBR_F32 ? 4 : 2;
-    const bool vec = pixels % 4 == 0 && aligned(src, 4 * esz) && aligned(dst, 4 * esz) && src_batch_stride % 4 == 0 &&
+    const bool vec = pixels % 4 == 0 && is_aligned(src, 4 * esz) && is_aligned(dst, 4 * esz) && src_batch_stride % 4 == 0 &&
                      src_plane_stride % 4 == 0 && dst_batch_stride % 4 == 0 && dst_plane_stride % 4 == 0;
     const Affine M = {m00, m01, m10, m11, (int)(m01 == 0.0f && m10 == 0.0f), (int)(renormalize != 0)};
     const int64_t units = vec ? pixels / 4 : pixels, total = units * batch;
@@ -390,7 +373,7 @@ int pbr_normal_transform(const void *src, int64_t src_batch_stride, int64_t src_
     if (dtype == PBR_F32) { if (vec) PBR_NT(float, 4); else PBR_NT(float, 1); }
     else { if (vec) PBR_NT(__half, 4); else PBR_NT(__half, 1); }
 #undef PBR_NT
-    return status();
+    return launch_status();
 }
 
 int pbr_normal_transform_backward(const void *src, int64_t src_batch_stride, int64_t src_plane_stride, const void *grad_out,
@@ -402,7 +385,7 @@ int pbr_normal_transform_backward(const void *src, int64_t src_batch_stride, int
     if (batch < 1 || pixels < 1 || src_batch_stride < 0 || src_plane_stride < 0 || grad_batch_stride < 0 || grad_plane_stride < 0 ||
         grad_in_batch_stride < 0 || grad_in_plane_stride < 0)
         return PBR_ERR_SHAPE;
-    const bool vec = pixels % 4 == 0 && aligned(src, 16) && aligned(grad_out, 16) && aligned(grad_in, 16) && src_batch_stride % 4 == 0 &&
+    const bool vec = pixels % 4 == 0 && is_aligned(src, 16) && is_aligned(grad_out, 16) && is_aligned(grad_in, 16) && src_batch_stride % 4 == 0 &&
                      src_plane_stride % 4 == 0 && grad_batch_stride % 4 == 0 && grad_plane_stride % 4 == 0 && grad_in_batch_stride % 4 == 0 &&
                      grad_in_plane_stride % 4 == 0;
     const Affine M = {m00, m01, m10, m11, (int)(m01 == 0.0f && m10 == 0.0f), (int)(renormalize != 0)};
@@ -417,7 +400,7 @@ int pbr_normal_transform_backward(const void *src, int64_t src_batch_stride, int
                                           units, total, M)
     if (vec) PBR_NT_BWD(4); else PBR_NT_BWD(1);
 #undef PBR_NT_BWD
-    return status();
+    return launch_status();
 }
 
 }  // extern "C"

@@ -33,6 +33,7 @@
 #include <cstdint>
 
 #include "../../include/pbr_hip.h"
+#include "stream_shape.hpp"
 #include "tuning.hpp"
 
 namespace pbr {
@@ -984,7 +985,7 @@ static bool launch_down(const float *large, float *small, int64_t planes, int h_
     // non-temporal 6.2).  There the lanes own 16 bytes of a row instead (4 / S columns: every line is touched by ONE instruction), loaded non-temporally,
     // three rows in flight: 111.8 (0.75) | 108.4 (0.66); on the 3-plane shapes that form costs 36.8 -> 50 | 32.0 -> 46 (it streams past the memory-side cache).
     if (S < 2 || (S > 8 && S != 16) || w_small % 4 != 0 || w_small < 8 || h_small < 2) return false;
-    if (((reinterpret_cast<uintptr_t>(large) | reinterpret_cast<uintptr_t>(small)) & 15u) != 0) return false;
+    if (!is_aligned(large, 16) || !is_aligned(small, 16)) return false;
     const bool streams = (int64_t)planes * h_small * w_small * S * S * 4 > (256ll << 20);      // the large side does not fit the memory-side cache
     const bool narrow = streams && (S == 2 || S == 4);           // 16 bytes of a row per lane, non-temporal loads
     // columns of the small side per lane: 32 bytes of the large side's row where S divides 8, else the fewest whose S-fold is a whole number of 16-byte pieces
@@ -1022,7 +1023,7 @@ static bool launch_stream(const float *src, float *dst, int64_t planes, int h_in
                           float *workspace, hipStream_t s, bool dry = false) {
     if (fw.scale < 1.01f || fh.scale < 1.01f || fw.support != fw.scale || fh.support != fh.scale) return false;      // (support = scale: antialiased)
     if ((int)(2.0f * fw.support) + 3 > 36 || (int)(2.0f * fh.support) + 3 > 36 || w_in % 4 != 0 || w_out < 16 || h_out < 4) return false;      // (the strip form's range of taps)
-    if (((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(workspace)) & 15u) != 0) return false;
+    if (!is_aligned(src, 16) || !is_aligned(workspace, 16)) return false;
     const int kt = (int)(2.0f * fw.support) + 2, kw = (kt + 3) & ~3;    // rows of the column table (a window holds at most ceil(2 s) taps: hi - lo < 2 s + 1); taps the width pass walks: whole groups of four
     const size_t words = 4 * (size_t)h_in + (size_t)h_in + 2 * (size_t)h_out + (size_t)(kt + 2) * (size_t)w_out;
     if (words > (size_t)planes * (size_t)h_in * (size_t)w_out) return false;
@@ -1069,11 +1070,6 @@ static bool launch_stream(const float *src, float *dst, int64_t planes, int h_in
     return true;
 }
 
-static inline unsigned stream_grid(int64_t items) {
-    const int64_t blocks = (items + 255) / 256, cap = 256 * 16;
-    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
-}
-
 }  // namespace pbr
 
 extern "C" {
@@ -1107,8 +1103,7 @@ static int resize_forward(const void *src, void *dst, int64_t planes, int32_t h_
             if (dry) return PBR_OK;
             hipLaunchKernelGGL(fn, dim3((unsigned)n_groups), dim3(64), 0, s, static_cast<const float *>(src), static_cast<float *>(dst),
                                (int)h_in, (int)w_in, (int)h_out, (int)w_out, (int)groups_x, (int)groups_y, xcd_groups, fw, fh);
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+            return launch_status();
         }
     }
     if (g_resize_up2 && antialias && h_in % h_out == 0 && w_in % w_out == 0 && h_in / h_out == w_in / w_out && h_in / h_out >= 2 && h_in / h_out <= 16 &&
@@ -1116,8 +1111,7 @@ static int resize_forward(const void *src, void *dst, int64_t planes, int32_t h_
         // a whole factor 2 ... 8 | 16 on both axes: the register form (resize_down.hpp)
         *form = PBR_RESIZE_BAND_WALK;
         if (dry) return PBR_OK;
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+        return launch_status();
     }
     // Antialiased down-scales from 7 x up that are not a whole factor (17 ... 36 taps per axis, (int)(2 s) + 3: the strip form's WIDE instantiation): every input row once
     // (resize_stream.hpp).  tools/resize_stream_probe.py, us, walk | strip, after 150 ms of launches (settled clocks), every repetition on freshly allocated buffers:
@@ -1134,12 +1128,11 @@ static int resize_forward(const void *src, void *dst, int64_t planes, int32_t h_
         launch_stream(static_cast<const float *>(src), static_cast<float *>(dst), planes, h_in, w_in, h_out, w_out, fw, fh, tmp, s, dry)) {
         *form = PBR_RESIZE_ROW_WALK;
         if (dry) return PBR_OK;
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+        return launch_status();
     }
     {   // strip form: tap tables + the height-reduced strip [toh][pitch] of a toh x 64 output tile in LDS, up to 36 taps per axis
         const int kx = (int)(2.0f * fw.support) + 3, ky = (int)(2.0f * fh.support) + 3;      // taps per output: xsize <= 2 support + 2
-        const bool vec_ok = w_in % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15u) == 0;
+        const bool vec_ok = w_in % 4 == 0 && is_aligned(src, 16);
         if (kx <= 36 && ky <= 36) {                                                           // (round 5: 16 -> 36 taps, i.e. down-scales below 17x keep the one-kernel form)
             const int cols_max = (int)(kTileW * fw.scale + 2.0f * fw.support) + 4 + 3;       // + 3: window start aligned down to 16 bytes
             const int pitch = ((cols_max + 3) & ~3) + 4;                                      // + 4 floats: rows land on different banks
@@ -1170,20 +1163,18 @@ static int resize_forward(const void *src, void *dst, int64_t planes, int32_t h_
                 if (dry) return PBR_OK;
                 hipLaunchKernelGGL(strip, dim3((unsigned)(planes * tx * tyy)), dim3(256), lds, s,
                                    static_cast<const float *>(src), static_cast<float *>(dst), (int)h_out, (int)w_out, (int)w_in, tg, fw, fh, StripTables{});
-                const hipError_t e = hipGetLastError();
-                return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+                return launch_status();
             }
         }
     }
     // more than 36 taps per axis (down-scales from 17x): two passes through `workspace`
     *form = PBR_RESIZE_TWO_PASS;
     if (dry) return PBR_OK;
-    hipLaunchKernelGGL(resize_width_kernel, dim3(stream_grid(planes * h_in * w_out)), dim3(256), 0, s,
+    hipLaunchKernelGGL(resize_width_kernel, dim3(stream_grid(planes * h_in * w_out, 16)), dim3(256), 0, s,
                        static_cast<const float *>(src), tmp, planes * h_in, (int)w_out, fw);
-    hipLaunchKernelGGL(resize_height_kernel, dim3(stream_grid(planes * h_out * w_out)), dim3(256), 0, s,
+    hipLaunchKernelGGL(resize_height_kernel, dim3(stream_grid(planes * h_out * w_out, 16)), dim3(256), 0, s,
                        tmp, static_cast<float *>(dst), planes, (int)h_out, (int)w_out, fh);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+    return launch_status();
 }
 
 int pbr_resize_bilinear(const void *src, void *dst, int64_t planes, int32_t h_in, int32_t w_in, int32_t h_out,
@@ -1228,8 +1219,7 @@ int pbr_resize_bilinear_backward(const void *grad_out, void *grad_in, int64_t pl
         // the forward's scale 1 / S is then exact and its two weights are the same for every S-th output; with 1/3, 1/5 ... the forward's fp32 tap positions drift
         // by ~6e-8 of the index, and the exact transpose of THAT is what the two-tap transpose below forms.)
         // 3 x 4096^2 upstream -> 2048^2: see DESIGN.md section 3 (the two-tap transpose below: 44.4 us, 1.17 x the bytes -- its lanes' windows overlap past L2)
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+        return launch_status();
     }
     if (g_resize_up2 && fw.scale <= 1.0f && fh.scale <= 1.0f && fw.scale >= 0.34f && fh.scale >= 0.25f && w_out >= 16) {
         // gradient of an up-scale (up to 3x across, 4x down the rows): the register-only transpose of the two-tap forward (round 4;
@@ -1243,8 +1233,7 @@ int pbr_resize_bilinear_backward(const void *grad_out, void *grad_in, int64_t pl
             auto fn = need <= 8 ? resize_up2_backward_kernel<8, R> : (need <= 12 ? resize_up2_backward_kernel<12, R> : resize_up2_backward_kernel<16, R>);
             hipLaunchKernelGGL(fn, dim3((unsigned)n_groups), dim3(64), 0, s, static_cast<const float *>(grad_out), static_cast<float *>(grad_in),
                                (int)h_in, (int)w_in, (int)h_out, (int)w_out, (int)groups_x, (int)groups_y, xcd_groups, fw, fh);
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+            return launch_status();
         }
     }
     auto fits = [](const AxisFilter &f) { return (int)((2.0f * f.support + 2.0f) / f.scale) + 2 <= kBwdMaxTaps; };
@@ -1274,13 +1263,12 @@ int pbr_resize_bilinear_backward(const void *grad_out, void *grad_in, int64_t pl
             auto fn = banded ? (need <= 8 ? resize_backward_gather_kernel<8, 8, true> : (need <= 12 ? resize_backward_gather_kernel<12, 8, true> : resize_backward_gather_kernel<16, 8, true>))
                              : (need <= 8 ? resize_backward_gather_kernel<8, 8, false> : (need <= 12 ? resize_backward_gather_kernel<12, 8, false> : resize_backward_gather_kernel<16, 8, false>));
             hipLaunchKernelGGL(fn, dim3((unsigned)n_groups), dim3(64), 0, s, g, gi, (int)h_in, (int)w_in, (int)h_out, (int)w_out, (int)ggx, (int)ggy, xcd_groups, tb);
-            const hipError_t e = hipGetLastError();
-            return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+            return launch_status();
         }
         // One pass: the strip kernel with the transposed tables (resize_strip_kernel<true>): a toh x 64 tile of the gradient, the
         // rows pass from global memory into the LDS strip, the columns pass out of it.  3 x 2048^2 gradient -> 4096^2: see DESIGN.md 3.8.
         const int kx = (int)((2.0f * fw.support + 2.0f) / fw.scale) + 2, ky = (int)((2.0f * fh.support + 2.0f) / fh.scale) + 2;     // <= kBwdMaxTaps
-        const bool vec_ok = w_out % 4 == 0 && (reinterpret_cast<uintptr_t>(grad_out) & 15u) == 0;
+        const bool vec_ok = w_out % 4 == 0 && is_aligned(grad_out, 16);
         const int cols_max = (int)((float)(kTileW - 1 + 2.0f * fw.support) / fw.scale) + 8;     // upstream columns a tile of 64 reads, + alignment
         const int pitch = ((cols_max + 3) & ~3) + 4;
         auto lds_for = [&](int rows) {
@@ -1299,8 +1287,7 @@ int pbr_resize_bilinear_backward(const void *grad_out, void *grad_in, int64_t pl
             if (chunk > n_tiles / 8) chunk = n_tiles / 8;
             // 16-byte stores where the gradient is at least twice its upstream (2048^2 -> 4096^2: 66.7 against 69.3 us; the other way,
             // 4096^2 -> 2048^2, 70.6 against 59.4: a quarter of the lanes then walk the LDS strip)
-            const int quads = (int64_t)h_in * w_in >= 2 * (int64_t)h_out * w_out && w_in % 4 == 0 &&
-                              (reinterpret_cast<uintptr_t>(grad_in) & 15u) == 0;
+            const int quads = (int64_t)h_in * w_in >= 2 * (int64_t)h_out * w_out && w_in % 4 == 0 && is_aligned(grad_in, 16);
             const StripGeom tg = {toh, (int)tx, (int)tyy, kx, ky, pitch, vec_ok ? 1 : 0, (int)chunk, (int)(chunk ? (n_tiles / (8 * chunk)) * 8 * chunk : 0), quads};
             const StripTables tb = {lo_x, cnt_x, lo_y, cnt_y, wx, wy, (int)w_in, (int)h_in, (int)h_out, nullptr, nullptr, nullptr};
             auto strip = quads ? resize_strip_kernel<true, true> : resize_strip_kernel<true, false>;
@@ -1312,11 +1299,10 @@ int pbr_resize_bilinear_backward(const void *grad_out, void *grad_in, int64_t pl
     } else {                                                                                  // many contributors per input: the generic passes
         hipLaunchKernelGGL(resize_norm_kernel, dim3((h_out + 255) / 256), dim3(256), 0, s, inv_y, (int)h_out, fh);
         hipLaunchKernelGGL(resize_norm_kernel, dim3((w_out + 255) / 256), dim3(256), 0, s, inv_x, (int)w_out, fw);
-        hipLaunchKernelGGL(resize_backward_rows_kernel, dim3(stream_grid(planes * h_in * w_out)), dim3(256), 0, s, g, tmp, inv_y, planes, (int)h_out, (int)w_out, fh);
-        hipLaunchKernelGGL(resize_backward_cols_kernel, dim3(stream_grid(planes * h_in * w_in)), dim3(256), 0, s, tmp, gi, inv_x, planes * h_in, (int)w_out, fw);
+        hipLaunchKernelGGL(resize_backward_rows_kernel, dim3(stream_grid(planes * h_in * w_out, 16)), dim3(256), 0, s, g, tmp, inv_y, planes, (int)h_out, (int)w_out, fh);
+        hipLaunchKernelGGL(resize_backward_cols_kernel, dim3(stream_grid(planes * h_in * w_in, 16)), dim3(256), 0, s, tmp, gi, inv_x, planes * h_in, (int)w_out, fw);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -1,10 +1,20 @@
-// stream_shape.hpp -- launch shape of the streaming map kernels (map_ops.hip, blend.hip).
+// stream_shape.hpp -- launch shape of the streaming kernels: stream_shape with its per-kernel rules, and stream_grid, the grid of the
+// grid-stride kernels.  Every translation unit with a launcher includes it, directly or through ct_launch.hpp, and with it
+// launch_util.hpp (hip_code, launch_status, call_status, is_aligned, resident_cus, Elem<T>).
 #pragma once
 #include <cstddef>
 
+#include "launch_util.hpp"
 #include "tuning.hpp"
 
 namespace pbr {
+
+// Grid of a grid-stride kernel with 256-lane workgroups: one lane per item up to `per_cu` workgroups for each of 256 CUs, walking beyond;
+// one workgroup for a count below 1.
+inline unsigned stream_grid(int64_t work_items, int64_t per_cu = 8) {
+    const int64_t blocks = (work_items + 255) / 256, cap = 256 * per_cu;
+    return (unsigned)(blocks < 1 ? 1 : (blocks > cap ? cap : blocks));
+}
 
 // Launch shape of the streaming map kernels (map_ops.hip, blend.hip): all of them are grid-stride loops over blockDim-agnostic
 // indices, so the shape is the launcher's choice.  shape 0 = 2048 workgroups of 256 lanes walking the data, 1 = one item per lane in

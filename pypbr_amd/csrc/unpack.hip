@@ -14,6 +14,7 @@
 
 #include "../../include/pbr_hip.h"
 #include "brdf_math.hpp"
+#include "stream_shape.hpp"
 
 namespace pbr {
 
@@ -92,7 +93,7 @@ static int unpack(const void *src, int channels, int height, int width, int64_t 
                   hipStream_t s) {
     const int64_t plane = (int64_t)height * width;
     const bool dense = sc == 1 && sw == channels && sh == (int64_t)width * channels && width % 4 == 0 &&
-                       (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+                       is_aligned(src, 4) && is_aligned(dst, 16);
     if (dense && normal && channels == 3) launch_dense<U, 3, true>(src, dst, plane, divisor, s);
     else if (dense && normal && channels == 2) launch_dense<U, 2, true>(src, dst, plane, divisor, s);
     else if (dense && !normal && channels == 1) launch_dense<U, 1, false>(src, dst, plane, divisor, s);
@@ -102,8 +103,7 @@ static int unpack(const void *src, int channels, int height, int width, int64_t 
         if (normal) hipLaunchKernelGGL((unpack_strided_kernel<U, true>), grid, dim3(256), 0, s, static_cast<const U *>(src), dst, channels, height, width, sc, sh, sw, divisor);
         else hipLaunchKernelGGL((unpack_strided_kernel<U, false>), grid, dim3(256), 0, s, static_cast<const U *>(src), dst, channels, height, width, sc, sh, sw, divisor);
     }
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? PBR_OK : 1000 + (int)e;
+    return launch_status();
 }
 
 }  // namespace pbr
