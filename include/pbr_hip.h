@@ -412,6 +412,29 @@ int pbr_normal_transform_backward(const void *src, int64_t src_batch_stride, int
                                   int32_t renormalize, void *stream);
 
 /*
+ * The geometric material transforms of pypbr/materials/base.py -- crop (:506-522, in-bounds), tile (:524-537), flip_horizontal /
+ * flip_vertical (:605-639), roll (:641-655) -- and every chain of them as ONE index map per axis:
+ *     src(i) = (offset + step * i) mod N,   i in [0, L),   step = +1 | -1,   0 <= offset < N
+ * with N the source extent and L the output extent (L < N a crop, L > N a tile).  src [batch][planes][h_src][w_src] ->
+ * dst [batch][planes][h_out][w_out]; rows dense, batch and plane strides in ELEMENTS (src: any non-negative value; dst: positive where
+ * there is more than one image / plane).  Bit i of `negate_mask` negates plane i (a flip's sign on a normal map's x or y plane), so
+ * planes <= 32.  `dtype` PBR_F32 | PBR_F16: values are copied, negated ones have their sign bit flipped -- nothing is rounded.
+ * `dst` must NOT overlap `src` (the kernel reads through __restrict__ pointers; a remap is not an in-place operation).
+ * A bad shape, stride, offset, step or dtype returns PBR_ERR_SHAPE / PBR_ERR_DTYPE before anything is launched.  No workspace.
+ */
+int pbr_remap_planes(const void *src, int64_t src_batch_stride, int64_t src_plane_stride, void *dst, int64_t dst_batch_stride,
+                     int64_t dst_plane_stride, int32_t batch, int32_t planes, int32_t h_src, int32_t w_src, int32_t h_out, int32_t w_out,
+                     int32_t y_offset, int32_t y_step, int32_t x_offset, int32_t x_step, uint32_t negate_mask, int dtype, void *stream);
+/* Gradient of pbr_remap_planes w.r.t. `src`, fp32, as a GATHER: source texel p of an axis sums the grad_out values of its preimages
+ * i0 + k N < L, i0 = step (p - offset) mod N, in registers and in a fixed order (rows outer, columns inner, k ascending), applies the
+ * plane's sign and writes 0 where a crop left no preimage.  No atomics, no workspace; every element of grad_src is written.
+ * grad_out [batch][planes][h_out][w_out] -> grad_src [batch][planes][h_src][w_src], strides as above; they must not overlap. */
+int pbr_remap_planes_backward(const void *grad_out, int64_t grad_out_batch_stride, int64_t grad_out_plane_stride, void *grad_src,
+                              int64_t grad_src_batch_stride, int64_t grad_src_plane_stride, int32_t batch, int32_t planes, int32_t h_src,
+                              int32_t w_src, int32_t h_out, int32_t w_out, int32_t y_offset, int32_t y_step, int32_t x_offset,
+                              int32_t x_step, uint32_t negate_mask, void *stream);
+
+/*
  * MaterialBase._to_tensor for PIL images, base.py:143-164, on the device: an image's own samples -- uint8 (`bits` 8; torchvision's
  * to_tensor: (H,W,C) -> float32 (C,H,W) / 255) or uint16 (`bits` 16; base.py:146-152: / 65535.0) -- become the float32 planar map
  * dst [channels][height][width] (dense).  The division is IEEE-exact: every one of the 256 / 65 536 possible samples gives the float

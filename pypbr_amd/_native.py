@@ -43,6 +43,7 @@ EXPORTS = (
     "pbr_mse_step_workspace_bytes", "pbr_cook_torrance_mse_step", "pbr_scale_by_device_scalar", "pbr_scale_list_by_device_scalar", "pbr_device_params_bytes", "pbr_prepare_device_params", "pbr_tuning_init", "pbr_build_id", "pbr_unpack_image",
     "pbr_backward_folded_workspace_bytes", "pbr_cook_torrance_backward_folded",
     "pbr_normal_from_height", "pbr_normal_from_height_backward", "pbr_normal_transform", "pbr_normal_transform_backward",
+    "pbr_remap_planes", "pbr_remap_planes_backward",
 )
 
 
@@ -194,6 +195,10 @@ def lib():
     for name in ("pbr_normal_from_height", "pbr_normal_from_height_backward", "pbr_normal_transform", "pbr_normal_transform_backward"):
         getattr(L, name).restype = ctypes.c_int
     L.pbr_decode_normal_backward.restype = ctypes.c_int
+    u32 = ctypes.c_uint32
+    L.pbr_remap_planes.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32, ctypes.c_int, vp]
+    L.pbr_remap_planes_backward.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32, vp]
+    L.pbr_remap_planes.restype = L.pbr_remap_planes_backward.restype = ctypes.c_int
     for name in ("pbr_srgb_to_linear", "pbr_linear_to_srgb", "pbr_metallic_to_specular",
                  "pbr_specular_to_metallic", "pbr_decode_normal", "pbr_abi_version", "pbr_set_tuning",
                  "pbr_bytes_per_pixel"):

@@ -1,6 +1,6 @@
 """Run reference scripts unchanged: `import pypbr_amd.compat; pypbr_amd.compat.install()` registers
-`pypbr`, `pypbr.models`, `pypbr.materials`, `pypbr.utils`, `pypbr.io` and `pypbr.blending` as aliases of the
-pypbr_amd modules, so that e.g. examples/example_brdf.py's
+`pypbr`, `pypbr.models`, `pypbr.materials`, `pypbr.utils`, `pypbr.io`, `pypbr.blending`, `pypbr.transforms` and
+`pypbr.transforms.functional` as aliases of the pypbr_amd modules, so that e.g. examples/example_brdf.py's
 
     from pypbr.models import CookTorranceBRDF
     from pypbr.io import load_material_from_folder
@@ -8,9 +8,11 @@ pypbr_amd modules, so that e.g. examples/example_brdf.py's
 resolve to the MI355X implementation.  The Cook-Torrance path and the calls either side of it
 (load, blend, resize, tile) exist here, and so do the normal-map operations: `pypbr.utils.compute_normal_from_height`,
 `rotate_normals`, `invert_normal` and the material methods `compute_normal_from_height`,
-`adjust_normal_strength`, `invert_normal` resolve through the aliases above.  Everything else of PyPBR
-(transforms, compute_height_from_normal, crop / rotate / flips / roll, saving, ...) is out of scope and raises
-ImportError/AttributeError as an absent module would."""
+`adjust_normal_strength`, `invert_normal` resolve through the aliases above.  The geometric transforms exist too: the material
+methods `crop` (in-bounds), `flip_horizontal`, `flip_vertical`, `roll`, and `pypbr.transforms` with upstream's classes and functional
+forms, `Compose` running a chain of geometric stages as one kernel launch.  Everything else of PyPBR (the rotate family --
+`MaterialBase.rotate`, `transforms.Rotate` / `RandomRotate`, `functional.rotate` / `random_rotate` --, out-of-bounds crops,
+compute_height_from_normal, saving, ...) is out of scope and raises ImportError/AttributeError as an absent module would."""
 import sys
 import types
 
@@ -18,7 +20,7 @@ import types
 def install(force: bool = False) -> types.ModuleType:
     """Registers the aliases.  Refuses to shadow an already-imported real `pypbr` unless `force`."""
     import pypbr_amd
-    from pypbr_amd import blending, io, materials, models, utils
+    from pypbr_amd import blending, io, materials, models, transforms, utils
 
     existing = sys.modules.get("pypbr")
     if existing is not None and not getattr(existing, "__pypbr_amd_alias__", False) and not force:
@@ -30,7 +32,9 @@ def install(force: bool = False) -> types.ModuleType:
     pkg.__pypbr_amd_alias__ = True
     pkg.__version__ = pypbr_amd.__version__
     sys.modules["pypbr.blending.functional"] = blending
-    for name, mod in (("models", models), ("materials", materials), ("utils", utils), ("io", io), ("blending", blending)):
+    sys.modules["pypbr.transforms.functional"] = transforms.functional
+    for name, mod in (("models", models), ("materials", materials), ("utils", utils), ("io", io), ("blending", blending),
+                      ("transforms", transforms)):
         setattr(pkg, name, mod)
         sys.modules["pypbr." + name] = mod
     sys.modules["pypbr"] = pkg

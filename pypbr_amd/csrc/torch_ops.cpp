@@ -424,6 +424,47 @@ Tensor normal_transform_backward(const Tensor &normal, const Tensor &grad_out, d
     return gi.reshape(normal.sizes());
 }
 
+// The geometric transforms as one index map (base.py:506-537, :605-655; csrc/geometry.hip): [..., P, H, W] -> [..., P, h_out, w_out]
+Tensor planes_as_batch(const Tensor &t, const char *what) {
+    TORCH_CHECK(t.is_cuda(), what, " needs a tensor on a ROCm device; there is no CPU path");
+    TORCH_CHECK_VALUE(t.dim() >= 3, what, ": expected [..., P, H, W], got ", t.sizes());
+    Tensor x = t.contiguous();
+    return x.reshape({-1, x.size(-3), x.size(-2), x.size(-1)});
+}
+
+Tensor remap_planes(const Tensor &texture, int64_t y_offset, int64_t y_step, int64_t x_offset, int64_t x_step, int64_t negate_mask,
+                    int64_t h_out, int64_t w_out) {
+    const Tensor t = planes_as_batch(texture, "pbr_hip::remap_planes");
+    TORCH_CHECK_VALUE(h_out >= 1 && w_out >= 1 && h_out <= INT32_MAX && w_out <= INT32_MAX, "pbr_hip::remap_planes: the output size must be positive");
+    TORCH_CHECK_VALUE(negate_mask >= 0 && negate_mask <= (int64_t)UINT32_MAX, "pbr_hip::remap_planes: negate_mask is one bit per plane (at most 32)");
+    const c10::DeviceGuard guard(t.device());
+    const int64_t B = t.size(0), P = t.size(1), H = t.size(2), W = t.size(3);
+    Tensor out = at::empty({B, P, h_out, w_out}, t.options());
+    check_status(pbr_remap_planes(t.data_ptr(), t.stride(0), t.stride(1), out.data_ptr(), out.stride(0), out.stride(1), (int32_t)B, (int32_t)P,
+                                  (int32_t)H, (int32_t)W, (int32_t)h_out, (int32_t)w_out, (int32_t)y_offset, (int32_t)y_step, (int32_t)x_offset,
+                                  (int32_t)x_step, (uint32_t)negate_mask, dtype_code(t, "texture"), current_stream(t)), "pbr_hip::remap_planes");
+    std::vector<int64_t> shape(texture.sizes().begin(), texture.sizes().end());
+    shape[shape.size() - 2] = h_out; shape[shape.size() - 1] = w_out;
+    return out.reshape(shape);
+}
+
+Tensor remap_planes_backward(const Tensor &grad_out, int64_t h_src, int64_t w_src, int64_t y_offset, int64_t y_step, int64_t x_offset,
+                             int64_t x_step, int64_t negate_mask) {
+    const Tensor g = planes_as_batch(grad_out.to(at::kFloat), "pbr_hip::remap_planes_backward");
+    TORCH_CHECK_VALUE(h_src >= 1 && w_src >= 1 && h_src <= INT32_MAX && w_src <= INT32_MAX, "pbr_hip::remap_planes_backward: the source size must be positive");
+    TORCH_CHECK_VALUE(negate_mask >= 0 && negate_mask <= (int64_t)UINT32_MAX, "pbr_hip::remap_planes_backward: negate_mask is one bit per plane (at most 32)");
+    const c10::DeviceGuard guard(g.device());
+    const int64_t B = g.size(0), P = g.size(1), Ho = g.size(2), Wo = g.size(3);
+    Tensor gi = at::empty({B, P, h_src, w_src}, g.options());
+    check_status(pbr_remap_planes_backward(g.data_ptr(), g.stride(0), g.stride(1), gi.data_ptr(), gi.stride(0), gi.stride(1), (int32_t)B, (int32_t)P,
+                                           (int32_t)h_src, (int32_t)w_src, (int32_t)Ho, (int32_t)Wo, (int32_t)y_offset, (int32_t)y_step,
+                                           (int32_t)x_offset, (int32_t)x_step, (uint32_t)negate_mask, current_stream(g)),
+                 "pbr_hip::remap_planes_backward");
+    std::vector<int64_t> shape(grad_out.sizes().begin(), grad_out.sizes().end());
+    shape[shape.size() - 2] = h_src; shape[shape.size() - 1] = w_src;
+    return gi.reshape(shape);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(pbr_hip, m) {
@@ -452,6 +493,8 @@ TORCH_LIBRARY(pbr_hip, m) {
     m.def("normal_from_height_backward(Tensor height, Tensor grad_normal, float scale, bool directx) -> Tensor");
     m.def("normal_transform(Tensor normal, float m00, float m01, float m10, float m11, bool renormalize) -> Tensor");
     m.def("normal_transform_backward(Tensor normal, Tensor grad_out, float m00, float m01, float m10, float m11, bool renormalize) -> Tensor");
+    m.def("remap_planes(Tensor texture, int y_offset, int y_step, int x_offset, int x_step, int negate_mask, int h_out, int w_out) -> Tensor");
+    m.def("remap_planes_backward(Tensor grad_out, int h_src, int w_src, int y_offset, int y_step, int x_offset, int x_step, int negate_mask) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(pbr_hip, CUDA, m) {       // the CUDA dispatch key is the HIP device on a ROCm build of torch
@@ -471,4 +514,6 @@ TORCH_LIBRARY_IMPL(pbr_hip, CUDA, m) {       // the CUDA dispatch key is the HIP
     m.impl("normal_from_height_backward", &normal_from_height_backward);
     m.impl("normal_transform", &normal_transform);
     m.impl("normal_transform_backward", &normal_transform_backward);
+    m.impl("remap_planes", &remap_planes);
+    m.impl("remap_planes_backward", &remap_planes_backward);
 }

@@ -575,6 +575,88 @@ class MaterialBase:
                     store[name] = t.repeat(*((1,) * (t.dim() - 2) + (ny, nx)))
         return self
 
+    # -- geometric transforms (base.py:506-522, :605-655), in place, returning self; csrc/geometry.hip.  Each is an index map, and so is a
+    # chain of them (functional.PlaneMap; transforms.Compose hands a whole run over as `stages`).  As with the normal-map operations above,
+    # the normal map is stored as it comes out of the kernel, never through _process_normal_map: a flipped flat normal (0, 0, 1) has no
+    # negative value and would be decoded a second time.
+    def _geometry(self, stages, fresh: bool = False):
+        """Runs geometric stages (functional.fold_stages) over every map.  All float32 (C,H,W) maps of one size go through ONE
+        pbr_remap_planes launch per folded map, over all their planes; other maps (batches, fp16) and maps that require grad one at a
+        time through the differentiable path.  Everything is checked and folded on the host before any device work.  `fresh`: maps the
+        stages leave as they are become copies (the result must not share memory with the maps it was made from)."""
+        stages = list(stages)
+        ny, nx = self.lazy_tile
+        if (ny, nx) != (1, 1):                                   # a recorded tile(n) is the first stage of the chain
+            stages.insert(0, ("tile", ny, nx))
+        sizes = {tuple(t.shape[-2:]) for t in self._raw.values() if t is not None}
+        pending = self.__dict__.get("_lazy_blend")
+        if pending is not None:
+            sizes |= {tuple(t.shape[-2:]) for t in pending[0].values() if t is not None}
+        folded = {hw: F_.fold_stages(hw[0], hw[1], stages) for hw in sizes}      # raises for a crop outside a map
+        maps = self._resident(keep=True)
+        object.__setattr__(self, "_lazy_tile", (1, 1))
+        store = self._raw
+
+        def run(t, chain, negate):
+            for pm in chain:
+                t = F_.remap_planes(t, pm.ymap, pm.xmap, negate=[p for p, on in zip(negate, pm.neg) if on], out_size=pm.size)
+            return t
+        groups = {}
+        for name, t in maps.items():
+            chain = folded[tuple(t.shape[-2:])]
+            if not chain:
+                store[name] = t.clone() if fresh else t
+            elif t.dim() == 3 and t.dtype == torch.float32 and not (t.requires_grad and torch.is_grad_enabled()):
+                groups.setdefault(tuple(t.shape[-2:]), []).append(name)
+            else:
+                c0 = t.dim() - 3
+                store[name] = run(t, chain, (0, 1) if name == "normal" and t.shape[c0] >= 2 else ())
+        for hw, names in groups.items():
+            names.sort(key=lambda k: maps[k].data_ptr())
+            while names:                                         # at most 32 planes share a launch (one sign bit per plane)
+                take, planes = [], 0
+                while names and planes + maps[names[0]].shape[0] <= 32:
+                    planes += maps[names[0]].shape[0]
+                    take.append(names.pop(0))
+                if not take:                                     # a single map of more than 32 planes: plane by plane blocks
+                    k = names.pop(0)
+                    store[k] = torch.cat([run(maps[k][i:i + 32], folded[hw], ()) for i in range(0, maps[k].shape[0], 32)], dim=0)
+                    continue
+                ts = [maps[k] for k in take]
+                first = {k: sum(t.shape[0] for t in ts[:i]) for i, k in enumerate(take)}
+                negate = (first["normal"], first["normal"] + 1) if "normal" in first and maps["normal"].shape[0] >= 2 else ()
+                out = run(_as_block(ts), folded[hw], negate)
+                for k, t in zip(take, ts):
+                    store[k] = out[first[k]:first[k] + t.shape[0]]
+        return self
+
+    def crop(self, top: int, left: int, height: int, width: int):
+        """base.py:506-522 for crops that lie inside every map; a crop that does not raises ValueError before any device work (upstream
+        pads it with zeros through torchvision: INTEGRATION.md)."""
+        return self._geometry([("crop", top, left, height, width)])
+
+    def flip_horizontal(self):
+        """base.py:605-621: every map mirrored along its width, the normal map's x negated."""
+        return self._geometry([("flip_h",)])
+
+    def flip_vertical(self):
+        """base.py:623-639: every map mirrored along its height, the normal map's y negated."""
+        return self._geometry([("flip_v",)])
+
+    def roll(self, shift: Tuple[int, int]):
+        """base.py:641-655: torch.roll over (height, width) by shift = (dy, dx); any integers."""
+        dy, dx = shift
+        return self._geometry([("roll", int(dy), int(dx))])
+
+    def _shallow(self):
+        """A material over the SAME tensors with a map dict of its own (what a fused transforms.Compose run starts from: every map is
+        about to be replaced, so nothing is cloned)."""
+        new = copy.copy(self)
+        for k in ("_device_cache", "_plan_cache", "_plan_seen"):
+            new.__dict__.pop(k, None)
+        new.__dict__["_store"] = dict(self._raw)
+        return new
+
     def clone(self):
         """Deep copy: tensors cloned, flags copied (base.py:880-912)."""
         self.materialize_blend()          # a pending lazy blend is carried out first: the copy must not blend again

@@ -161,6 +161,21 @@ def _register():
         return (torch.ops.pbr_hip.normal_transform_backward(normal, grad_out, *ctx.args).to(normal.dtype),) + (None,) * 5
     lib.register_autograd("pbr_hip::normal_transform", transform_backward, setup_context=transform_setup)
 
+    # the geometric transforms as one index map (base.py:506-537, :605-655; csrc/geometry.hip): the gradient is a gather, in float32
+    lib.register_fake("pbr_hip::remap_planes")(
+        lambda texture, y_offset, y_step, x_offset, x_step, negate_mask, h_out, w_out: texture.new_empty(tuple(texture.shape[:-2]) + (h_out, w_out)))
+    lib.register_fake("pbr_hip::remap_planes_backward")(
+        lambda grad_out, h_src, w_src, y_offset, y_step, x_offset, x_step, negate_mask:
+        grad_out.new_empty(tuple(grad_out.shape[:-2]) + (h_src, w_src), dtype=torch.float32))
+
+    def remap_setup(ctx, inputs, output):
+        ctx.geom = (inputs[0].shape[-2], inputs[0].shape[-1]) + tuple(inputs[1:6])
+        ctx.dtype = inputs[0].dtype
+
+    def remap_backward(ctx, grad_out):
+        return (torch.ops.pbr_hip.remap_planes_backward(grad_out, *ctx.geom).to(ctx.dtype),) + (None,) * 7
+    lib.register_autograd("pbr_hip::remap_planes", remap_backward, setup_context=remap_setup)
+
     names = ("albedo", "normal", "roughness", "metallic", "specular", "view_dir", "lights", "intensities")
 
     def setup_context(ctx, inputs, output):
