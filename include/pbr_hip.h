@@ -435,6 +435,45 @@ int pbr_remap_planes_backward(const void *grad_out, int64_t grad_out_batch_strid
                               int32_t x_step, uint32_t negate_mask, void *stream);
 
 /*
+ * Packed material tensors: MaterialBase.from_tensor (base.py:416-487), as_tensor (:319-414) and normal_rgb (:279-291) as ONE launch over
+ * a table of at most PBR_MAX_PLANE_OPS plane operations, each over [batch] images of `pixels` elements per plane (strides in ELEMENTS):
+ *   PBR_PLANE_AFFINE     one plane:  dst = src * scale + bias.  (1, 0) copies; (0.5, 0.5) is from_tensor's is_normalized, (2, -1) as_tensor's
+ *                        (t - 0.5) / 0.5: each is one rounding of an exact product, so the results are the reference's bit for bit.
+ *   PBR_PLANE_NORMAL_XY  two planes (src, src + src_plane_stride) -> three (dst + k dst_plane_stride): _compute_normal_map_z_component,
+ *                        base.py:223-242, after a = src * scale + bias: v = 2 a - 1, s = x^2 + y^2, z = sqrt(max(1 - s, 1e-6)),
+ *                        n = (x, y, z) / max(|(x, y, z)|, 1e-12).  x^2, y^2, their sum and 1 - s are each rounded on their own, sqrt and the
+ *                        division are IEEE: z is ill-conditioned near the unit circle and this order is what keeps it within 1e-6 there.
+ * `dtype` PBR_F32 | PBR_F16 is the storage type of every source and destination (arithmetic in fp32).  Plane bases need element alignment
+ * only.  Nothing a launch writes may overlap anything it reads.  Caller errors, before anything is launched: a NULL table, source or
+ * destination PBR_ERR_NULL_MAP; n_ops outside [1, PBR_MAX_PLANE_OPS], batch outside [1, 65535], pixels < 1, a negative stride, written
+ * planes / images on top of each other, a misaligned pointer or an overlap PBR_ERR_SHAPE; an unknown kind PBR_ERR_UNSUPPORTED; a dtype
+ * PBR_ERR_DTYPE.  No workspace.  (ABI 9: entry points added, nothing changed.)
+ */
+enum { PBR_PLANE_AFFINE = 0, PBR_PLANE_NORMAL_XY = 1 };
+#define PBR_MAX_PLANE_OPS 32
+typedef struct pbr_plane_op {
+    int32_t kind;                 /* PBR_PLANE_* */
+    int32_t reserved;
+    const void *src;              /* forward: the source plane(s).  backward: the upstream gradient, NULL = zero */
+    int64_t src_batch_stride;
+    int64_t src_plane_stride;     /* NORMAL_XY only */
+    void *dst;                    /* forward: the destination plane(s).  backward: the gradient w.r.t. the forward's source plane(s) */
+    int64_t dst_batch_stride;
+    int64_t dst_plane_stride;     /* NORMAL_XY only */
+    const void *input;            /* backward of NORMAL_XY: the forward's source (x, y planes); ignored otherwise */
+    int64_t input_batch_stride;
+    int64_t input_plane_stride;
+    float scale;
+    float bias;
+} pbr_plane_op;
+int pbr_plane_ops(const pbr_plane_op *ops, int32_t n_ops, int32_t batch, int64_t pixels, int dtype, void *stream);
+/* Gradient of pbr_plane_ops w.r.t. every source plane, as a gather over the same table with `src` / `dst` holding gradients (see the
+ * struct): AFFINE g scale; NORMAL_XY F.normalize's adjoint (g - n (n . g)) / |v|, z's dependence on x and y where 1 - s >= 1e-6 (torch's
+ * clamp passes the gradient there, the bound included; nothing where it clamped), then x 2 and x scale.  Every element of every `dst`
+ * is written exactly once; an operation whose `src` is NULL writes zeros.  fp32 only (`dtype` must be PBR_F32). */
+int pbr_plane_ops_backward(const pbr_plane_op *ops, int32_t n_ops, int32_t batch, int64_t pixels, int dtype, void *stream);
+
+/*
  * MaterialBase._to_tensor for PIL images, base.py:143-164, on the device: an image's own samples -- uint8 (`bits` 8; torchvision's
  * to_tensor: (H,W,C) -> float32 (C,H,W) / 255) or uint16 (`bits` 16; base.py:146-152: / 65535.0) -- become the float32 planar map
  * dst [channels][height][width] (dense).  The division is IEEE-exact: every one of the 256 / 65 536 possible samples gives the float

@@ -44,6 +44,7 @@ EXPORTS = (
     "pbr_backward_folded_workspace_bytes", "pbr_cook_torrance_backward_folded",
     "pbr_normal_from_height", "pbr_normal_from_height_backward", "pbr_normal_transform", "pbr_normal_transform_backward",
     "pbr_remap_planes", "pbr_remap_planes_backward",
+    "pbr_plane_ops", "pbr_plane_ops_backward",
 )
 
 
@@ -97,6 +98,18 @@ class MapGrads(ctypes.Structure):
 
 
 BLEND_SIGN_COMPUTE, BLEND_SIGN_GIVEN = 0, 1
+
+PLANE_AFFINE, PLANE_NORMAL_XY = 0, 1
+MAX_PLANE_OPS = 32
+
+
+class PlaneOp(ctypes.Structure):
+    """pbr_plane_op: one operation of a pbr_plane_ops / pbr_plane_ops_backward table (strides in elements)."""
+    _fields_ = [("kind", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("src", ctypes.c_void_p), ("src_batch_stride", ctypes.c_int64), ("src_plane_stride", ctypes.c_int64),
+                ("dst", ctypes.c_void_p), ("dst_batch_stride", ctypes.c_int64), ("dst_plane_stride", ctypes.c_int64),
+                ("input", ctypes.c_void_p), ("input_batch_stride", ctypes.c_int64), ("input_plane_stride", ctypes.c_int64),
+                ("scale", ctypes.c_float), ("bias", ctypes.c_float)]
 
 
 SCHEDULE_AUTO, SCHEDULE_LINEAR = 0, 1
@@ -199,6 +212,8 @@ def lib():
     L.pbr_remap_planes.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32, ctypes.c_int, vp]
     L.pbr_remap_planes_backward.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32, vp]
     L.pbr_remap_planes.restype = L.pbr_remap_planes_backward.restype = ctypes.c_int
+    L.pbr_plane_ops.argtypes = L.pbr_plane_ops_backward.argtypes = [ctypes.POINTER(PlaneOp), i32, i32, i64, ctypes.c_int, vp]
+    L.pbr_plane_ops.restype = L.pbr_plane_ops_backward.restype = ctypes.c_int
     for name in ("pbr_srgb_to_linear", "pbr_linear_to_srgb", "pbr_metallic_to_specular",
                  "pbr_specular_to_metallic", "pbr_decode_normal", "pbr_abi_version", "pbr_set_tuning",
                  "pbr_bytes_per_pixel"):

@@ -10,7 +10,8 @@ resolve to the MI355X implementation.  The Cook-Torrance path and the calls eith
 `rotate_normals`, `invert_normal` and the material methods `compute_normal_from_height`,
 `adjust_normal_strength`, `invert_normal` resolve through the aliases above.  The geometric transforms exist too: the material
 methods `crop` (in-bounds), `flip_horizontal`, `flip_vertical`, `roll`, and `pypbr.transforms` with upstream's classes and functional
-forms, `Compose` running a chain of geometric stages as one kernel launch.  Everything else of PyPBR (the rotate family --
+forms, `Compose` running a chain of geometric stages as one kernel launch.  So do the packed-tensor methods `MaterialBase.from_tensor`,
+`as_tensor` and `normal_rgb` (one kernel launch each).  Everything else of PyPBR (the rotate family --
 `MaterialBase.rotate`, `transforms.Rotate` / `RandomRotate`, `functional.rotate` / `random_rotate` --, out-of-bounds crops,
 compute_height_from_normal, saving, ...) is out of scope and raises ImportError/AttributeError as an absent module would."""
 import sys

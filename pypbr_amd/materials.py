@@ -3,7 +3,7 @@
 Mirrors the part of pypbr.materials the hot path touches (SURVEY.md 8a rows H13-H16,
 8b "Material surface"): the name -> tensor dict `_maps`, attribute access to maps,
 `device`, `albedo_is_srgb` / `specular_is_srgb`, `linear_albedo` / `linear_specular`,
-`to()`, `to_linear()` / `to_srgb()`, the two workflow conversions, `tile()`.
+`to()`, `to_linear()` / `to_srgb()`, the two workflow conversions, `tile()`, the packed-tensor methods `from_tensor()` / `as_tensor()`.
 Reference: /root/reference/pypbr/materials/{base,metallic,diffuse}.py.
 
 Every computation (normal decode, colour transfer, workflow conversion) runs in
@@ -421,6 +421,113 @@ class MaterialBase:
     def as_dict(self):
         self.materialize_tile()
         return dict(self._maps)
+
+    @property
+    def normal_rgb(self):
+        """base.py:279-291: the normal map as colours, (normal + 1) * 0.5, or None -- one affine pass of csrc/packing.hip (n * 0.5 + 0.5
+        rounds once, to the same float)."""
+        normal = self._maps.get("normal")
+        if normal is None:
+            return None
+        return _through_device(normal, lambda t: F_._pack([t], [None], [(0.5, 0.5)]))
+
+    # -- packed tensors (base.py:319-487); csrc/packing.hip: one launch each way, forward and backward
+    def as_tensor(self, names=None, normalize: bool = False) -> torch.Tensor:
+        """base.py:319-414: the selected maps stacked along the channels, on the material's device.  `names`: None or empty = every map
+        in dict order; else a list of map names and (name, channel_limit) tuples.  `normalize`: every map but the normal map as
+        (t - 0.5) / 0.5.  Upstream's errors, raised before any device work.  It stacks what a reader of `_maps` would see: a pending
+        lazy blend or tile is carried out, a deferred normal decode too.  ONE launch writes the result (functional.pack_planes)."""
+        selected = []
+        if names:
+            if not isinstance(names, list):
+                raise TypeError("names must be a list of strings or tuples.")
+            for item in names:
+                if isinstance(item, str):
+                    selected.append((item, None))
+                elif isinstance(item, tuple):
+                    if len(item) != 2:
+                        raise ValueError("Each tuple in names must have exactly two elements: (map_name, channel_limit).")
+                    map_name, channel_limit = item
+                    if not isinstance(map_name, str):
+                        raise TypeError("The first element of each tuple must be a string (map name).")
+                    if not isinstance(channel_limit, int) or channel_limit <= 0:
+                        raise ValueError("The second element of each tuple must be a positive integer (channel limit).")
+                    selected.append((map_name, channel_limit))
+                else:
+                    raise TypeError("Each item in names must be either a string or a tuple of (str, int).")
+        self.materialize_blend()                                 # the names and channel counts of a pending blend are the blended maps'
+        store = self._raw
+        if not names:
+            selected = [(name, None) for name in store.keys()]
+        shapes = []
+        for name, channel_limit in selected:
+            if name not in store:
+                raise KeyError(f"Map '{name}' does not exist in the texture maps.")
+            t = store[name]
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"Map '{name}' is not a torch.Tensor.")
+            available = 3 if name == "normal" and self.__dict__.get("_raw_normal") else t.shape[-3]     # a deferred decode gives 3
+            if channel_limit is not None and channel_limit > available:
+                raise ValueError(f"Requested {channel_limit} channels for map '{name}', but only {available} channels are available.")
+            shapes.append(tuple(t.shape[:-3]) + tuple(t.shape[-2:]))
+        if not selected:
+            raise ValueError("No valid texture maps found to stack.")
+        if not all(s == shapes[0] for s in shapes):
+            raise ValueError("All texture maps must have the same spatial dimensions for concatenation.")
+        self.materialize_tile()
+        maps = self._resident(keep=True)
+        ts = [maps[name] for name, _ in selected]
+        dtype = ts[0].dtype
+        for t in ts[1:]:
+            dtype = torch.promote_types(dtype, t.dtype)
+        out = F_.pack_planes([t.to(dtype) for t in ts], [limit for _, limit in selected],
+                             [bool(normalize) and name != "normal" for name, _ in selected])
+        if out.device != self.device:
+            out = F_.to_host(out, self.device) if self.device.type == "cpu" else out.to(self.device)
+        return out
+
+    @classmethod
+    def from_tensor(cls, tensor: torch.Tensor, names=None, normal_convention: NormalConvention = NormalConvention.OPENGL,
+                    is_normalized: bool = False, device: torch.device = torch.device("cpu")):
+        """base.py:416-487: a material of this class from a packed (C_total,H,W) tensor -- (B,C_total,H,W) too -- and `names` =
+        [(map_name, channels), ...].  Every map is its channels (x 0.5 + 0.5 when `is_normalized`); a 2-channel "normal" gets its z
+        and is normalised; a 3-channel "normal" is stored AS GIVEN, as upstream stores it (no decode: under `is_normalized` it ends up
+        in [0, 1]).  Upstream's configuration errors, raised before any device work.  ONE launch writes all maps into one
+        allocation (functional.unpack_planes): they are new tensors, never views of `tensor`, and stay on the compute device -- a device
+        tensor puts the material on its device, for a CPU tensor `device` is where the maps are handed out.  Differentiable."""
+        instance = cls(normal_convention=normal_convention, device=device)
+        if not names:
+            names = []                                           # upstream: the maps of a fresh instance -- none
+        config, total = [], 0
+        for item in names:
+            if isinstance(item, str):                            # upstream infers the count from the instance's map: a fresh one has none
+                raise KeyError(f"Cannot infer channel count for map '{item}'. Provide a tuple instead.")
+            elif isinstance(item, tuple):
+                if len(item) != 2:
+                    raise ValueError("Each tuple must be (map_name, channel_limit).")
+                config.append((item[0], item[1]))
+                total += item[1]
+            else:
+                raise TypeError("Configuration items must be a string or tuple (str, int).")
+        if not isinstance(tensor, torch.Tensor) or tensor.dim() not in (3, 4):
+            raise ValueError("a packed tensor is (C,H,W) or (B,C,H,W), got %s" % (tuple(tensor.shape) if isinstance(tensor, torch.Tensor) else type(tensor),))
+        channels = tensor.shape[-3]
+        if channels != total:
+            raise ValueError(f"Packed tensor has {channels} channels, but configuration expects {total} channels.")
+        if not config:
+            return instance
+        if tensor.dtype not in (torch.float32, torch.float16):
+            raise TypeError("from_tensor supports float32/float16, got %s" % tensor.dtype)
+        if any(not isinstance(n, int) or n < 1 for _, n in config):
+            raise ValueError("a map of a packed tensor has at least one channel, got %s" % (config,))
+        if tensor.is_cuda and instance.device.type == "cpu":
+            instance.device = tensor.device                      # a device tensor pulls the material onto its device (module docstring)
+        t = tensor if tensor.is_cuda else tensor.to(_compute_device(instance.device))
+        for (name, _), m in zip(config, F_.unpack_planes(t, config, is_normalized=is_normalized)):
+            instance._raw[name] = m                              # upstream writes _maps directly: no _process_normal_map
+            if name == "normal":
+                instance.__dict__["_raw_normal"] = False
+        return instance
 
     def cache_on_device(self, enable: bool = True):
         """Opt-in: CookTorranceBRDF keeps the device copy of this CPU-resident material between calls (one upload for a

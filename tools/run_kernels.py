@@ -355,3 +355,39 @@ if want("resize_bwd"):
     us = timed(lambda: lib.pbr_resize_bilinear_backward(gout.data_ptr(), gin.data_ptr(), 3, S, S, hu, hu, 1, ws.data_ptr(), stream))
     report("resize backward 3 x 6144^2 gradient -> 4096^2 (gradient of a 1.5x up-scale: 3 planes of 6144^2 in, 3 of 4096^2 out): the two-tap transpose", "resize_up2_backward_kernel<8, 4>",
            12 * (hu * hu + PX), us)
+if want("packing"):
+    # packed material tensors (csrc/packing.hip): from_tensor / as_tensor of a 10-channel 4096^2 tensor, one launch each, beside the decode a user of
+    # the tutorial writes by hand in ATen (slice, clone, x 0.5 + 0.5, z of the 2-channel normal, normalise) on the same box in the same run
+    g = torch.Generator(device=DEV).manual_seed(0)
+    layout = [("albedo", 3), ("normal", 2), ("roughness", 1), ("metallic", 1), ("height", 1), ("opacity", 1), ("emission", 1)]
+    t = torch.rand(10, S, S, device=DEV, generator=g) * 2 - 1
+    report("packing unpack: from_tensor of 10 x 4096^2 fp32, is_normalized, 2-channel normal (10 planes in, 11 out)", "plane_ops_kernel<float>", 84 * PX,
+           timed(lambda: F.unpack_planes(t, layout, is_normalized=True)))
+
+    def by_hand():
+        out, c = [], 0
+        for name, k in layout:
+            m = t[c:c + k].clone() * 0.5 + 0.5
+            if (name, k) == ("normal", 2):
+                v = m * 2 - 1
+                z = torch.sqrt(torch.clamp(1.0 - (v ** 2).sum(0, keepdim=True), min=1e-6))
+                m = torch.nn.functional.normalize(torch.cat([v, z], dim=0), dim=0)
+            out.append(m)
+            c += k
+        return out
+    report("packing unpack by hand: the same decode as ATen calls (slice, clone, affine, z, normalise)", "(ATen)", 84 * PX, timed(by_hand))
+    maps = F.unpack_planes(t, layout, is_normalized=True)
+    flags = [name != "normal" for name, _ in layout]
+    report("packing pack: as_tensor(normalize=True) of the same material (11 planes in, 11 out)", "plane_ops_kernel<float>", 88 * PX,
+           timed(lambda: F.pack_planes(maps, None, flags)))
+    report("packing pack by hand: torch.cat of (t - 0.5) / 0.5 per map", "(ATen)", 88 * PX,
+           timed(lambda: torch.cat([(m - 0.5) / 0.5 if f else m for m, f in zip(maps, flags)], dim=0)))
+    gmaps = [torch.rand_like(m) for m in maps]
+    leaf = t.clone().requires_grad_()
+
+    def step():
+        leaf.grad = None
+        torch.autograd.backward(F.unpack_planes(leaf, layout, is_normalized=True), gmaps)
+    report("packing unpack + its backward (10 in, 11 out; then 2 input + 11 upstream planes in, 10 gradient planes out)", "plane_ops_backward_kernel",
+           (84 + 92) * PX, timed(step))
+    del t, maps, gmaps, leaf
