@@ -1,0 +1,600 @@
+"""Inputs that put render gradients on every branch of the reference's clamps, sRGB knees and sign tests.
+
+TEST INFRASTRUCTURE ONLY (like torch_oracle.py): tests/test_branch_cases_host.py fixes the inputs on the CPU; the GPU
+gradient tests of the backward kernels are to run on them.  No GPU code here.
+
+The render backward (pypbr_amd/csrc/ct_backward.hpp) is a hand-written chain rule in which every clamp, knee and sign
+test of cooktorrance.py is a select.  Random maps lit and seen from +Z never leave the ordinary branch of any of them.
+The cases below are BUILT to leave it (angles from a grid, colours from a list, intensities per case), and `decisions`
+says, from the float64 oracle alone, which side of which threshold every pixel is on:
+
+    raw N.L, N.V and N.H of every light                         against 0
+    stored albedo / specular channels that go through a decode  against 0, 0.04045 and 1
+    every light's linear contribution, per channel              against 0 and 1
+    several lights: the summed colour                           against 1
+    return_srgb: the clamped colour                             against 0.0031308
+
+A pixel is DECIDED when each of these is at least MARGIN = 1e-3 from its threshold -- 100 x the 1e-5 the forward is
+asserted to, so an fp32 evaluation cannot be on the other side.  Two readings that the definition needs:
+
+  * a light with N.L decided negative (N.L <= -MARGIN) contributes exactly 0 in any precision (radiance = clamp(N.L) = 0),
+    so its contribution is not compared with 0 again (the gradient there is exactly 0);
+  * `closed_ends`, and only that case, stores albedo channels of exactly 0.0 and 1.0 on purpose.  A stored value that
+    EQUALS a clamp end is the same number in every precision: there it counts as decided, and whether the pixel is kept
+    is settled by the agreement of the oracle's own float32 and float64 gradients (`well_conditioned`).
+
+All map values are exactly representable in fp16, so fp16 and fp32 kernels and the float64 oracle see the same inputs.
+"""
+import functools
+import math
+
+import torch
+import torch.nn.functional as TF
+
+import torch_oracle as O
+
+MARGIN = 1e-3
+BAND = 2e-5                     # the project's gradient band: |g - g64| <= BAND * (1 + |g64|)
+KNEE_DECODE, KNEE_ENCODE = 0.04045, 0.0031308
+ALBEDO_VALUES = (-0.2, 0.01, 0.03, 0.06, 0.5, 0.97, 1.3)
+
+CASE_NAMES = ("backlit", "backview", "half_clamp", "saturated", "dark", "albedo_range", "closed_ends")
+
+# name -> the variants of the case that the tests run (keyword arguments of `build`)
+VARIANTS = {
+    "backlit": [dict()],
+    "backview": [dict()],
+    "half_clamp": [dict()],
+    "saturated": [dict()],
+    "dark": [dict(return_srgb=True), dict(return_srgb=False)],
+    # linear output: a channel whose albedo decodes to ~0 is dim, and the encode knee (which `dark` owns) would leave it undecided
+    "albedo_range": [dict(return_srgb=False, **kw) for kw in (
+        dict(workflow="metallic", albedo_is_srgb=True), dict(workflow="metallic", albedo_is_srgb=False),
+        dict(workflow="specular", albedo_is_srgb=True), dict(workflow="specular", albedo_is_srgb=False),
+        dict(workflow="converted", quirk=True, albedo_is_srgb=True), dict(workflow="converted", quirk=False, albedo_is_srgb=True),
+        dict(workflow="converted", quirk=True, albedo_is_srgb=False))],
+    "closed_ends": [dict()],
+}
+
+
+# (h, w, light type, lights, tile) of every entry point of the chain rule that the GPU gradient tests are to drive; the host test
+# holds every case to its caps at every one of them
+ENTRY_CONFIGS = {
+    "fp32-vector-lanes": (24, 40, "directional", 1, 1),
+    "fp32-vector-lanes-point": (24, 40, "point", 1, 1),
+    "fp32-one-pixel": (23, 37, "point", 1, 1),
+    "multi-point": (24, 40, "point", 3, 1),
+    "multi-directional": (24, 40, "directional", 3, 1),
+    # the 16 x 120 one-tile launch is `crop(case, 120)` of this case, not a case built at 120 columns: under a directional light a pixel
+    # shades the same wherever it is, so the two launches can be compared bit for bit on the shared columns
+    "fp16-streamed": (16, 128, "directional", 1, 1),
+    "fp16-streamed-point": (16, 128, "point", 1, 1),
+    "tiled-sum-first": (12, 16, "directional", 1, 2),
+    "tiled-point": (12, 16, "point", 1, 2),
+    "tiled-two-kernels": (12, 18, "point", 1, 2),
+}
+
+
+def build_for(entry, name, kw, seed=0):
+    h, w, light_type, n_lights, tile = ENTRY_CONFIGS[entry]
+    return build(name, h, w, light_type=light_type, n_lights=n_lights, tile=tile, seed=seed, **kw)
+
+
+def crop(case, width):
+    """The first `width` columns of an untiled case, maps and upstream weight alike."""
+    assert case.tile == 1
+    names = ("albedo", "normal", "roughness", "metallic", "specular")
+    return case.replace(weight=case.weight[:, :, :width].contiguous(),
+                        **{n: t[:, :, :width].contiguous() for n, t in zip(names, case.maps()) if t is not None})
+
+
+def unfold(mask, k):
+    """Map-grid mask -> output-grid mask (the inverse direction of a tiled map's repeats)."""
+    return mask if k == 1 else mask.repeat(k, k)
+
+
+def variant_id(name, kw):
+    return name + "".join("-%s=%s" % (k, v) for k, v in sorted(kw.items()))
+
+
+def all_variants():
+    return [(n, kw) for n in CASE_NAMES for kw in VARIANTS[n]]
+
+
+def _h(t):
+    """Round to fp16-exact values."""
+    return t.to(torch.float16).to(torch.float64)
+
+
+class Case:
+    """One set of inputs.  Maps are float64 tensors holding fp16-exact values: albedo [3,h,w], normal [3,h,w], roughness [1,h,w],
+    metallic [1,h,w] | specular [3,h,w]; view [3]; lights, intensities [L,3]; weight [3,H,W] with (H, W) = tile * (h, w)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def n_lights(self):
+        return self.lights.shape[0]
+
+    @property
+    def out_shape(self):
+        return (self.albedo.shape[1] * self.tile, self.albedo.shape[2] * self.tile)
+
+    def maps(self):
+        return (self.albedo, self.normal, self.roughness, self.metallic, self.specular)
+
+    def map_names(self):
+        return [n for n, t in zip(("albedo", "normal", "roughness", "metallic", "specular"), self.maps()) if t is not None]
+
+    def replace(self, **kw):
+        d = dict(self.__dict__)
+        d.update(kw)
+        d.pop("_cache", None)
+        return Case(**d)
+
+    def product_kwargs(self):
+        """Keyword arguments of pypbr_amd.functional.cook_torrance for this case (view / light tensors are added by the caller)."""
+        kw = dict(light_type=self.light_type, light_size=self.light_size, albedo_is_srgb=self.albedo_is_srgb, return_srgb=self.return_srgb)
+        if self.workflow == "converted":
+            kw.update(convert_to_diffuse_specular=True, specular_is_srgb=self.quirk)
+        elif self.workflow == "specular":
+            kw.update(specular_is_srgb=self.specular_is_srgb)
+        if self.tile != 1:
+            kw.update(tile=self.tile)
+        return kw
+
+
+# ------------------------------------------------------------------------------------------------ the oracle on a case
+def _rep(t, k):
+    return t if (t is None or k == 1) else t.repeat(1, k, k)
+
+
+def _render_inputs(case, maps, view, lights, intens):
+    """-> (albedo, normal, roughness, metallic, specular, kwargs) of torch_oracle.cook_torrance[_multi] on the (repeated) maps;
+    the converted workflow is metallic.py's conversion followed by the specular workflow, as torch_oracle.cook_torrance_converted."""
+    a, n, r, m, s = [_rep(t, case.tile) for t in maps]
+    kw = dict(view=view, light_type=case.light_type, light_size=case.light_size)
+    if case.workflow == "converted":
+        lin = O.srgb_to_linear(a) if case.albedo_is_srgb else a
+        a, s = O.metallic_to_diffuse_specular(lin, m)
+        m = None
+        kw.update(albedo_is_srgb=False, specular_is_srgb=case.quirk)
+    else:
+        kw.update(albedo_is_srgb=case.albedo_is_srgb, specular_is_srgb=case.specular_is_srgb)
+    return a, n, r, m, s, kw
+
+
+def render(case, maps=None, view=None, lights=None, intens=None, dtype=torch.float64):
+    """The oracle's rendering of the case (of other maps / parameters when given), in `dtype`."""
+    maps = [None if t is None else t.to(dtype) for t in (case.maps() if maps is None else maps)]
+    view = (case.view if view is None else view).to(dtype)
+    lights = (case.lights if lights is None else lights).to(dtype)
+    intens = (case.intensities if intens is None else intens).to(dtype)
+    a, n, r, m, s, kw = _render_inputs(case, maps, view, lights, intens)
+    if lights.shape[0] == 1:
+        return O.cook_torrance(a, n, r, m, s, light=lights[0], intensity=intens[0], return_srgb=case.return_srgb, **kw)
+    return O.cook_torrance_multi(a, n, r, m, s, lights=lights, intensities=intens, return_srgb=case.return_srgb, **kw)
+
+
+def gradients(case, dtype=torch.float64, params=False, loss_target=None):
+    """Autograd through the oracle of sum(out * weight) -- or of mse_loss(out, loss_target) -- in `dtype`.
+    -> dict: map name -> gradient (map-sized: a tiled map owns the sum over its repeats), 'out' -> the rendering, and with
+    params=True also 'view', 'lights', 'intensities'."""
+    leaves = [None if t is None else t.to(dtype).clone().requires_grad_(True) for t in case.maps()]
+    P = [t.to(dtype).clone().requires_grad_(params) for t in (case.view, case.lights, case.intensities)]
+    out = render(case, leaves, P[0], P[1], P[2], dtype)
+    if loss_target is None:
+        (out * case.weight.to(dtype)).sum().backward()
+    else:
+        TF.mse_loss(out, loss_target.to(dtype)).backward()
+    res = {name: t.grad for name, t in zip(("albedo", "normal", "roughness", "metallic", "specular"), leaves) if t is not None}
+    res["out"] = out.detach()
+    if params:
+        res.update(view=P[0].grad, lights=P[1].grad, intensities=P[2].grad)
+    return res
+
+
+def _terms(case, maps=None):
+    """The reference's intermediate quantities in float64, from torch_oracle's own pieces (cooktorrance.py:92-182).
+    -> dict with ndv [1,H,W]; per light lists ndl, ndh [1,H,W] and u [3,H,W] (the contribution BEFORE its clamp); base, f0."""
+    dt = torch.float64
+    maps = [None if t is None else t.to(dt) for t in (case.maps() if maps is None else maps)]
+    a, n, r, m, s, kw = _render_inputs(case, maps, case.view, case.lights, case.intensities)
+    v = TF.normalize(case.view.to(dt), dim=0)
+    base = O.srgb_to_linear(a) if kw["albedo_is_srgb"] else a
+    if m is not None:
+        f0 = torch.lerp(torch.full_like(base, 0.04), base, m)
+    else:
+        f0 = O.srgb_to_linear(s) if kw["specular_is_srgb"] else s
+    _, H, W = base.shape
+    vmap = v.view(3, 1, 1).expand(3, H, W)
+    nn = TF.normalize(n, dim=0)
+    ndv_raw = (nn * vmap).sum(dim=0, keepdim=True)
+    ndv = ndv_raw.clamp(0, 1)
+    res = dict(ndv=ndv_raw, ndl=[], ndh=[], u=[], base=base, f0=f0, shade=[], rad=[])
+    for l in range(case.n_lights):
+        lmap, att = O._light_geometry(case.light_type, case.lights[l].to(dt), case.light_size, H, W, dt, 0, H)
+        half = TF.normalize(vmap + lmap, dim=0)
+        cos_theta = torch.clamp((half * vmap).sum(dim=0, keepdim=True), 0.0, 1.0)
+        fr = O._fresnel(cos_theta, f0)
+        ndl_raw = (nn * lmap).sum(dim=0, keepdim=True)
+        ndl = ndl_raw.clamp(0, 1)
+        spec = (fr * O._ggx(nn, half, r) * O._smith(nn, vmap, lmap, r)) / (4.0 * ndv * ndl + 1e-7)
+        kd = (1.0 - fr) * (1.0 - m) if m is not None else 1.0 - fr
+        rad = case.intensities[l].to(dt).view(3, 1, 1) * (ndl * att)
+        res["ndl"].append(ndl_raw)
+        res["ndh"].append((nn * half).sum(dim=0, keepdim=True))
+        res["u"].append((kd * base / math.pi + spec) * rad)
+        res["shade"].append((kd / math.pi, spec))         # u = (shade[0] * base + shade[1]) * rad
+        res["rad"].append(rad)
+    return res
+
+
+def decisions(case, maps=None):
+    """-> list of (name, value [C,H,W] float64 on the OUTPUT grid, threshold, applies [C,H,W] bool | None, exact_ok)."""
+    t = _terms(case, maps)
+    maps = case.maps() if maps is None else maps
+    k = case.tile
+    out = [("n.v", t["ndv"], 0.0, None, False)]
+    for l in range(case.n_lights):
+        lit = t["ndl"][l] > -MARGIN          # skipped only where N.L is DECIDED negative (<= -MARGIN): the contribution is then 0 in any precision
+        out.append(("n.l[%d]" % l, t["ndl"][l], 0.0, None, False))
+        out.append(("n.h[%d]" % l, t["ndh"][l], 0.0, None, False))
+        out.append(("u[%d] vs 0" % l, t["u"][l], 0.0, lit.expand_as(t["u"][l]), False))
+        out.append(("u[%d] vs 1" % l, t["u"][l], 1.0, None, False))
+    decoded = []
+    if case.albedo_is_srgb:
+        decoded.append(("albedo", _rep(maps[0].double(), k)))
+    if case.workflow == "specular" and case.specular_is_srgb:
+        decoded.append(("specular", _rep(maps[4].double(), k)))
+    if case.workflow == "converted" and case.quirk:      # the converted specular map is decoded once more
+        a = _rep(maps[0].double(), k)
+        lin = O.srgb_to_linear(a) if case.albedo_is_srgb else a
+        decoded.append(("converted specular", O.metallic_to_diffuse_specular(lin, _rep(maps[3].double(), k))[1]))
+    for name, x in decoded:
+        for thr in (0.0, KNEE_DECODE, 1.0):
+            out.append(("%s vs %g" % (name, thr), x, thr, None, thr != KNEE_DECODE and case.name == "closed_ends"))
+    colour = t["u"][0].clamp(0, 1)
+    if case.n_lights > 1:
+        total = sum(u.clamp(0, 1) for u in t["u"])
+        out.append(("sum vs 1", total, 1.0, None, False))
+        colour = total.clamp(0, 1)
+    if case.return_srgb:
+        out.append(("colour vs knee", colour, KNEE_ENCODE, None, False))
+    return out
+
+
+def threshold_decided(case, maps=None):
+    """[H,W] bool on the output grid: every compared quantity is at least MARGIN from its threshold."""
+    ok = None
+    for _, x, thr, applies, exact_ok in decisions(case, maps):
+        good = (x - thr).abs() >= MARGIN
+        if exact_ok:
+            good = good | (x == thr)
+        if applies is not None:
+            good = good | ~applies
+        good = good.all(dim=0)
+        ok = good if ok is None else ok & good
+    return ok
+
+
+def _fold_all(mask, k):
+    """Output-grid mask -> map-grid mask: a texel counts when every one of its k x k repeats does."""
+    if k == 1:
+        return mask
+    H, W = mask.shape
+    return mask.reshape(k, H // k, k, W // k).all(dim=2).all(dim=0)
+
+
+def _cached(fn):
+    @functools.wraps(fn)
+    def wrapper(case):
+        cache = case.__dict__.setdefault("_cache", {})
+        if fn.__name__ not in cache:
+            cache[fn.__name__] = fn(case)
+        return cache[fn.__name__]
+    return wrapper
+
+
+@_cached
+def reference(case):
+    """float64 gradients of the case (computed once per case object, shared, never modified)."""
+    return gradients(case, torch.float64)
+
+
+@_cached
+def well_conditioned(case):
+    """[h,w] bool on the MAP grid: the oracle's own float32 gradients lie within half the band of its float64 gradients,
+    for every map and channel."""
+    g64, g32 = reference(case), gradients(case, torch.float32)
+    ok = None
+    for name in case.map_names():
+        good = ((g32[name].double() - g64[name]).abs() <= 0.5 * BAND * (1 + g64[name].abs())).all(dim=0)
+        ok = good if ok is None else ok & good
+    return ok
+
+
+@_cached
+def decided(case):
+    """[h,w] bool on the MAP grid: threshold-decided at every repeat, and well conditioned."""
+    return _fold_all(threshold_decided(case), case.tile) & well_conditioned(case)
+
+
+def backlit(case):
+    """[h,w] bool on the map grid: every light is behind the surface at every repeat (N.L < 0): all map gradients are exactly 0."""
+    t = _terms(case)
+    m = None
+    for x in t["ndl"]:
+        m = (x[0] < 0) if m is None else m & (x[0] < 0)
+    return _fold_all(m, case.tile)
+
+
+def branches(case):
+    """-> dict name -> [H,W] bool on the output grid; 'named' is the branch the case is for, 'complement' the other side,
+    further entries are sub-branches that the case promises too."""
+    t = _terms(case)
+    L = case.n_lights
+    ndv, ndl, ndh, u = t["ndv"][0], [x[0] for x in t["ndl"]], [x[0] for x in t["ndh"]], t["u"]
+    name = case.name
+    if name == "backlit":
+        return dict(named=functools.reduce(torch.logical_and, [x < 0 for x in ndl]), complement=functools.reduce(torch.logical_or, [x > 0 for x in ndl]))
+    if name == "backview":
+        return dict(named=ndv < 0, complement=ndv > 0)
+    if name == "half_clamp":
+        # several lights: a pixel is on the branch as soon as ONE light has N.H < 0 < N.L (each light runs the GGX term by itself),
+        # and on the complementary branch only if no light has, while some light is lit with N.H > 0
+        named = functools.reduce(torch.logical_or, [(h < 0) & (l > 0) for h, l in zip(ndh, ndl)])
+        return dict(named=named, complement=functools.reduce(torch.logical_or, [(h > 0) & (l > 0) for h, l in zip(ndh, ndl)]) & ~named)
+    if name == "saturated":
+        alone = functools.reduce(torch.logical_or, [(x > 1).any(dim=0) for x in u])
+        some_not = functools.reduce(torch.logical_or, [((x < 1).any(dim=0)) for x in u])
+        res = dict(named=alone & some_not, complement=~alone)
+        if L > 1:
+            total = sum(x.clamp(0, 1) for x in u)
+            each_below = functools.reduce(torch.logical_and, [x < 1 for x in u])          # per channel
+            only_sum = ((total > 1) & each_below).any(dim=0)
+            res.update(named=alone | only_sum, complement=~(alone | (total > 1).any(dim=0)), alone=alone, only_in_sum=only_sum)
+        return res
+    if name == "dark":
+        colour = sum(x.clamp(0, 1) for x in u).clamp(0, 1)
+        under = (colour > 0) & (colour < KNEE_ENCODE)
+        return dict(named=under.any(dim=0), complement=(colour > KNEE_ENCODE).all(dim=0))
+    k = case.tile
+    a = _rep(case.albedo, k)
+    if name == "albedo_range":
+        x = torch.cat([a, _rep(case.specular, k)], 0) if case.workflow == "specular" else a
+        ordinary = (x > KNEE_DECODE) & (x < 1)
+        return dict(named=(~ordinary).any(dim=0), complement=ordinary.all(dim=0), below_zero=(x < 0).any(dim=0),
+                    under_knee=((x > 0) & (x < KNEE_DECODE)).any(dim=0), above_one=(x > 1).any(dim=0))
+    if name == "closed_ends":
+        m = _rep(case.metallic, k)[0]
+        ends = ((a == 0) | (a == 1)).any(dim=0) | (m == 0) | (m == 1)
+        return dict(named=ends, complement=~ends, albedo_zero=(a == 0).any(dim=0), albedo_one=(a == 1).any(dim=0),
+                    metallic_zero=m == 0, metallic_one=m == 1)
+    raise KeyError(name)
+
+
+# ------------------------------------------------------------------------------------------------ building blocks
+def _pattern(values, C, h, w, seed, step=(1, 3, 5)):
+    """[C,h,w] of values from a list, by position: a fixed interleave (no random draw), shifted by the seed.  Blocks of
+    2 x 4 texels share a value, so that the lanes of a vector group meet equal and different values."""
+    v = torch.tensor(values, dtype=torch.float64)
+    y = torch.arange(h).view(1, h, 1) // 2
+    x = torch.arange(w).view(1, 1, w) // 4
+    c = torch.arange(C).view(C, 1, 1)
+    idx = (y * step[0] + x * step[1] + c * step[2] + seed) % len(values)
+    return _h(v[idx])
+
+
+def _tilted_normals(h, w, max_x, max_y, case_geom, reverse):
+    """Unit normals tilted about both axes on a grid of angles (degrees): columns sweep the tilt towards +-x over
+    [-max_x, max_x], rows the tilt towards +-y over [-max_y, max_y].  Where a raw dot product with the view, a light or a
+    half vector would be within 0.02 of zero the angle is SKIPPED: the pixel moves on along the grid by 3 degrees until all
+    are clear.  N.L is kept further from zero (|N.L| >= 0.15): a lit pixel at a grazing light is so dim that its colour sits within
+    MARGIN of the contribution's clamp at 0 or of the encode knee.  fp16-exact."""
+    ax = torch.linspace(-max_x, max_x, w, dtype=torch.float64).view(1, w).expand(h, w).clone()
+    ay = torch.linspace(-max_y, max_y, h, dtype=torch.float64).view(h, 1).expand(h, w).clone()
+    if reverse:
+        ax = -ax
+
+    def make(ax, ay):
+        rx, ry = torch.deg2rad(ax), torch.deg2rad(ay)
+        n = torch.stack([torch.sin(rx) * torch.cos(ry), torch.sin(ry), torch.cos(rx) * torch.cos(ry)], 0)
+        return _h(n * 0.75)                           # stored un-normalised on purpose (F.normalize, :154); fp16-exact
+
+    n = make(ax, ay)
+    for step in range(1, 24):
+        dots = case_geom(n).abs()
+        floor = torch.full((dots.shape[0], 1, 1), 0.02, dtype=torch.float64)
+        floor[1::2] = 0.15                               # rows 1, 3, 5 ...: N.L of each light
+        near = (dots < floor).any(dim=0)
+        if not bool(near.any()):
+            break
+        shift = 3.0 * ((step + 1) // 2) * (1 if step % 2 else -1)
+        ax2 = torch.where(near, (ax + shift).clamp(-80, 80), ax)
+        n = torch.where(near.unsqueeze(0), make(ax2, ay), n)
+    return n
+
+
+def _geom_dots(view, lights, light_type, light_size, tile):
+    """-> function(normal [3,h,w]) -> [1 + 2 L, H, W] raw N.V, N.L and N.H on the output grid."""
+    def f(n):
+        n = TF.normalize(_rep(n, tile), dim=0)
+        _, H, W = n.shape
+        v = TF.normalize(view, dim=0).view(3, 1, 1).expand(3, H, W)
+        rows = [(n * v).sum(0)]
+        for l in range(lights.shape[0]):
+            lmap, _ = O._light_geometry(light_type, lights[l], light_size, H, W, torch.float64, 0, H)
+            rows.append((n * lmap).sum(0))
+            rows.append((n * TF.normalize(v + lmap, dim=0)).sum(0))
+        d = torch.stack(rows, 0)
+        if tile != 1:          # a texel must be clear at every repeat
+            k = tile
+            d = d.reshape(d.shape[0], k, H // k, k, W // k)
+            worst = d.abs().amin(dim=(1, 3))
+            return worst
+        return d
+    return f
+
+
+_POINT_DISTANCE = 2.5
+
+
+def _lights(dirs, intens, light_type, distance=_POINT_DISTANCE):
+    """Directions and intensities as given for a directional light; a point light sits `distance` along the same
+    direction, its intensity raised by the squared distance (attenuation :140), so both types light the map alike."""
+    d = torch.tensor(dirs, dtype=torch.float64)
+    i = torch.tensor(intens, dtype=torch.float64)
+    if light_type == "point":
+        return TF.normalize(d, dim=1) * distance, i * distance ** 2
+    return d, i
+
+
+def _weight(H, W, seed):
+    """Upstream gradient of both signs, |w| in [0.25, 1]."""
+    g = torch.Generator().manual_seed(seed)
+    mag = torch.rand(3, H, W, generator=g, dtype=torch.float64) * 0.75 + 0.25
+    sign = torch.where(torch.rand(3, H, W, generator=g) < 0.5, -1.0, 1.0).double()
+    return (mag * sign).float().double()
+
+
+ROUGHNESS_VALUES = (0.4, 0.55, 0.7, 0.85)
+
+
+def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, workflow="metallic", albedo_is_srgb=True,
+          return_srgb=True, quirk=True):
+    """The case `name` on an h x w map (output tile*h x tile*w), one or three lights of one type."""
+    assert name in CASE_NAMES and n_lights in (1, 3)
+    specular_is_srgb = albedo_is_srgb
+    # per case: view, light directions (the first is the case's own), intensities, tilt range, colours
+    behind = [[0.1, -0.2, -1.0], [-0.3, 0.1, -0.9]]                      # lights under the surface: N.L < 0 at every tilt used with them
+    albedo_values, metal_values = (0.4, 0.5, 0.7, 0.85), (0.0, 0.25, 0.5)
+    max_x, max_y = 80.0, 80.0
+    rough_values, point_distance = ROUGHNESS_VALUES, _POINT_DISTANCE
+    if name == "backlit":
+        view, dirs = [0.1, 0.05, 1.0], [[0.9, 0.25, 0.3], [0.8, 0.4, 0.25], [0.95, 0.1, 0.4]]
+        intens = [[4.0, 3.5, 4.5]] * 3
+        max_y = 50.0
+    elif name == "backview":
+        view, dirs = [-0.75, 0.15, 0.6], [[0.15, 0.2, 1.0], [0.3, -0.1, 0.9], [-0.1, 0.3, 0.95]]
+        intens = [[4.0, 3.5, 4.5]] * 3
+        max_y = 50.0
+    elif name == "half_clamp":
+        view, dirs = [-0.99, 0.0, 0.141], [[0.3, 0.0, 0.954], [0.35, 0.1, 0.93], [0.25, -0.1, 0.96]]
+        intens = [[4.0, 3.5, 4.5]] * 3
+        max_y = 40.0
+    elif name == "saturated":
+        view, dirs = [0.1, -0.1, 1.0], [[0.2, 0.1, 1.0], [-0.2, 0.2, 1.0], [0.1, -0.3, 1.0]]
+        intens = [[9.0, 1.2, 2.4], [7.0, 0.6, 0.5], [7.0, 0.5, 0.6]]
+        albedo_values, metal_values = (0.97, 0.5, 0.97, 0.25, 0.5), (0.0, 0.25)
+        max_x = max_y = 35.0
+    elif name == "dark":
+        view, dirs = [0.1, -0.1, 1.0], [[0.2, 0.1, 1.0]] + behind
+        intens = [[0.04, 0.04, 0.04]] * 3
+        metal_values = (0.0,)
+        max_x = max_y = 30.0
+        rough_values = (0.55, 0.7, 0.85)
+        point_distance = 4.0
+    else:      # albedo_range, closed_ends: light and view near +Z and shallow tilts, so that a channel whose albedo decodes to ~0
+        # still shows a specular term well above MARGIN and the encode knee
+        view, dirs = [0.1, -0.1, 1.0], [[0.25, 0.15, 1.0], [-0.3, 0.2, 0.9], [0.1, -0.35, 1.0]]
+        # the converted workflow with the double decode has f0 <= decode(0.04) = 0.003 where the albedo is ~0: it needs more light
+        k = 10.0 if (workflow == "converted" and quirk) else 1.0
+        intens = [[3.0 * k, 2.5 * k, 3.5 * k]] * 3 if n_lights == 1 else [[3.0 * k, 2.5 * k, 3.5 * k], [2.4 * k, 2.0 * k, 2.6 * k], [2.0 * k, 2.2 * k, 1.8 * k]]
+        max_x = max_y = 25.0
+        rough_values = (0.55, 0.7, 0.85)
+    if name == "saturated" and n_lights == 1:
+        intens = [[9.0, 1.2, 2.4]]
+    lights, intensities = _lights(dirs[:n_lights], intens[:n_lights], light_type, point_distance)
+    lights, intensities = lights.float().double(), intensities.float().double()          # fp32-exact: the kernels take them as floats
+    view = torch.tensor(view, dtype=torch.float32).double()
+    light_size = 1.0 if light_type == "point" else None
+    # half_clamp's branch lives at the steepest tilts towards +x: they come FIRST, so that cutting a map's last columns keeps them
+    reverse = (seed % 2 == 1) != (name == "half_clamp")
+    normal = _tilted_normals(h, w, max_x, max_y, _geom_dots(view, lights, light_type, light_size, tile), reverse)
+    rough = _pattern(rough_values, 1, h, w, seed + 1, step=(3, 1, 0))
+    albedo = _pattern(albedo_values, 3, h, w, seed)
+    metallic = _pattern(metal_values, 1, h, w, seed + 2, step=(1, 2, 0)) if workflow != "specular" else None
+    specular = _pattern((0.3, 0.5, 0.97, 0.7), 3, h, w, seed + 3, step=(2, 1, 3)) if workflow == "specular" else None
+    if name in ("albedo_range", "closed_ends"):
+        # texel classes in 2 x 4 blocks: 0 = every channel ordinary (the complementary branch), 1 and 2 = the listed values
+        cls = _pattern((0.0, 1.0, 2.0, 1.0), 1, h, w, seed + 4, step=(1, 1, 0))
+        if name == "albedo_range":
+            ordinary = _pattern((0.06, 0.5, 0.97, 0.3), 3, h, w, seed + 5)
+            listed = _pattern(ALBEDO_VALUES, 3, h, w, seed)
+            albedo = torch.where(cls == 0, ordinary, listed)
+            if workflow == "specular":
+                # class 2: the SPECULAR map takes the listed values under an ordinary albedo (both ~0 in one channel would render ~0 there)
+                albedo = torch.where(cls == 2, _pattern((0.5, 0.97, 0.7), 3, h, w, seed + 6), albedo)
+                specular = torch.where(cls == 2, _pattern(ALBEDO_VALUES, 3, h, w, seed + 1, step=(1, 2, 3)), specular)
+            elif workflow == "converted":
+                metallic = _pattern((0.5, 0.75), 1, h, w, seed + 2, step=(1, 2, 0))
+            else:
+                metallic = _pattern((0.0, 0.25, 0.5, 0.75), 1, h, w, seed + 2, step=(1, 2, 0))
+        else:
+            ends_a = _pattern((0.0, 1.0, 0.5, 1.0, 0.25, 0.0, 0.75), 3, h, w, seed)
+            ends_m = _pattern((0.0, 1.0, 0.5, 0.0, 0.25), 1, h, w, seed + 2, step=(1, 2, 0))
+            albedo = torch.where(cls == 0, _pattern((0.5, 0.25, 0.75), 3, h, w, seed + 5), ends_a)
+            metallic = torch.where(cls == 0, _pattern((0.25, 0.5), 1, h, w, seed + 6), ends_m)
+            # a black metal (albedo 0, metallic 1) renders ~0 in that channel, which is within MARGIN of the contribution's clamp
+            # at 0: metallic 1 goes with albedo 1 / interior values, metallic 0 with every albedo
+            albedo = torch.where((metallic == 1.0) & (albedo == 0.0), torch.ones_like(albedo), albedo)
+    H, W = h * tile, w * tile
+    case = Case(name=name, albedo=albedo, normal=normal, roughness=rough, metallic=metallic, specular=specular, view=view, lights=lights,
+                intensities=intensities, light_type=light_type, light_size=light_size, workflow=workflow, albedo_is_srgb=albedo_is_srgb,
+                specular_is_srgb=specular_is_srgb, return_srgb=return_srgb, quirk=quirk, tile=tile, weight=_weight(H, W, 1000 + seed))
+    if name == "dark":
+        case = _solve_dark(case, seed)
+    return case
+
+
+DARK_TARGETS = (1.4e-3, 1.5e-3, 1.6e-3)          # linear colours inside (MARGIN, knee - MARGIN)
+LIT_TARGETS = (5.2e-3, 5.6e-3, 6.0e-3)           # ... and above knee + MARGIN: the complementary branch
+
+
+def _solve_dark(case, seed):
+    """`dark`: the albedo of every texel is SOLVED for, so that the linear colour of each channel is one of DARK_TARGETS (half of
+    the 2 x 4 blocks) or of LIT_TARGETS (the others).  With metallic = 0 the contribution is (kd base / pi + spec) rad (:169-176),
+    linear in base.  Tiled maps: solved for the mean over the repeats (a point light shades them a little differently)."""
+    h, w = case.albedo.shape[1:]
+    k = case.tile
+    trial = case.replace(albedo=torch.full_like(case.albedo, 0.5), albedo_is_srgb=False)
+    t = _terms(trial)
+    fold = lambda x: x.reshape(x.shape[0], k, h, k, w).mean(dim=(1, 3))
+    kd_pi, spec = t["shade"][0]
+    slope, offset = fold(kd_pi * t["rad"][0]), fold(spec * t["rad"][0])
+    dark = _pattern((1.0, 0.0), 1, h, w, seed, step=(1, 1, 0)) == 1.0
+    target = torch.where(dark, _pattern(DARK_TARGETS, 3, h, w, seed, step=(1, 1, 1)), _pattern(LIT_TARGETS, 3, h, w, seed, step=(1, 1, 1)))
+    base = (target - offset) / slope
+    if case.albedo_is_srgb:      # store the sRGB encoding (functions.py:50-66 inverted)
+        base = torch.where(base <= KNEE_ENCODE, base * 12.92, 1.055 * base.clamp_min(1e-9) ** (1 / 2.4) - 0.055)
+    return case.replace(albedo=_h(base))
+
+
+def fill_undecided(case):
+    """For gradients that are sums over all pixels (view, light, intensity): texels that are not decided take the values of a
+    decided neighbour -- tried in a fixed order of offsets, and taken only when they are decided at the new place too.
+    -> (case, share of texels still undecided)."""
+    cur = case
+    for dy, dx in ((0, 1), (0, -1), (1, 0), (-1, 0), (0, 4), (0, -4), (2, 0), (-2, 0), (2, 4), (-2, -4), (0, 8), (4, 0)):
+        bad = ~decided(cur)
+        if not bool(bad.any()):
+            break
+        maps = [None if t is None else torch.where(bad.unsqueeze(0), torch.roll(t, (dy, dx), (1, 2)), t) for t in cur.maps()]
+        trial = cur.replace(**dict(zip(("albedo", "normal", "roughness", "metallic", "specular"), maps)))
+        take = bad & decided(trial)
+        maps = [None if t is None else torch.where(take.unsqueeze(0), n, t) for t, n in zip(cur.maps(), maps)]
+        cur = cur.replace(**dict(zip(("albedo", "normal", "roughness", "metallic", "specular"), maps)))
+    return cur, float((~decided(cur)).double().mean())
+
+
+def report(case):
+    """One line: branch populations and undecided share (what the host test prints)."""
+    b = branches(case)
+    d = decided(case)
+    parts = ["%s %.1f%%" % (k, 100 * float(v.double().mean())) for k, v in b.items()]
+    return "%-13s %dx%d tile %d %-11s L=%d %-9s | %s | undecided %.2f%% (thresholds %.2f%%, conditioning %.2f%%)" % (
+        case.name, case.albedo.shape[1], case.albedo.shape[2], case.tile, case.light_type, case.n_lights, case.workflow, ", ".join(parts),
+        100 * float((~d).double().mean()), 100 * float((~_fold_all(threshold_decided(case), case.tile)).double().mean()),
+        100 * float((~well_conditioned(case)).double().mean()))
