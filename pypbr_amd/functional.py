@@ -27,6 +27,7 @@ from typing import Optional, Sequence, Tuple, Union
 import torch
 
 from . import _native as N
+from ._caches import CACHING, KeptPlan, VersionMemo, host_values, set_caching, version_of  # noqa: F401  (the settings are re-exported)
 
 TensorLike = Union[torch.Tensor, Sequence[float]]
 
@@ -38,41 +39,8 @@ def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-# ------------------------------------------------------------------ caches keyed on tensor identity + version counter
-# Three caches save repeated work on tensors that did not change between calls: the device copy of a CPU-resident material
-# (models.CookTorranceBRDF), the host copy of device-resident light / view tensors (below) and the "already signed?" verdict
-# of a normal map (materials).  They recognise "did not change" by object identity and `tensor._version` -- which is NOT
-# bumped by `t.data.add_()`, by edits of a numpy array that shares the tensor's memory (`torch.from_numpy(a).float()` shares
-# it for float32 arrays, and materials ingest arrays exactly so, as upstream does), or by kernels that write through raw
-# pointers (`out=`).  The reference re-reads its maps and parameters on every call, so all three are OFF by default and
-# opt-in: `set_caching(device_maps=True, parameters=True, decode_verdicts=True)`, or PBR_CACHE=maps,params,decode in the
-# environment, for loops that are known not to edit their tensors behind autograd's back.  Inference tensors
-# (torch.inference_mode) have no version counter at all and are never cached.
-CACHING = {"device_maps": False, "parameters": False, "decode_verdicts": False}
-for _tok, _key in (("maps", "device_maps"), ("params", "parameters"), ("decode", "decode_verdicts")):
-    if _tok in os.environ.get("PBR_CACHE", "").split(","):
-        CACHING[_key] = True
-
-
-def set_caching(device_maps: Optional[bool] = None, parameters: Optional[bool] = None, decode_verdicts: Optional[bool] = None) -> dict:
-    """Switches the identity + version keyed caches (see above) on or off; returns the previous settings."""
-    old = dict(CACHING)
-    for key, v in (("device_maps", device_maps), ("parameters", parameters), ("decode_verdicts", decode_verdicts)):
-        if v is not None:
-            CACHING[key] = bool(v)
-    return old
-
-
-def version_of(t: torch.Tensor):
-    """`t._version`, or None for tensors that do not track one (created under torch.inference_mode): those are not cached."""
-    try:
-        return None if t.is_inference() else t._version
-    except RuntimeError:
-        return None
-
-
-_HOST_COPIES = {}          # id(tensor) -> (weakref to it, its version, host copy) for device-resident parameter tensors
-_HOST_COPIES_MAX = 64
+# The caches' settings live in _caches (what they recognise as "did not change", and why all three are off by default, is said there).
+_HOST_COPIES = VersionMemo()          # host copies of device-resident parameter tensors
 
 
 def _host_vec3(v: TensorLike, rows: Optional[int] = None):
@@ -87,17 +55,11 @@ def _host_vec3(v: TensorLike, rows: Optional[int] = None):
         t = torch.as_tensor(v, dtype=torch.float32)
     elif v.is_cuda:
         ver = version_of(v) if CACHING["parameters"] else None
-        hit = _HOST_COPIES.get(id(v)) if ver is not None else None
-        if hit is not None and hit[0]() is v and hit[1] == ver:
-            t = hit[2]
-        else:
+        t = _HOST_COPIES.get(v, ver) if ver is not None else None
+        if t is None:
             t = v.detach().to("cpu", torch.float32)
             if ver is not None:
-                for k in [k for k, e in _HOST_COPIES.items() if e[0]() is None]:
-                    del _HOST_COPIES[k]
-                if len(_HOST_COPIES) >= _HOST_COPIES_MAX:
-                    _HOST_COPIES.clear()
-                _HOST_COPIES[id(v)] = (weakref.ref(v), ver, t)
+                _HOST_COPIES.put(v, ver, t)
     else:
         t = v.detach().to(torch.float32)
     if rows is None:
@@ -280,6 +242,7 @@ class RenderPlan:
     def __init__(self, desc, out, keep_alive, squeeze):
         self.desc, self.out, self._keep, self._squeeze = desc, out, keep_alive, squeeze
         self.device = out.device
+        self._second_given = keep_alive[3] is not None or keep_alive[4] is not None    # a metallic or specular map (a kept plan empties _keep)
         self._fn = N.lib().pbr_cook_torrance
         self._ref = ctypes.byref(desc)
         self._param_tensors = (None, None, None)            # device-resident view / lights / intensities (prepare_device_parameters)
@@ -338,6 +301,14 @@ class RenderPlan:
         self.desc.device_params = self._param_block.data_ptr()
         self._param_stream = st                             # launches on another stream fold the parameters again there (launch)
 
+    def refill(self, view_dir, light, light_intensity) -> bool:
+        """refill_parameters on this plan's descriptor; False, and nothing written, when the values do not fit it (another number of lights)."""
+        try:
+            refill_parameters(self.desc, view_dir, light, light_intensity)
+        except ValueError:
+            return False
+        return True
+
     def attach_blend(self, blend_desc, workspace, keep_alive):
         """Turns the plan into blend + evaluate (pbr_cook_torrance_blend): material 2 and the mask."""
         self._blend, self._blend_ref, self._workspace = blend_desc, ctypes.byref(blend_desc), workspace
@@ -362,7 +333,7 @@ class RenderPlan:
 
     def launch(self, stream: Optional[int] = None) -> torch.Tensor:
         """Enqueue on `stream` (raw hipStream_t) or torch's current stream of the maps' device."""
-        if self.out.numel() == 0 and (self._keep[3] is not None or self._keep[4] is not None):
+        if self.out.numel() == 0 and self._second_given:
             return self.result         # zero-sized maps: the reference's whole-map ops return an empty (3, H, W) image; nothing to enqueue
         st = _stream_ptr(self.device) if stream is None else stream
         if self._param_stream is not None and st != self._param_stream:
@@ -843,31 +814,22 @@ class _MseStepFn(torch.autograd.Function):
 
     @staticmethod
     def _kept_plan(maps, kwargs):
-        params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
-        vals = []
-        for v in params:
-            if isinstance(v, torch.Tensor):
-                if v.is_cuda or v.requires_grad:
-                    return None, None, None                 # parameters on the device / with gradients: the general path every time
-                vals.append(v.tolist())
-            elif isinstance(v, (list, tuple)):
-                vals.append([list(r) if isinstance(r, (list, tuple)) else r for r in v])
-            else:
-                return None, None, None
+        vals = tuple(host_values(kwargs.get(k)) for k in _PARAM_KEYS)
         rest = tuple(sorted((k, v if not isinstance(v, list) else tuple(v)) for k, v in kwargs.items() if k not in _PARAM_KEYS))
         try:
             hash(rest)
         except TypeError:
             return None, None, None
-        for t in maps:
-            if t is not None and (t.stride(-1) != 1 or t.stride(-2) != t.shape[-1]):
-                return None, None, None                     # strided rows are evaluated through a copy (_as_batched): nothing to keep
+        # parameters on the device / with gradients: the general path every time; strided rows are evaluated through a copy (_as_batched):
+        # nothing to keep
+        if None in vals or any(t is not None and (t.stride(-1) != 1 or t.stride(-2) != t.shape[-1]) for t in maps):
+            return None, None, None
         key = (tuple(None if t is None else (id(t), t.data_ptr(), tuple(t.shape), t.dtype) for t in maps), rest)
         hit = _MseStepFn._PLANS.get(key)
         if hit is not None:
-            if all((r is None and t is None) or (r is not None and r() is t) for r, t in zip(hit[1], maps)):
+            if hit.describes(maps):
                 _MseStepFn._PLANS.move_to_end(key)
-                return hit, key, vals                       # [plan, weak maps, parameter values, the entry's lock]: refilled by the caller under that lock
+                return hit, key, vals                       # a KeptPlan: refreshed by the caller under the entry's lock
             del _MseStepFn._PLANS[key]
         return None, key, vals
 
@@ -878,23 +840,18 @@ class _MseStepFn(torch.autograd.Function):
         # and the launch run outside it, under the ENTRY's own lock -- threads that drive different materials / GPUs do not serialise.
         with _MseStepFn._LOCK:
             hit, key, vals = _MseStepFn._kept_plan(maps, kwargs)
-        plan = entry_lock = None
-        if hit is not None:
-            if hit[3].acquire(False):
-                entry_lock, plan = hit[3], hit[0]
-            else:                                           # another thread is launching through this very plan: build a private one, keep nothing
-                key = None
-        kept = plan is not None
+        plan = None
+        if hit is not None and not hit.try_acquire():       # another thread is launching through this very plan: build a private one, keep nothing
+            hit = key = None
         try:
-            if kept and hit[2] != vals:                     # light / view VALUES are re-read every call
-                try:
-                    refill_parameters(plan.desc, *vals)
-                    hit[2] = vals
-                except ValueError:                          # another number of lights: another kernel, another plan
+            if hit is not None:
+                if hit.refresh(vals):                       # light / view VALUES are re-read every call
+                    plan = hit.plan
+                else:                                       # another number of lights: another kernel, another plan
                     with _MseStepFn._LOCK:
                         if _MseStepFn._PLANS.get(key) is hit:
                             del _MseStepFn._PLANS[key]
-                    plan, kept = None, False
+            kept = plan is not None
             if plan is None:
                 plan = plan_cook_torrance(*[None if t is None else t.detach() for t in maps], **kwargs)
                 plan.out = None                                 # the colour is never written
@@ -908,16 +865,15 @@ class _MseStepFn(torch.autograd.Function):
                     with _MseStepFn._LOCK:
                         _MseStepFn._PLANS.pop(key, None)
                 raise
-            if (not kept and key is not None and plan._param_block is None
-                    and all(p is None or p.data_ptr() == t.data_ptr() for p, t in zip(plan._keep, maps))):
-                plan._keep = ()                                 # the cache holds the maps weakly (their owner keeps them alive while it wants the plan)
+            entry = KeptPlan.adopt(plan, maps, vals) if not kept and key is not None else None
+            if entry is not None:
                 with _MseStepFn._LOCK:                          # cached only AFTER a launch that was served
-                    _MseStepFn._PLANS[key] = [plan, tuple(None if t is None else weakref.ref(t) for t in maps), vals, threading.Lock()]
+                    _MseStepFn._PLANS[key] = entry
                     while len(_MseStepFn._PLANS) > _MseStepFn._PLANS_MAX:
                         _MseStepFn._PLANS.popitem(last=False)
         finally:
-            if entry_lock is not None:
-                entry_lock.release()
+            if hit is not None:
+                hit.release()
         # the plan (descriptor + strong references to every map) is NOT kept: a second backward rebuilds it from the saved tensors
         ctx.kwargs, ctx.wanted, ctx.grads = kwargs, wanted, bufs
         ctx.present = [t is not None for t in maps]

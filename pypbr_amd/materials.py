@@ -35,7 +35,6 @@ Differences from the reference, all supersets:
 """
 import copy
 import enum
-import weakref
 from typing import Optional, Tuple
 
 import numpy as np
@@ -43,6 +42,7 @@ import torch
 
 from . import _native
 from . import functional as F_
+from ._caches import VersionMemo
 
 
 class NormalConvention(enum.Enum):
@@ -159,28 +159,26 @@ def _compute_device(home) -> torch.device:
 # that flag once, and from then on a signed map is handed back as it is -- no kernel, no copy, the reference's object
 # identity -- while an encoded map is decoded afresh.  Off by default: the version counter does not see every edit
 # (functional.CACHING), and the reference looks at the values every time.
-_DECODE_VERDICTS = {}          # id(tensor) -> [weakref, version, device flag, host verdict or None]
-_DECODE_VERDICTS_MAX = 64
+_DECODE_VERDICTS = VersionMemo()          # payload: [device flag, host verdict or None]
 
 
 def _decode_remembering(t: torch.Tensor) -> torch.Tensor:
     ver = F_.version_of(t) if F_.CACHING["decode_verdicts"] else None
     if ver is None:                 # the default (functional.set_caching): decide afresh, on the device, every assignment
         return F_.decode_normal(t)
-    hit = _DECODE_VERDICTS.get(id(t))
-    if hit is not None and hit[0]() is t and hit[1] == ver:
-        if hit[3] is None:
-            hit[3] = bool(hit[2].item())       # the decode that wrote it ran an assignment ago: no wait in practice
-        if hit[3]:
+    hit = _DECODE_VERDICTS.get(t, ver)
+    if hit is not None:
+        if hit[1] is None:
+            hit[1] = bool(hit[0].item())       # the decode that wrote it ran an assignment ago: no wait in practice
+        if hit[1]:
             return t
         return F_.decode_normal(t)
     out, flag = F_._decode_normal_raw(t)
-    for k in [k for k, e in _DECODE_VERDICTS.items() if e[0]() is None]:
-        del _DECODE_VERDICTS[k]
-    if len(_DECODE_VERDICTS) >= _DECODE_VERDICTS_MAX:
-        _DECODE_VERDICTS.clear()
-    _DECODE_VERDICTS[id(t)] = [weakref.ref(t), ver, flag, None]
+    _DECODE_VERDICTS.put(t, ver, [flag, None])
     return out
+
+
+_CALL_CACHES = ("_device_cache", "_plan_cache", "_plan_seen")     # what CookTorranceBRDF keeps in a material's __dict__ between calls
 
 
 class MaterialBase:
@@ -542,7 +540,12 @@ class MaterialBase:
 
     def drop_device_cache(self):
         """Frees the device copy CookTorranceBRDF keeps of a CPU-resident material between calls."""
-        self.__dict__.pop("_device_cache", None)
+        return self._drop_call_caches(("_device_cache",))
+
+    def _drop_call_caches(self, keys=_CALL_CACHES):
+        """Forgets what CookTorranceBRDF keeps on a material between calls: it describes the tensors of the material it was made for."""
+        for k in keys:
+            self.__dict__.pop(k, None)
         return self
 
     def _convert_in_place(self, name, flag, fn):
@@ -758,9 +761,7 @@ class MaterialBase:
     def _shallow(self):
         """A material over the SAME tensors with a map dict of its own (what a fused transforms.Compose run starts from: every map is
         about to be replaced, so nothing is cloned)."""
-        new = copy.copy(self)
-        for k in ("_device_cache", "_plan_cache", "_plan_seen"):
-            new.__dict__.pop(k, None)
+        new = copy.copy(self)._drop_call_caches()
         new.__dict__["_store"] = dict(self._raw)
         return new
 
@@ -770,10 +771,7 @@ class MaterialBase:
         self._samples_on_host()
         if self.__dict__.get("_raw_normal"):
             self._bring_home_normal()
-        new = copy.copy(self)
-        new.__dict__.pop("_device_cache", None)
-        new.__dict__.pop("_plan_cache", None)
-        new.__dict__.pop("_plan_seen", None)
+        new = copy.copy(self)._drop_call_caches()
         new.__dict__["_lazy_blend"] = None
         object.__setattr__(new, "_maps", {k: (None if v is None else v.clone()) for k, v in self._raw.items()})
         return new

@@ -7,7 +7,6 @@ replaced by a single call into libpbr_hip.so (pypbr_amd.functional.cook_torrance
 """
 import collections
 import os
-import threading
 import weakref
 from abc import ABC
 from typing import Optional
@@ -18,6 +17,7 @@ from torch import Tensor
 
 from . import _native
 from . import functional as F_
+from ._caches import KeptPlan, host_values, same_tensors, weak_refs
 from .materials import MaterialBase, _normalised
 
 
@@ -98,16 +98,13 @@ class CookTorranceBRDF(BRDFModel):
         versions = tuple(None if t is None else F_.version_of(t) for t in tensors)
         wanted = (F_.CACHING["device_maps"] or material.__dict__.get("_cache_on_device", False))
         cacheable = wanted and all(v is not None for t, v in zip(tensors, versions) if t is not None)
-        hit = material.__dict__.get("_device_cache") if cacheable else None
-        if (hit is not None and hit[0] == compute and hit[1] == versions and len(hit[2]) == len(tensors)
-                and all((r is None and t is None) or (r is not None and r() is t) for r, t in zip(hit[2], tensors))):
-            moved = hit[3]
+        at, seen, refs, moved = (material.__dict__.get("_device_cache") if cacheable else None) or (None, None, (), None)
+        if moved is not None and at == compute and seen == versions and same_tensors(refs, tensors):
             _touch_device_cache(material)
         else:
             moved = _upload_together(tensors, compute)
             if cacheable:
-                refs = tuple(None if t is None else weakref.ref(t) for t in tensors)
-                material.__dict__["_device_cache"] = (compute, versions, refs, moved)
+                material.__dict__["_device_cache"] = (compute, versions, weak_refs(tensors), moved)
                 _register_device_cache(material, sum(t.numel() * t.element_size() for t in moved if t is not None))
         return moved[:5], (None if blend is None else moved[5:])
 
@@ -120,31 +117,21 @@ class CookTorranceBRDF(BRDFModel):
     # CPU-resident or pending maps, a lazy blend, another thread using the plan) takes the general path below.
     PLAN_REUSE = True
 
-    @staticmethod
-    def _host_values(v):
-        if isinstance(v, torch.Tensor):
-            if v.is_cuda or v.requires_grad:
-                return None
-            return v.tolist()
-        if isinstance(v, (list, tuple)):                      # a copy: the caller may edit its list in place between calls
-            return [list(r) if isinstance(r, (list, tuple)) else r for r in v]
-        return None
-
     def _reuse_plan(self, material, view_dir, light, intensity, light_size, return_srgb):
         d = material.__dict__
         store = d.get("_store")
         if store is None or d.get("_lazy_blend") is not None or d.get("_raw_normal") or self.override_device is not None:
             return None
-        vals = (self._host_values(view_dir), self._host_values(light), self._host_values(intensity))
+        vals = (host_values(view_dir), host_values(light), host_values(intensity))
         if vals[0] is None or vals[1] is None or vals[2] is None:
             return None
         albedo, normal, rough = store.get("albedo"), store.get("normal", False), store.get("roughness")
-        second = store.get("metallic")
-        if second is None:
-            second = store.get("specular")
-        if albedo is None or normal is False or rough is None or second is None or not albedo.is_cuda or albedo.device != material.device:
+        metallic = store.get("metallic")
+        specular = store.get("specular") if metallic is None else None
+        if (albedo is None or normal is False or rough is None or (metallic is None and specular is None) or not albedo.is_cuda
+                or albedo.device != material.device):
             return None
-        maps = (albedo, normal, rough, second)
+        maps = (albedo, normal, rough, metallic, specular)     # the plan's own order (KeptPlan.adopt)
         grad = torch.is_grad_enabled()
         for t in maps:
             # rows must be dense: a map with strided rows is evaluated through a contiguous COPY (functional._as_batched), and a kept plan
@@ -153,31 +140,27 @@ class CookTorranceBRDF(BRDFModel):
                                   or t.stride(-1) != 1 or t.stride(-2) != t.shape[-1]):
                 return None
         key = (self.light_type, light_size, bool(return_srgb), bool(material.albedo_is_srgb), bool(getattr(material, "specular_is_srgb", True)),
-               d.get("_lazy_tile", (1, 1)), "metallic" in store and store["metallic"] is not None,
+               d.get("_lazy_tile", (1, 1)),
                tuple((id(t), t.data_ptr(), t.shape, t.dtype, t.stride()) if t is not None else None for t in maps))
-        hit = d.get("_plan_cache")
-        if hit is not None and (hit[0] != key or not all((r is None and t is None) or (r is not None and r() is t) for r, t in zip(hit[5], maps))):
+        kept_key, kept = d.get("_plan_cache") or (None, None)
+        if kept is not None and (kept_key != key or not kept.describes(maps)):
             # the store moved on (resize, an assignment, to(), a conversion): the kept descriptor describes maps that are no longer the
             # material's.  It holds them only weakly, so nothing was pinned; drop it now rather than at the next refill.
             d.pop("_plan_cache", None)
-            hit = None
-        if hit is None:
+            kept = None
+        if kept is None:
             if d.get("_plan_seen") != key:                    # first sighting of this call: a material whose maps are new tensors every step
                 d["_plan_seen"] = key                         # (a training loop) never pays for a plan it would not use twice
                 return None
             return key
-        if not hit[3].acquire(False):                         # another thread is launching through this plan right now
+        if not kept.try_acquire():                            # another thread is launching through this plan right now
             return None
-        plan = hit[1]
+        plan = kept.plan
         try:
-            last = hit[2]
-            if last != vals:
-                if len(F_._host_vec3(vals[1], rows=-1)) != plan.desc.n_lights:
-                    return key                                # another number of lights: another kernel, another plan
-                F_.refill_parameters(plan.desc, *vals)
-                hit[2] = vals
+            if not kept.refresh(vals):
+                return key                                    # another number of lights: another kernel, another plan
             dev = plan.device
-            out = torch.empty(hit[4], dtype=torch.float32, device=dev)
+            out = torch.empty(kept.out_shape, dtype=torch.float32, device=dev)
             plan.out = out                                    # for the duration of the launch only: the plan keeps no result alive
             plan.desc.out = out.data_ptr()
             if torch.cuda.current_device() == dev.index:
@@ -188,7 +171,7 @@ class CookTorranceBRDF(BRDFModel):
             return out[0] if plan._squeeze else out
         finally:
             plan.out = None
-            hit[3].release()
+            kept.release()
 
     def forward(self, material, view_dir: Tensor, light_dir_or_position: Tensor, light_intensity: Tensor,
                 light_size: Optional[float] = None, return_srgb: bool = True) -> Tensor:
@@ -267,31 +250,20 @@ class CookTorranceBRDF(BRDFModel):
         maps = (albedo, normal, roughness, metallic, specular)
         if any(t is not None and t.device != compute for t in maps + (blend or ())):
             maps, blend = self._staged(material, maps, blend, compute)
+        kw = dict(view_dir=view_dir, light=light_dir_or_position, light_intensity=light_intensity, light_type=self.light_type,
+                  light_size=light_size, albedo_is_srgb=bool(material.albedo_is_srgb), specular_is_srgb=specular_is_srgb,
+                  return_srgb=return_srgb, tile=getattr(material, "lazy_tile", (1, 1)))
         if reuse_key is not None and blend is None and albedo.numel() > 0:
-            plan = F_.plan_cook_torrance(*maps, view_dir=view_dir, light=light_dir_or_position, light_intensity=light_intensity,
-                                         light_type=self.light_type, light_size=light_size, albedo_is_srgb=bool(material.albedo_is_srgb),
-                                         specular_is_srgb=specular_is_srgb, return_srgb=return_srgb, tile=getattr(material, "lazy_tile", (1, 1)))
+            plan = F_.plan_cook_torrance(*maps, **kw)
             with torch.cuda.device(plan.device):
                 color = plan.launch()
-            four = (maps[0], maps[1], maps[2], maps[3] if maps[3] is not None else maps[4])       # _reuse_plan's order
-            held = tuple(t for t in four if t is not None)
-            if plan._param_block is None and all(p is None or any(p.data_ptr() == t.data_ptr() for t in held) for p in plan._keep):
-                # the plan points INTO the material's own tensors (no staging copy): the material keeps them alive for as long as it wants
-                # this plan, so the plan holds them weakly -- a resize() / to() / assignment that replaces the store frees the old maps at
-                # once instead of leaving e.g. 537 MB of 4K maps pinned behind a descriptor nobody will launch again
-                plan._keep = ()
-                material.__dict__["_plan_cache"] = [reuse_key, plan, (self._host_values(view_dir), self._host_values(light_dir_or_position),
-                                                                     self._host_values(light_intensity)), threading.Lock(), tuple(plan.out.shape),
-                                                    tuple(None if t is None else weakref.ref(t) for t in four)]
+            kept = KeptPlan.adopt(plan, maps, (host_values(view_dir), host_values(light_dir_or_position), host_values(light_intensity)),
+                                  tuple(plan.out.shape))
+            if kept is not None:
+                material.__dict__["_plan_cache"] = (reuse_key, kept)
             plan.out = None                                   # the result belongs to the caller; later calls bring their own
             return color
-        color = F_.cook_torrance(
-            *maps,
-            view_dir=view_dir, light=light_dir_or_position, light_intensity=light_intensity,
-            light_type=self.light_type, light_size=light_size,
-            albedo_is_srgb=bool(material.albedo_is_srgb), specular_is_srgb=specular_is_srgb,
-            return_srgb=return_srgb, tile=getattr(material, "lazy_tile", (1, 1)),
-            blend=blend)
+        color = F_.cook_torrance(*maps, blend=blend, **kw)
         if color.device == out_device:
             return color
         return F_.to_host(color, out_device) if out_device.type == "cpu" else color.to(out_device)

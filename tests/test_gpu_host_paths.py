@@ -181,8 +181,9 @@ def test_device_resident_light_tensors_sync_once():
     try:
         assert F._host_vec3(light) == pytest.approx([0.1, 0.1, 1.0])
         assert len(F._HOST_COPIES) == 1
-        hit = F._HOST_COPIES[id(light)][2]
-        assert F._host_vec3(light) == pytest.approx([0.1, 0.1, 1.0]) and F._HOST_COPIES[id(light)][2] is hit
+        hit = F._HOST_COPIES.get(light, F.version_of(light))
+        assert hit is not None
+        assert F._host_vec3(light) == pytest.approx([0.1, 0.1, 1.0]) and F._HOST_COPIES.get(light, F.version_of(light)) is hit
         light.mul_(2.0)                                                   # in-place change: read again
         assert F._host_vec3(light) == pytest.approx([0.2, 0.2, 2.0])
         other = torch.tensor([0.5, 0.5, 0.5], device="cuda")

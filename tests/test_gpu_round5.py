@@ -324,7 +324,7 @@ def test_plan_reuse_is_invisible_except_for_its_speed():
             CookTorranceBRDF.PLAN_REUSE = True
     want = reference()
     outs = [brdf(mat, view, light, inten, 1.0) for _ in range(4)]           # 1st: seen, 2nd: plan built, 3rd and 4th: reused
-    assert "_plan_cache" in mat.__dict__ and mat.__dict__["_plan_cache"][1].out is None
+    assert "_plan_cache" in mat.__dict__ and mat.__dict__["_plan_cache"][1].plan.out is None
     assert all(torch.equal(o, want) for o in outs) and len({o.data_ptr() for o in outs}) == 4
     light[0] = -0.3                                                             # a CPU tensor edited in place
     assert torch.equal(brdf(mat, view, light, inten, 1.0), reference())
