@@ -435,6 +435,43 @@ int pbr_remap_planes_backward(const void *grad_out, int64_t grad_out_batch_strid
                               int32_t x_step, uint32_t negate_mask, void *stream);
 
 /*
+ * MaterialBase.rotate, base.py:539-603 -- pad, torchvision's nearest-neighbour rotate(expand=True), centre crop and, for the normal map,
+ * utils.rotate_normals -- as ONE index function per output pixel.  The host computes the constants below from
+ * (h, w, angle, expand, padding_mode); per output pixel (i, j) the kernel evaluates, in fp32 and in this rounding order,
+ *     x = j + x0, y = i + y0 (exact);  gx = rn(rn(x t00) + rn(y t10)), gy = rn(rn(x t01) + rn(y t11))   (no fused multiply-add);
+ *     fx = ((gx + 1) Wp - 1) / 2, fy = ((gy + 1) Hp - 1) / 2 (each step rounded);  ix = rint(fx), iy = rint(fy) (halves to even)
+ * with Hp x Wp = (h + 2 pad) x (w + 2 pad).  Outside [0, Wp) x [0, Hp) the pixel is 0; otherwise `pad` is subtracted and the pixel is 0
+ * outside the h x w map (constant padding) or wraps once into it (circular; pad <= h, w).
+ */
+typedef struct pbr_rotate_geom {
+    int32_t pad;                  /* ceil(sqrt(H^2 + W^2)) - H, on all four sides of the h x w map */
+    int32_t circular;             /* 0: constant (zero) padding, 1: circular */
+    float x0, y0;                 /* left - ow / 2 + 0.5, top - oh / 2 + 0.5: the centre crop inside torchvision's expanded ow x oh image */
+    float t00, t10, t01, t11;     /* the inverse matrix cast to fp32 and divided in fp32 by (0.5 Wp, 0.5 Hp): x row t00 t10, y row t01 t11 */
+    float cos_r, sin_r;           /* cos and sin of radians(-angle) in fp32 (the backward maps texel centres to output coordinates) */
+} pbr_rotate_geom;
+/* src [batch][planes][h_src][w_src] -> dst [batch][planes][h_out][w_out]; rows dense, batch and plane strides in ELEMENTS as for
+ * pbr_remap_planes; planes <= 32.  Values are copied bit for bit (`dtype` PBR_F32 | PBR_F16), except, when normal_first_plane >= 0,
+ * planes normal_first_plane .. + 2 of every pixel: they are a normal map's (x, y, z) and pass through pbr_normal_transform's arithmetic
+ * with M = [[m00, m01], [m10, m11]], renormalised (a filled pixel stays 0).  normal_first_plane = -1: no normal map in the block.
+ * `dst` must not overlap `src`.  A bad shape, stride, plane index or geometry (a circular pad beyond the map) returns PBR_ERR_SHAPE
+ * before anything is launched.  No workspace.  (ABI 9: entry points added, nothing changed.) */
+int pbr_rotate_planes(const void *src, int64_t src_batch_stride, int64_t src_plane_stride, void *dst, int64_t dst_batch_stride,
+                      int64_t dst_plane_stride, int32_t batch, int32_t planes, int32_t h_src, int32_t w_src, int32_t h_out, int32_t w_out,
+                      const pbr_rotate_geom *geom, int32_t normal_first_plane, float m00, float m01, float m10, float m11, int dtype,
+                      void *stream);
+/* Gradient of pbr_rotate_planes w.r.t. `src`, fp32, as a GATHER over source texels: every place of the texel in the padded image (one;
+ * up to three per axis in circular mode) is mapped to output coordinates, and the 3 x 3 output pixels around it that the FORWARD's index
+ * function sends to that place are summed in a fixed order (places ascending, then output row, then column).  The normal triple's three
+ * sums then pass ONCE through pbr_normal_transform_backward's arithmetic at the texel's own normal, read from `src` (the forward's
+ * input; may be NULL when normal_first_plane is -1).  No atomics, no workspace; every element of grad_src is written. */
+int pbr_rotate_planes_backward(const void *grad_out, int64_t grad_out_batch_stride, int64_t grad_out_plane_stride, void *grad_src,
+                               int64_t grad_src_batch_stride, int64_t grad_src_plane_stride, const void *src, int64_t src_batch_stride,
+                               int64_t src_plane_stride, int32_t batch, int32_t planes, int32_t h_src, int32_t w_src, int32_t h_out,
+                               int32_t w_out, const pbr_rotate_geom *geom, int32_t normal_first_plane, float m00, float m01, float m10,
+                               float m11, void *stream);
+
+/*
  * Packed material tensors: MaterialBase.from_tensor (base.py:416-487), as_tensor (:319-414) and normal_rgb (:279-291) as ONE launch over
  * a table of at most PBR_MAX_PLANE_OPS plane operations, each over [batch] images of `pixels` elements per plane (strides in ELEMENTS):
  *   PBR_PLANE_AFFINE     one plane:  dst = src * scale + bias.  (1, 0) copies; (0.5, 0.5) is from_tensor's is_normalized, (2, -1) as_tensor's

@@ -85,6 +85,30 @@ class VersionMemo:
         self._entries.clear()
 
 
+class ValueMemo:
+    """key (hashable host values) -> payload, for host-side plans that depend on nothing but their arguments (functional.rotate_plan: the
+    constants of one rotation).  Nothing to invalidate; at `limit` entries everything is forgotten."""
+
+    def __init__(self, limit: int = 256):
+        self.limit, self._entries = limit, {}
+
+    def get(self, key, make):
+        """The payload of `key`, made by `make()` on a miss (an exception from `make` is the caller's and caches nothing)."""
+        hit = self._entries.get(key)
+        if hit is None:
+            hit = make()
+            if len(self._entries) >= self.limit:
+                self._entries.clear()
+            self._entries[key] = hit
+        return hit
+
+    def __len__(self):
+        return len(self._entries)
+
+    def clear(self):
+        self._entries.clear()
+
+
 class KeptPlan:
     """A functional.RenderPlan kept between calls: pointers, never values of maps.  `maps` are held weakly, `values` are the host_values the
     descriptor was last filled from, `lock` serialises refill + launch through this one descriptor (taken non-blocking: a busy entry is

@@ -45,6 +45,7 @@ EXPORTS = (
     "pbr_normal_from_height", "pbr_normal_from_height_backward", "pbr_normal_transform", "pbr_normal_transform_backward",
     "pbr_remap_planes", "pbr_remap_planes_backward",
     "pbr_plane_ops", "pbr_plane_ops_backward",
+    "pbr_rotate_planes", "pbr_rotate_planes_backward",
 )
 
 
@@ -110,6 +111,13 @@ class PlaneOp(ctypes.Structure):
                 ("dst", ctypes.c_void_p), ("dst_batch_stride", ctypes.c_int64), ("dst_plane_stride", ctypes.c_int64),
                 ("input", ctypes.c_void_p), ("input_batch_stride", ctypes.c_int64), ("input_plane_stride", ctypes.c_int64),
                 ("scale", ctypes.c_float), ("bias", ctypes.c_float)]
+
+
+class RotateGeom(ctypes.Structure):
+    """pbr_rotate_geom: the host-computed constants of one rotation (functional.rotate_plan)."""
+    _fields_ = [("pad", ctypes.c_int32), ("circular", ctypes.c_int32), ("x0", ctypes.c_float), ("y0", ctypes.c_float),
+                ("t00", ctypes.c_float), ("t10", ctypes.c_float), ("t01", ctypes.c_float), ("t11", ctypes.c_float),
+                ("cos_r", ctypes.c_float), ("sin_r", ctypes.c_float)]
 
 
 SCHEDULE_AUTO, SCHEDULE_LINEAR = 0, 1
@@ -214,6 +222,10 @@ def lib():
     L.pbr_remap_planes.restype = L.pbr_remap_planes_backward.restype = ctypes.c_int
     L.pbr_plane_ops.argtypes = L.pbr_plane_ops_backward.argtypes = [ctypes.POINTER(PlaneOp), i32, i32, i64, ctypes.c_int, vp]
     L.pbr_plane_ops.restype = L.pbr_plane_ops_backward.restype = ctypes.c_int
+    geom = ctypes.POINTER(RotateGeom)
+    L.pbr_rotate_planes.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, geom, i32, f32, f32, f32, f32, ctypes.c_int, vp]
+    L.pbr_rotate_planes_backward.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, geom, i32, f32, f32, f32, f32, vp]
+    L.pbr_rotate_planes.restype = L.pbr_rotate_planes_backward.restype = ctypes.c_int
     for name in ("pbr_srgb_to_linear", "pbr_linear_to_srgb", "pbr_metallic_to_specular",
                  "pbr_specular_to_metallic", "pbr_decode_normal", "pbr_abi_version", "pbr_set_tuning",
                  "pbr_bytes_per_pixel"):

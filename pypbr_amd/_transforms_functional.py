@@ -2,8 +2,8 @@
 
 Each takes a material and returns a NEW one, leaving its argument untouched: the argument is cloned and the clone's in-place method runs
 (kernels of libpbr_hip.so on a ROCm device).  The random forms draw from Python's `random.random()` in upstream's order and with upstream's
-arithmetic (functional.py:87-88, :151-152, :273, :290), so after `random.seed(k)` they make upstream's choices.  The rotate family is absent
-(upstream implements it with torchvision, which has no stand-in here): INTEGRATION.md.
+arithmetic (functional.py:87-88, :151-152, :273, :290), so after `random.seed(k)` they make upstream's choices.  The rotate family is not
+among them (it is built apart from this module and not re-exported here): INTEGRATION.md.
 """
 from random import random
 from typing import Tuple

@@ -11,9 +11,10 @@ resolve to the MI355X implementation.  The Cook-Torrance path and the calls eith
 `adjust_normal_strength`, `invert_normal` resolve through the aliases above.  The geometric transforms exist too: the material
 methods `crop` (in-bounds), `flip_horizontal`, `flip_vertical`, `roll`, and `pypbr.transforms` with upstream's classes and functional
 forms, `Compose` running a chain of geometric stages as one kernel launch.  So do the packed-tensor methods `MaterialBase.from_tensor`,
-`as_tensor` and `normal_rgb` (one kernel launch each).  Everything else of PyPBR (the rotate family --
-`MaterialBase.rotate`, `transforms.Rotate` / `RandomRotate`, `functional.rotate` / `random_rotate` --, out-of-bounds crops,
-compute_height_from_normal, saving, ...) is out of scope and raises ImportError/AttributeError as an absent module would."""
+`as_tensor` and `normal_rgb` (one kernel launch each).  Rotation exists as `pypbr_amd.rotation` (`rotate`, `random_rotate`, `Rotate`,
+`RandomRotate`: one kernel launch per block of maps); the upstream NAMES `MaterialBase.rotate`, `transforms.Rotate` / `RandomRotate` and
+`functional.rotate` / `random_rotate` do not resolve through the aliases yet.  Everything else of PyPBR (out-of-bounds
+crops, compute_height_from_normal, saving, ...) is out of scope and raises ImportError/AttributeError as an absent module would."""
 import sys
 import types
 

@@ -21,29 +21,13 @@
 
 #include "../../include/pbr_hip.h"
 #include "launch_util.hpp"
+#include "plane_quads.hpp"
 
 namespace pbr {
 namespace {
 
-// The bits of one element (uint32_t: fp32, uint16_t: fp16): quads aligned as quads (stores) and as single elements (source spans).
-template <typename U> struct Quad;
-template <> struct Quad<uint32_t> {
-    typedef uint32_t v4 __attribute__((ext_vector_type(4)));
-    typedef uint32_t v4e __attribute__((ext_vector_type(4), aligned(4)));
-    static constexpr uint32_t sign = 0x80000000u;
-};
-template <> struct Quad<uint16_t> {
-    typedef uint16_t v4 __attribute__((ext_vector_type(4)));
-    typedef uint16_t v4e __attribute__((ext_vector_type(4), aligned(2)));
-    static constexpr uint16_t sign = 0x8000u;
-};
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f4e __attribute__((ext_vector_type(4), aligned(4)));
-
 struct Axes { int hs, ws, ho, wo, oy, sy, ox, sx; };
 
-// v in (-n, 2 n) -> [0, n)
-__device__ __forceinline__ int wrap_once(int v, int n) { return v < 0 ? v + n : (v >= n ? v - n : v); }
 // v a few steps outside [0, n) (a quad's pixels on an axis shorter than the quad)
 __device__ __forceinline__ int wrap_near(int v, int n) {
     while (v < 0) v += n;
@@ -166,16 +150,6 @@ int remap_arguments(int64_t a_bs, int64_t a_ps, int64_t w_bs, int64_t w_ps, int3
     if (y_offset < 0 || y_offset >= h_src || x_offset < 0 || x_offset >= w_src) return PBR_ERR_SHAPE;
     if ((y_step != 1 && y_step != -1) || (x_step != 1 && x_step != -1)) return PBR_ERR_SHAPE;
     return PBR_OK;
-}
-
-// Quads per row, quads per image and workgroups of a launch over [batch] images of h x w; false when the grid would not fit.
-bool quad_grid(int32_t batch, int32_t h, int32_t w, uint32_t &qpr, uint32_t &quads, uint32_t &per_image, uint32_t &blocks) {
-    const int64_t per_row = ((int64_t)w + 3) / 4, total = per_row * h;
-    if (total > 0x7fffffff) return false;
-    const int64_t bpi = (total + 255) / 256, all = bpi * batch;
-    if (all > 0x7fffffff) return false;
-    qpr = (uint32_t)per_row; quads = (uint32_t)total; per_image = (uint32_t)bpi; blocks = (uint32_t)all;
-    return true;
 }
 
 }  // namespace

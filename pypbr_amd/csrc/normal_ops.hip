@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "../../include/pbr_hip.h"
+#include "normal_affine.hpp"
 #include "stream_shape.hpp"
 
 namespace pbr {
@@ -204,19 +205,7 @@ __global__ __launch_bounds__(256) void normal_from_height_backward_kernel(const 
 }
 
 // ---- the affine transform of (x, y), optional renormalisation ---------------------------------------------------------------
-struct Affine { float m00, m01, m10, m11; int diag, renorm; };
-
-__device__ __forceinline__ void affine_xy(const Affine &M, float x, float y, float &xo, float &yo) {
-    if (M.diag) { xo = M.m00 * x; yo = M.m11 * y; }                   // strength / invert: x f, -y exactly as the reference's in-place ops
-    else { xo = fmaf(M.m01, y, M.m00 * x); yo = fmaf(M.m11, y, M.m10 * x); }
-}
-
-// F.normalize's denominator: max(|v|, 1e-12); a NaN norm stays NaN
-__device__ __forceinline__ float norm_denominator(float x, float y, float z) {
-    const float len = __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));
-    return len < 1e-12f ? 1e-12f : len;
-}
-
+// Affine, affine_xy, norm_denominator, normal_affine and normal_affine_backward: normal_affine.hpp (shared with rotation.hip)
 template <typename T, int V>
 __global__ __launch_bounds__(256) void normal_transform_kernel(const void *src, int64_t s_bs, int64_t s_ps, void *dst, int64_t d_bs,
                                                                int64_t d_ps, int64_t units, int64_t total, Affine M) {
@@ -229,21 +218,13 @@ __global__ __launch_bounds__(256) void normal_transform_kernel(const void *src, 
     Vec<T, V>::ld(src, so + s_ps, y);
     Vec<T, V>::ld(src, so + 2 * s_ps, z);
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-        float xo, yo;
-        affine_xy(M, x[j], y[j], xo, yo);
-        x[j] = xo; y[j] = yo;
-        if (M.renorm) {
-            const float d = norm_denominator(x[j], y[j], z[j]);
-            x[j] = __fdiv_rn(x[j], d); y[j] = __fdiv_rn(y[j], d); z[j] = __fdiv_rn(z[j], d);
-        }
-    }
+    for (int j = 0; j < V; ++j) normal_affine(M, x[j], y[j], z[j]);
     Vec<T, V>::st(dst, dO, x);                                         // dst == src: every lane reads its pixels before it writes them
     Vec<T, V>::st(dst, dO + d_ps, y);
     Vec<T, V>::st(dst, dO + 2 * d_ps, z);
 }
 
-// g_v = renorm ? (g - n (n . g)) / |v|  (g / 1e-12 where the clamp held) : g;  g_xy = M^T g_v_xy, g_z = g_v_z
+// normal_affine_backward per pixel: g_v = renorm ? (g - n (n . g)) / |v|  (g / 1e-12 where the clamp held) : g;  g_xy = M^T g_v_xy, g_z = g_v_z
 template <int V>
 __global__ __launch_bounds__(256) void normal_transform_backward_kernel(const float *src, int64_t s_bs, int64_t s_ps, const float *grad,
                                                                         int64_t g_bs, int64_t g_ps, float *grad_in, int64_t gi_bs,
@@ -260,24 +241,7 @@ __global__ __launch_bounds__(256) void normal_transform_backward_kernel(const fl
     Vec<float, V>::ld(grad, go + g_ps, gy);
     Vec<float, V>::ld(grad, go + 2 * g_ps, gz);
 #pragma unroll
-    for (int j = 0; j < V; ++j) {
-        float vx, vy, vz = z[j];
-        affine_xy(M, x[j], y[j], vx, vy);
-        float ax = gx[j], ay = gy[j], az = gz[j];
-        if (M.renorm) {
-            const float d = norm_denominator(vx, vy, vz);
-            if (d > 1e-12f) {
-                const float nx = vx / d, ny = vy / d, nz = vz / d;
-                const float k = fmaf(nz, az, fmaf(ny, ay, nx * ax));
-                ax = (ax - nx * k) / d; ay = (ay - ny * k) / d; az = (az - nz * k) / d;
-            } else {
-                ax = ax / d; ay = ay / d; az = az / d;
-            }
-        }
-        gx[j] = fmaf(M.m10, ay, M.m00 * ax);
-        gy[j] = fmaf(M.m11, ay, M.m01 * ax);
-        gz[j] = az;
-    }
+    for (int j = 0; j < V; ++j) normal_affine_backward(M, x[j], y[j], z[j], gx[j], gy[j], gz[j]);
     Vec<float, V>::st(grad_in, io, gx);
     Vec<float, V>::st(grad_in, io + gi_ps, gy);
     Vec<float, V>::st(grad_in, io + 2 * gi_ps, gz);
@@ -363,7 +327,7 @@ int pbr_normal_transform(const void *src, int64_t src_batch_stride, int64_t src_
     const size_t esz = dtype == PBR_F32 ? 4 : 2;
     const bool vec = pixels % 4 == 0 && is_aligned(src, 4 * esz) && is_aligned(dst, 4 * esz) && src_batch_stride % 4 == 0 &&
                      src_plane_stride % 4 == 0 && dst_batch_stride % 4 == 0 && dst_plane_stride % 4 == 0;
-    const Affine M = {m00, m01, m10, m11, (int)(m01 == 0.0f && m10 == 0.0f), (int)(renormalize != 0)};
+    const Affine M = make_affine(m00, m01, m10, m11, renormalize);
     const int64_t units = vec ? pixels / 4 : pixels, total = units * batch;
     const StreamShape sh = stream_shape((size_t)total, {1, 0});
     if ((int64_t)sh.grid * sh.block < total) return PBR_ERR_SHAPE;
@@ -388,7 +352,7 @@ int pbr_normal_transform_backward(const void *src, int64_t src_batch_stride, int
     const bool vec = pixels % 4 == 0 && is_aligned(src, 16) && is_aligned(grad_out, 16) && is_aligned(grad_in, 16) && src_batch_stride % 4 == 0 &&
                      src_plane_stride % 4 == 0 && grad_batch_stride % 4 == 0 && grad_plane_stride % 4 == 0 && grad_in_batch_stride % 4 == 0 &&
                      grad_in_plane_stride % 4 == 0;
-    const Affine M = {m00, m01, m10, m11, (int)(m01 == 0.0f && m10 == 0.0f), (int)(renormalize != 0)};
+    const Affine M = make_affine(m00, m01, m10, m11, renormalize);
     const int64_t units = vec ? pixels / 4 : pixels, total = units * batch;
     const StreamShape sh = stream_shape((size_t)total, {1, 0});
     if ((int64_t)sh.grid * sh.block < total) return PBR_ERR_SHAPE;

@@ -1,6 +1,7 @@
 """pypbr.transforms for the MI355X build: upstream's transform classes (pypbr/transforms/transforms.py) and, as `transforms.functional`,
-their functional forms -- all but the rotate family (`Rotate`, `RandomRotate`, `rotate`, `random_rotate`: upstream builds them on
-torchvision, which has no stand-in here; the names are absent as an absent module's would be).
+their functional forms -- all but the rotate family (`Rotate`, `RandomRotate`, `rotate`, `random_rotate`), which is built in a module
+of its own and not re-exported here: the names stay absent from this module as an absent module's would be, and a
+`Rotate` instance from that module is an ordinary callable to `Compose`.
 
 Every transform takes a material and returns a new one.  `Compose` does what upstream's does -- each stage applied to the previous
 stage's result -- but a maximal run of GEOMETRIC stages (`Crop`, `CenterCrop`, `RandomCrop`, `FlipHorizontal`, `FlipVertical`,
