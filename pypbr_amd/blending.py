@@ -11,14 +11,11 @@ import torch
 
 from . import _native
 from . import functional as F_
+from ._dispatch import launch, ptr
 from .materials import MaterialBase, _compute_device
 
 
 # ---------------------------------------------------------------- device ops (fp32 planar maps)
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _check_f32(t, what):
     if not t.is_cuda:
         raise RuntimeError("%s needs tensors on a ROCm device; there is no CPU path" % what)
@@ -29,9 +26,8 @@ def _check_f32(t, what):
 
 def _blend_maps_raw(a, b, m, is_normal):
     out = torch.empty_like(a)
-    with torch.cuda.device(a.device):
-        _native.check(_native.lib().pbr_blend_maps(a.data_ptr(), b.data_ptr(), m.data_ptr(), out.data_ptr(), a.shape[0],
-                                                   a.shape[1] * a.shape[2], int(bool(is_normal)), _stream(a)))
+    launch(a.device, _native.lib().pbr_blend_maps, a.data_ptr(), b.data_ptr(), m.data_ptr(), out.data_ptr(), a.shape[0],
+           a.shape[1] * a.shape[2], int(bool(is_normal)))
     return out
 
 
@@ -52,11 +48,8 @@ class _BlendMapsFn(torch.autograd.Function):
         ga = torch.empty_like(a) if ctx.needs_input_grad[0] else None
         gb = torch.empty_like(b) if ctx.needs_input_grad[1] else None
         gm = torch.empty_like(m) if ctx.needs_input_grad[2] else None
-        with torch.cuda.device(a.device):
-            _native.check(_native.lib().pbr_blend_maps_backward(
-                a.data_ptr(), b.data_ptr(), m.data_ptr(), g.data_ptr(), None if ga is None else ga.data_ptr(),
-                None if gb is None else gb.data_ptr(), None if gm is None else gm.data_ptr(), a.shape[0], a.shape[1] * a.shape[2],
-                int(ctx.is_normal), 0, _stream(a)))
+        launch(a.device, _native.lib().pbr_blend_maps_backward, a.data_ptr(), b.data_ptr(), m.data_ptr(), g.data_ptr(), ptr(ga), ptr(gb), ptr(gm),
+               a.shape[0], a.shape[1] * a.shape[2], int(ctx.is_normal), 0)
         return ga, gb, gm, None
 
 
@@ -79,9 +72,7 @@ def blend_maps(map1: torch.Tensor, map2: torch.Tensor, mask: torch.Tensor, is_no
 
 def _sigmoid_mask_raw(a, b, blend_width, shift):
     out = torch.empty_like(a)
-    with torch.cuda.device(a.device):
-        _native.check(_native.lib().pbr_blend_sigmoid_mask(a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(),
-                                                           float(shift), float(blend_width), _stream(a)))
+    launch(a.device, _native.lib().pbr_blend_sigmoid_mask, a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), float(shift), float(blend_width))
     return out
 
 
@@ -102,10 +93,8 @@ class _SigmoidMaskFn(torch.autograd.Function):
         g = grad_out.to(torch.float32).contiguous()
         g1 = torch.empty_like(mask) if ctx.needs_input_grad[0] else None
         g2 = torch.empty_like(mask) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(mask.device):
-            _native.check(_native.lib().pbr_blend_sigmoid_mask_backward(mask.data_ptr(), g.data_ptr(), None if g1 is None else g1.data_ptr(),
-                                                                        None if g2 is None else g2.data_ptr(), mask.numel(), ctx.blend_width,
-                                                                        _stream(mask)))
+        launch(mask.device, _native.lib().pbr_blend_sigmoid_mask_backward, mask.data_ptr(), g.data_ptr(), ptr(g1), ptr(g2), mask.numel(),
+               ctx.blend_width)
         return g1, g2, None, None
 
 
@@ -124,9 +113,7 @@ def gradient_mask(height: int, width: int, direction: str, device) -> torch.Tens
     if direction not in ("horizontal", "vertical"):
         raise ValueError("Direction must be 'horizontal' or 'vertical'.")
     out = torch.empty((1, height, width), dtype=torch.float32, device=device)
-    with torch.cuda.device(out.device):
-        _native.check(_native.lib().pbr_blend_gradient_mask(out.data_ptr(), height, width, int(direction == "vertical"),
-                                                            _stream(out)))
+    launch(out.device, _native.lib().pbr_blend_gradient_mask, out.data_ptr(), height, width, int(direction == "vertical"))
     return out
 
 

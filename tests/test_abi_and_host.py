@@ -450,15 +450,16 @@ def test_pack_maps_layouts_on_the_host():
     assert pr.untyped_storage().data_ptr() == base == out.untyped_storage().data_ptr()
     assert all(t.data_ptr() % 256 == 0 and t.stride(-1) == 1 and t.stride(-2) == 16 for t in (pa, pr, out)) and pa.is_contiguous()
     big = torch.rand(3, 2048, 1024, generator=g)                      # 8 MiB planes: the size the skew option applies to
-    old = F.PLANE_SKEW_BYTES
+    from pypbr_amd import _upload as U
+    old = U.PLANE_SKEW_BYTES
     try:
-        F.PLANE_SKEW_BYTES = 4352
+        U.PLANE_SKEW_BYTES = 4352
         (skewed,) = F.pack_maps(big)
         assert torch.equal(skewed, big) and skewed.stride() == (2048 * 1024 + 1088, 1024, 1) and not skewed.is_contiguous()
         (small,) = F.pack_maps(a)                                       # other plane sizes stay dense
         assert small.is_contiguous()
     finally:
-        F.PLANE_SKEW_BYTES = old
+        U.PLANE_SKEW_BYTES = old
     (dense,) = F.pack_maps(big)
     assert dense.is_contiguous() and torch.equal(dense, big)
     pm = F.pack_maps(a, None, r, reserve_output=True, material_major=True)

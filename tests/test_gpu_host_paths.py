@@ -101,9 +101,10 @@ def test_cpu_material_keeps_its_device_copy_between_calls():
 
 
 def test_page_locked_results_are_bounded():
+    from pypbr_amd import _upload as U
     from pypbr_amd import functional as F
-    old = F.PINNED_RESULT_CAP
-    F.PINNED_RESULT_CAP = 3 * 4 * 64 * 64 * 2 + 16                    # room for two results
+    old = U.PINNED_RESULT_CAP
+    U.PINNED_RESULT_CAP = 3 * 4 * 64 * 64 * 2 + 16                    # room for two results
     try:
         t = torch.rand(3, 64, 64, device="cuda")
         held = [F.to_host(t) for _ in range(4)]
@@ -111,7 +112,7 @@ def test_page_locked_results_are_bounded():
         del held
         assert F.to_host(t).is_pinned()                               # released results free the budget again
     finally:
-        F.PINNED_RESULT_CAP = old
+        U.PINNED_RESULT_CAP = old
 
 
 def test_fp32_maps_fp16_result():

@@ -216,7 +216,7 @@ def test_blend_example_with_sample_maps_equals_the_eager_path():
 def test_loader_decodes_into_one_page_locked_block_that_goes_up_as_it_is(monkeypatch):
     """io.load_material_from_folder: the workflow is chosen from the file names, only its maps are decoded, and their samples sit in ONE
     page-locked allocation laid out for the transfer -- upload_packed sends that block without a staging copy."""
-    from pypbr_amd import functional as F
+    from pypbr_amd import _upload as U
     eager = _maps_eagerly()
     material = _load(True)
     raw = material._raw
@@ -224,9 +224,9 @@ def test_loader_decodes_into_one_page_locked_block_that_goes_up_as_it_is(monkeyp
     assert len({t.untyped_storage().data_ptr() for t in raw.values()}) == 1 and all(t.is_pinned() for t in raw.values())
     assert raw["albedo"].untyped_storage().nbytes() == 1024 * 1024 * (3 + 3 + 1 + 2 + 1)
     copies, sent = [], []
-    stage_copy, arena = F._stage_copy, F._aligned_arena
-    monkeypatch.setattr(F, "_stage_copy", lambda *a, **k: (copies.append(1), stage_copy(*a, **k))[1])
-    monkeypatch.setattr(F, "_aligned_arena", lambda n, d: (sent.append(n), arena(n, d))[1])
+    stage_copy, arena = U._stage_copy, U._aligned_arena
+    monkeypatch.setattr(U, "_stage_copy", lambda *a, **k: (copies.append(1), stage_copy(*a, **k))[1])
+    monkeypatch.setattr(U, "_aligned_arena", lambda n, d: (sent.append(n), arena(n, d))[1])
     resident = material._resident(keep=True)
     assert copies == [] and sent == [1024 * 1024 * (10 + 4 * 9)]                        # samples + nine float planes, nothing else
     for k, v in eager._raw.items():

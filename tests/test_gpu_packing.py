@@ -134,14 +134,14 @@ def test_as_tensor_sees_what_a_reader_of_the_maps_sees():
 
 # ---- 3. layout ------------------------------------------------------------------------------------------------------------------------
 def _count_calls(monkeypatch):
-    from pypbr_amd import functional as F
+    from pypbr_amd import _packing
     calls = []
-    real = F._plane_ops_call
+    real = _packing._plane_ops_call
 
     def counted(ops, *a, **kw):
         calls.append((len(ops), bool(kw.get("backward", a[4] if len(a) > 4 else False))))
         return real(ops, *a, **kw)
-    monkeypatch.setattr(F, "_plane_ops_call", counted)
+    monkeypatch.setattr(_packing, "_plane_ops_call", counted)
     return calls
 
 

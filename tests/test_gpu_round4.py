@@ -27,13 +27,14 @@ def test_example_brdf_statements_are_one_upload_and_one_download(golden, monkeyp
     """/root/reference/examples/example_brdf.py:8-26 on the CPU-resident material the loader returns: the maps go up ONCE (all of
     them in one transfer, the normal map decoded on arrival), resize is one launch over all planes, tile(2) is only recorded (the
     kernel evaluates every texel at its four positions), and the image is the one thing that comes back."""
+    from pypbr_amd import _map_ops
     from pypbr_amd import functional as F
     from pypbr_amd.models import CookTorranceBRDF
     calls = {"up": 0, "down": 0, "resize": 0}
-    up, down, rz = F.upload_packed, F.to_host, F._resize_raw
+    up, down, rz = F.upload_packed, F.to_host, _map_ops._resize_raw
     monkeypatch.setattr(F, "upload_packed", lambda *a, **k: (calls.__setitem__("up", calls["up"] + 1), up(*a, **k))[1])
     monkeypatch.setattr(F, "to_host", lambda *a, **k: (calls.__setitem__("down", calls["down"] + 1), down(*a, **k))[1])
-    monkeypatch.setattr(F, "_resize_raw", lambda *a, **k: (calls.__setitem__("resize", calls["resize"] + 1), rz(*a, **k))[1])
+    monkeypatch.setattr(_map_ops, "_resize_raw", lambda *a, **k: (calls.__setitem__("resize", calls["resize"] + 1), rz(*a, **k))[1])
     material = _load()
     assert material.device.type == "cpu" and material.__dict__["_raw_normal"] and all(t.device.type == "cpu" for t in material._raw.values())
     assert calls == {"up": 0, "down": 0, "resize": 0}                    # loading moved nothing

@@ -4,7 +4,7 @@ python3 - <<'PY'
 import torch, sys, os
 sys.path.insert(0,'.')
 from bench import synth_material
-from pypbr_amd import functional as F
+from pypbr_amd import functional as F, _upload
 dev=torch.device('cuda',0)
 def timed(plan, iters=20):
     st=torch.cuda.current_stream().cuda_stream
@@ -19,7 +19,7 @@ for S,B in ((2048,16),(2048,64),(4096,4)):
     kw=dict(view_dir=[0,0,1], light=[0.3,-0.2,1.0], light_intensity=[1,1,1], light_type='directional')
     base=min(timed(F.plan_cook_torrance(*maps, **kw)) for _ in range(3))
     for sk in (0,4352):
-        F.PLANE_SKEW_BYTES=sk
+        _upload.PLANE_SKEW_BYTES=sk
         *pm,out=F.pack_maps(*maps, reserve_output=True)
         t=min(timed(F.plan_cook_torrance(*pm, out=out, **kw)) for _ in range(3))
         print(f'{B}x{S}^2 directional: plain tensors {base:.1f} us; pack_maps skew {sk}: {t:.1f} us  {44*B*S*S/t/1e3:.0f} GB/s')

@@ -2,7 +2,7 @@
 """Where `material.resize(...)` of a freshly loaded CPU material -- the statement of examples/example_brdf.py that uploads it -- spends its
 time, phase by phase on the host clock: layout, page-locked staging, host copies into it, device allocation, H2D enqueue, unpack launches,
 the rest of MaterialBase._resident (the samples are freed there), the resize launch.  `python tools/upload_phase_probe.py [torch threads]
-[--aten-copies]`: --aten-copies stages with Tensor.copy_ as the library did before (functional.STAGE_MEMCPY_LIMIT = 0)."""
+[--aten-copies]`: --aten-copies stages with Tensor.copy_ as the library did before (_upload.STAGE_MEMCPY_LIMIT = 0)."""
 import os
 import sys
 import time
@@ -13,6 +13,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import pypbr_amd.materials as M  # noqa: E402
+from pypbr_amd import _map_ops, _upload  # noqa: E402
 from pypbr_amd import functional as F  # noqa: E402
 from pypbr_amd.io import load_material_from_folder  # noqa: E402
 from pypbr_amd.models import CookTorranceBRDF  # noqa: E402
@@ -31,15 +32,17 @@ def wrapped(name, fn):
     return g
 
 
-for name in ("upload_packed", "_upload_stage", "_aligned_arena", "unpack_image", "_resize_raw"):
-    setattr(F, name, wrapped(name, getattr(F, name)))
+# each helper is wrapped on the module whose code calls it: materials reaches upload_packed through the functional namespace, the rest are
+# called inside their own modules
+for mod, name in ((F, "upload_packed"), (_upload, "_upload_stage"), (_upload, "_aligned_arena"), (_upload, "unpack_image"), (_map_ops, "_resize_raw")):
+    setattr(mod, name, wrapped(name, getattr(mod, name)))
 M.MaterialBase._resident = wrapped("_resident", M.MaterialBase._resident)
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 if args:
     torch.set_num_threads(int(args[0]))
 if "--aten-copies" in sys.argv:
-    F.STAGE_MEMCPY_LIMIT = 0
-print("torch threads %d, staging copies by %s" % (torch.get_num_threads(), "Tensor.copy_" if F.STAGE_MEMCPY_LIMIT == 0 else "memcpy"), flush=True)
+    _upload.STAGE_MEMCPY_LIMIT = 0
+print("torch threads %d, staging copies by %s" % (torch.get_num_threads(), "Tensor.copy_" if _upload.STAGE_MEMCPY_LIMIT == 0 else "memcpy"), flush=True)
 for rep in range(12):
     t_load = time.perf_counter()
     m = load_material_from_folder(os.path.join(ROOT, "tests", "golden", "tiles"), preferred_workflow="metallic")
