@@ -412,6 +412,53 @@ int pbr_normal_transform_backward(const void *src, int64_t src_batch_stride, int
                                   int32_t renormalize, void *stream);
 
 /*
+ * Normal -> height by Poisson reconstruction: utils.compute_height_from_normal, pypbr/utils/functions.py:180-323 (and
+ * MaterialBase.compute_height_from_normal, base.py:731-751), everything but the two Fourier transforms.  The caller
+ * runs, per batch:   pbr_normal_divergence -> rfft2 -> pbr_poisson_scale -> irfft2(s = (H, W)) -> pbr_height_stats -> pbr_height_normalize
+ * and, backwards:    pbr_height_normalize_backward -> rfft2 -> pbr_poisson_scale -> irfft2 -> pbr_normal_divergence_backward
+ * (the solve is its own adjoint: its denominators are real and even).  Normals [batch][3][height][width], every other map
+ * [batch][height][width]; rows dense, strides in ELEMENTS, any non-negative values; height * width < 2^31.  `dtype` PBR_F32 | PBR_F16 is
+ * the storage of the normals (divergence) and of the height map (normalize); everything in between and every backward is fp32.  A bad
+ * shape, stride, alignment or dtype returns PBR_ERR_SHAPE / PBR_ERR_DTYPE before anything is launched.  The images of a batch never
+ * see each other; no kernel uses atomics, and the same input gives the same bits on every run.
+ *
+ * pbr_normal_divergence: functions.py:205-228, :250-283, bit-equal to upstream's div_g.  ze = n_z + 1e-8, g_x = (-n_x / ze) scale,
+ *   g_y = (-n_y / ze) scale (OpenGL, directx 0) | (+n_y / ze) scale (DirectX);  div = (g_x(y,x+1) - g_x(y,x)) + (g_y(y+1,x) - g_y(y,x)),
+ *   the last column's x difference and the last row's y difference being g - g (replicate padding).  No clamps.  `div` is fp32.
+ */
+int pbr_normal_divergence(const void *normal, int64_t normal_batch_stride, int64_t normal_plane_stride, void *div, int64_t div_batch_stride,
+                          int32_t batch, int32_t height_px, int32_t width, float scale, int32_t directx, int dtype, void *stream);
+/* Gradient of pbr_normal_divergence w.r.t. the normals, a gather: a_x(y,x) = dd(y,x-1) [x >= 1] - dd(y,x) [x <= W-2], a_y likewise along y;
+ * g_nx = -scale a_x / ze, g_ny = -+scale a_y / ze, g_nz = scale (n_x a_x +- n_y a_y) / ze^2 (upper signs: OpenGL).  fp32; `normal` is the
+ * forward's input. */
+int pbr_normal_divergence_backward(const void *normal, int64_t normal_batch_stride, int64_t normal_plane_stride, const void *grad_div,
+                                   int64_t grad_div_batch_stride, void *grad_normal, int64_t grad_batch_stride, int64_t grad_plane_stride,
+                                   int32_t batch, int32_t height_px, int32_t width, float scale, int32_t directx, void *stream);
+/* functions.py:286-323 between its transforms, in place on the half spectrum [batch][height_px][width / 2 + 1] of interleaved complex64
+ * (8-byte aligned; `spectrum_batch_stride` in complex elements; `width` is the REAL width): both components divided by
+ * den(ky, kx) = -4 (sin^2(pi kx / width) + sin^2(pi ky / height_px)), the DC bin set to 0.  den is upstream's
+ * (2 cos(2 pi kx / W) - 2) + (2 cos(2 pi ky / H) - 2) in the form that does not cancel at low frequencies. */
+int pbr_poisson_scale(void *spectrum, int64_t spectrum_batch_stride, int32_t batch, int32_t height_px, int32_t width, void *stream);
+/* Bytes of the workspace pbr_height_stats / pbr_height_normalize and pbr_height_normalize_backward need (8-byte aligned; 0: bad shape):
+ * one 24-byte partial per 12288 pixels of every image. */
+size_t pbr_height_workspace_bytes(int32_t batch, int32_t height_px, int32_t width);
+/* Per image of `height` (fp32, the inverse transform's output): sum (fp64), min, max and the linear indices of the first minimum and
+ * the first maximum, as per-workgroup partials over fixed pixel ranges in `workspace`. */
+int pbr_height_stats(const void *height, int64_t height_batch_stride, void *workspace, int32_t batch, int32_t height_px, int32_t width,
+                     void *stream);
+/* functions.py:234-242: folds the partials in index order (64 consecutive groups one by one, then the groups: a fixed association), then out = ((h - mean) - mn) / ((mx - mn) + 1e-8) with mn = fl(min h - mean),
+ * mx = fl(max h - mean), stored as `dtype`; `stats` [batch][5] fp32 receives {mean, mn, range, argmin, argmax}, the two indices as int32
+ * bit patterns (what the backward reads). */
+int pbr_height_normalize(const void *height, int64_t height_batch_stride, const void *workspace, void *out, int64_t out_batch_stride,
+                         void *stats, int32_t batch, int32_t height_px, int32_t width, int dtype, void *stream);
+/* Gradient of pbr_height_normalize w.r.t. its input: with r = range, q = sum(G out) / r, s = sum(G) / r (fp64 partials in `workspace`,
+ * folded as the forward's), dh = G / r + [i = argmin] (q - s) - [i = argmax] q.  The gradient of min / max goes to the FIRST index (upstream
+ * spreads it over ties); the mean subtraction's adjoint vanishes (sum(dh) = 0).  fp32; `out` and `stats` are the forward's results. */
+int pbr_height_normalize_backward(const void *grad_out, int64_t grad_batch_stride, const void *out, int64_t out_batch_stride, const void *stats,
+                                  void *workspace, void *grad_height, int64_t grad_height_batch_stride, int32_t batch, int32_t height_px,
+                                  int32_t width, void *stream);
+
+/*
  * The geometric material transforms of pypbr/materials/base.py -- crop (:506-522, in-bounds), tile (:524-537), flip_horizontal /
  * flip_vertical (:605-639), roll (:641-655) -- and every chain of them as ONE index map per axis:
  *     src(i) = (offset + step * i) mod N,   i in [0, L),   step = +1 | -1,   0 <= offset < N

@@ -46,6 +46,8 @@ EXPORTS = (
     "pbr_remap_planes", "pbr_remap_planes_backward",
     "pbr_plane_ops", "pbr_plane_ops_backward",
     "pbr_rotate_planes", "pbr_rotate_planes_backward",
+    "pbr_normal_divergence", "pbr_normal_divergence_backward", "pbr_poisson_scale", "pbr_height_workspace_bytes", "pbr_height_stats",
+    "pbr_height_normalize", "pbr_height_normalize_backward",
 )
 
 
@@ -226,6 +228,17 @@ def lib():
     L.pbr_rotate_planes.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, geom, i32, f32, f32, f32, f32, ctypes.c_int, vp]
     L.pbr_rotate_planes_backward.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, geom, i32, f32, f32, f32, f32, vp]
     L.pbr_rotate_planes.restype = L.pbr_rotate_planes_backward.restype = ctypes.c_int
+    L.pbr_normal_divergence.argtypes = [vp, i64, i64, vp, i64, i32, i32, i32, f32, i32, ctypes.c_int, vp]
+    L.pbr_normal_divergence_backward.argtypes = [vp, i64, i64, vp, i64, vp, i64, i64, i32, i32, i32, f32, i32, vp]
+    L.pbr_poisson_scale.argtypes = [vp, i64, i32, i32, i32, vp]
+    L.pbr_height_workspace_bytes.argtypes = [i32, i32, i32]
+    L.pbr_height_workspace_bytes.restype = ctypes.c_size_t
+    L.pbr_height_stats.argtypes = [vp, i64, vp, i32, i32, i32, vp]
+    L.pbr_height_normalize.argtypes = [vp, i64, vp, vp, i64, vp, i32, i32, i32, ctypes.c_int, vp]
+    L.pbr_height_normalize_backward.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp]
+    for name in ("pbr_normal_divergence", "pbr_normal_divergence_backward", "pbr_poisson_scale", "pbr_height_stats", "pbr_height_normalize",
+                 "pbr_height_normalize_backward"):
+        getattr(L, name).restype = ctypes.c_int
     for name in ("pbr_srgb_to_linear", "pbr_linear_to_srgb", "pbr_metallic_to_specular",
                  "pbr_specular_to_metallic", "pbr_decode_normal", "pbr_abi_version", "pbr_set_tuning",
                  "pbr_bytes_per_pixel"):

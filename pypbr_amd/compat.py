@@ -13,8 +13,10 @@ methods `crop` (in-bounds), `flip_horizontal`, `flip_vertical`, `roll`, and `pyp
 forms, `Compose` running a chain of geometric stages as one kernel launch.  So do the packed-tensor methods `MaterialBase.from_tensor`,
 `as_tensor` and `normal_rgb` (one kernel launch each).  Rotation exists as `pypbr_amd.rotation` (`rotate`, `random_rotate`, `Rotate`,
 `RandomRotate`: one kernel launch per block of maps); the upstream NAMES `MaterialBase.rotate`, `transforms.Rotate` / `RandomRotate` and
-`functional.rotate` / `random_rotate` do not resolve through the aliases yet.  Everything else of PyPBR (out-of-bounds
-crops, compute_height_from_normal, saving, ...) is out of scope and raises ImportError/AttributeError as an absent module would."""
+`functional.rotate` / `random_rotate` do not resolve through the aliases yet.  The Poisson reconstruction of a height
+map exists as `MaterialBase.compute_height_from_normal` and `pypbr_amd.functional.height_from_normal`; the function's upstream name
+`pypbr.utils.compute_height_from_normal` does not resolve yet either.  Everything else of PyPBR (out-of-bounds
+crops, saving, ...) is out of scope and raises ImportError/AttributeError as an absent module would."""
 import sys
 import types
 

@@ -24,6 +24,7 @@ sibling modules, one per file of csrc/, and their names are imported back below,
   _upload       to_host, pack_maps, upload_packed, unpack_image, the staging areas                      csrc/unpack.hip
   _map_ops      colour transfers, metallic <-> specular, resize, decode_normal                          csrc/map_ops.hip, resize.hip
   _normal_ops   normal_from_height, transform_normals                                                   csrc/normal_ops.hip
+  _height_ops   height_from_normal (around torch.fft.rfft2 / irfft2)                                     csrc/height_ops.hip
   _geometry     PlaneMap, fold_stages, check_crop, remap_planes                                         csrc/geometry.hip
   _packing      unpack_planes, pack_planes, the plane-op tables                                         csrc/packing.hip
   _rotate_ops   rotate_plan, rotate_indices, rotate_maps                                                csrc/rotation.hip
@@ -53,6 +54,7 @@ from ._map_ops import (  # noqa: F401
     _resize_raw, decode_normal, diffuse_specular_to_basecolor_metallic, linear_to_srgb, metallic_to_diffuse_specular, resize, srgb_to_linear)
 from ._normal_ops import (  # noqa: F401
     _NormalFromHeightFn, _TransformNormalsFn, _directx, _matrix, _nfh_raw, _transform_raw, normal_from_height, transform_normals)
+from ._height_ops import _HeightFromNormalFn, _hfn_raw, _poisson_solve, height_from_normal  # noqa: F401
 from ._geometry import PlaneMap, _RemapFn, _axis_map, _remap_raw, check_crop, fold_stages, remap_planes  # noqa: F401
 from ._packing import (  # noqa: F401
     _PackFn, _UnpackFn, _affine_plan, _on_device, _pack, _pack_raw, _plane_ops_call, _plane_ptr, _planes_of, _run_plane_ops, _unpack_layout,

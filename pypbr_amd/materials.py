@@ -609,6 +609,20 @@ class MaterialBase:
         self.__dict__["_raw_normal"] = False
         return self
 
+    def compute_height_from_normal(self, scale: float = 1.0):
+        """base.py:731-751: the height map reconstructed from the normal map (a Poisson solve, functional.height_from_normal) in this
+        material's normal_convention, normalised to [0, 1].  A pending lazy blend and a pending tile(n, lazy=True) are carried out
+        first, as for compute_normal_from_height: the solve is periodic over the map it is given.  The result is stored as it comes out
+        of the kernel, on the compute device (upstream writes _maps["height"] directly).  A normal map that requires grad keeps its graph."""
+        directx = F_._directx(self.normal_convention)           # argument errors before any device work
+        self.materialize_blend()
+        if self._raw.get("normal") is None:
+            raise ValueError("Normal map is required to compute height.")
+        self.materialize_tile()
+        maps = self._resident(keep=True)                        # a deferred decode of the normal map happens on the way
+        self._raw["height"] = F_.height_from_normal(maps["normal"], scale, "directx" if directx else "opengl")
+        return self
+
     # -- the two calls around the BRDF in examples/example_brdf.py:11 (SURVEY.md 8f, N1)
     def resize(self, size, antialias: bool = True):
         """Resize every map (base.py:490-504): bilinear, antialiased by default; in place, returns self.  All float32 (C,H,W) maps

@@ -1,6 +1,7 @@
 """The reference's utility functions (pypbr/utils/functions.py:31-177) with its names and signatures, evaluated by libpbr_hip.so.
 CPU tensors are staged through the device; with no ROCm device present the call raises (no CPU arithmetic in this package).
-compute_height_from_normal (an FFT Poisson solve) is not provided."""
+compute_height_from_normal (functions.py:180-323) is built as functional.height_from_normal and MaterialBase.compute_height_from_normal;
+its one-line re-export under upstream's name in this module is pending (an existing test pins the name's absence)."""
 import math
 
 import torch
