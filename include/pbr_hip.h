@@ -572,6 +572,36 @@ int pbr_unpack_image(const void *src, int32_t bits, int32_t channels, int32_t he
                      int64_t stride_h, int64_t stride_w, float *dst, int32_t decode_normal, void *stream);
 
 /*
+ * MaterialBase.to_pil, base.py:793-850, on the device -- the way back of pbr_unpack_image: planar float32 maps become image samples,
+ * dense (height, width, channels) uint8 (`bits` 8) or uint16 (`bits` 16) arrays as PIL takes them.  ONE launch for a table of at most
+ * PBR_MAX_IMAGE_PACKS maps that share (height, width) -- a material's maps as a rule.  `src` is addressed as
+ * src[c*stride_c + y*stride_h + x*stride_w] (strides in ELEMENTS, none negative), so a view with a plane pitch or a row pitch is read as
+ * it is.  Arithmetic, every product and sum rounded on its own, in fp32:
+ *   bits 8          torchvision's to_pil_image: pic.mul(255).byte() -- v * 255, truncated toward zero;
+ *   bits 16         base.py:837: (t * 65535).clip(0, 65535).astype(uint16) -- v * 65535, truncated toward zero;
+ *   encode_normal   base.py:818 first: (v + 1.0) * 0.5; channels must be 3.
+ * Inside [0, 1] every sample is the reference's bit for bit.  Where the reference is undefined behaviour the result SATURATES: below 0
+ * -> 0, above the maximum -> the maximum, +-inf likewise, NaN -> 0.  A map whose rows are dense, with width % 4 == 0, plane starts
+ * 16-byte aligned and dst dword aligned is written in whole dwords, 4 pixels per lane; every other map one pixel per lane.  A launch
+ * writes exactly height * width * channels samples per map and must not write what it reads.  No workspace, no atomics.  Caller errors,
+ * before anything is launched: a NULL table, `src` or `dst` PBR_ERR_NULL_MAP; n_maps outside [1, PBR_MAX_IMAGE_PACKS], an extent < 1,
+ * height * width > 2^40, a negative stride, a `src` that is not 4-byte aligned, a `dst` for 16 bit that is not 2-byte aligned, two `dst`
+ * ranges of one call that overlap PBR_ERR_SHAPE; `bits` not 8 or 16 PBR_ERR_DTYPE; `channels` outside 1..4, or not 3 with
+ * encode_normal, PBR_ERR_CHANNELS.  (ABI 9: an entry point added, nothing changed.)
+ */
+#define PBR_MAX_IMAGE_PACKS 8
+typedef struct pbr_image_pack {
+    const float *src;             /* planar float32; element strides below */
+    int64_t stride_c, stride_h, stride_w;
+    void *dst;                    /* dense (H, W, C) samples, uint8 or uint16 */
+    int32_t channels;             /* 1..4; 3 when encode_normal */
+    int32_t bits;                 /* 8 | 16 */
+    int32_t encode_normal;        /* (v + 1) * 0.5 first */
+    int32_t reserved;
+} pbr_image_pack;
+int pbr_pack_images(const pbr_image_pack *maps, int32_t n_maps, int32_t height, int32_t width, void *stream);
+
+/*
  * MaterialBase.resize, base.py:490-504 (torchvision resize of a float (C,H,W) map ==
  * F.interpolate(mode="bilinear", align_corners=False, antialias=...)).  fp32 planar
  * [planes][h_in][w_in] -> [planes][h_out][w_out]; `workspace` holds the width-pass

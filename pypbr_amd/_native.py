@@ -48,6 +48,7 @@ EXPORTS = (
     "pbr_rotate_planes", "pbr_rotate_planes_backward",
     "pbr_normal_divergence", "pbr_normal_divergence_backward", "pbr_poisson_scale", "pbr_height_workspace_bytes", "pbr_height_stats",
     "pbr_height_normalize", "pbr_height_normalize_backward",
+    "pbr_pack_images",
 )
 
 
@@ -113,6 +114,16 @@ class PlaneOp(ctypes.Structure):
                 ("dst", ctypes.c_void_p), ("dst_batch_stride", ctypes.c_int64), ("dst_plane_stride", ctypes.c_int64),
                 ("input", ctypes.c_void_p), ("input_batch_stride", ctypes.c_int64), ("input_plane_stride", ctypes.c_int64),
                 ("scale", ctypes.c_float), ("bias", ctypes.c_float)]
+
+
+MAX_IMAGE_PACKS = 8
+
+
+class ImagePack(ctypes.Structure):
+    """pbr_image_pack: one map of a pbr_pack_images table (strides in elements)."""
+    _fields_ = [("src", ctypes.c_void_p), ("stride_c", ctypes.c_int64), ("stride_h", ctypes.c_int64), ("stride_w", ctypes.c_int64),
+                ("dst", ctypes.c_void_p), ("channels", ctypes.c_int32), ("bits", ctypes.c_int32), ("encode_normal", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
 
 
 class RotateGeom(ctypes.Structure):
@@ -210,6 +221,8 @@ def lib():
     L.pbr_decode_normal_backward.argtypes = [vp, vp, vp, i32, i64, vp, vp]
     L.pbr_unpack_image.argtypes = [vp, i32, i32, i32, i32, i64, i64, i64, vp, i32, vp]
     L.pbr_unpack_image.restype = ctypes.c_int
+    L.pbr_pack_images.argtypes = [ctypes.POINTER(ImagePack), i32, i32, i32, vp]
+    L.pbr_pack_images.restype = ctypes.c_int
     f32 = ctypes.c_float
     L.pbr_normal_from_height.argtypes = [vp, i64, vp, i64, i64, i32, i32, i32, f32, i32, ctypes.c_int, vp]
     L.pbr_normal_from_height_backward.argtypes = [vp, i64, vp, i64, i64, vp, i64, i32, i32, i32, f32, i32, vp]

@@ -1,7 +1,9 @@
 """Host <-> device movement of maps: results that come home through page-locked memory (`to_host`), maps packed into one device
 allocation (`pack_maps`), and a CPU-resident material's upload as ONE transfer (`upload_packed`) with an image's samples turned into
 float32 on arrival -- MaterialBase._to_tensor, pypbr/materials/base.py:143-164, and :191-242 behind it for a normal map:
-csrc/unpack.hip (pbr_unpack_image).  `_staged` is how the family modules run a CPU tensor through the device.
+csrc/unpack.hip (pbr_unpack_image).  The way back is its mirror image: float maps become image samples on the device (`pack_image`,
+csrc/pack_image.hip, pbr_pack_images: MaterialBase.to_pil, base.py:793-850) and a material's samples come home in ONE transfer
+(`download_samples`).  `_staged` is how the family modules run a CPU tensor through the device.
 
 The four settings below are read HERE, so this is the module to assign them on (`from pypbr_amd import _upload as U; U.PLANE_SKEW_BYTES =
 4352`); pypbr_amd.functional does not re-export them.  The PBR_* environment variables seed them at import."""
@@ -220,6 +222,99 @@ def unpack_image(samples: torch.Tensor, bits: int, strides, shape, out: torch.Te
         raise ValueError("unpack_image: `out` must be a contiguous float32 (C,H,W) tensor on the samples' device")
     launch(out.device, N.lib().pbr_unpack_image, samples.data_ptr(), bits, C, H, W, strides[0], strides[1], strides[2],
            out.data_ptr(), 1 if decode_normal else 0)
+    return out
+
+
+_SAMPLE_DTYPES = {8: torch.uint8, 16: torch.uint16}
+
+
+def _image_pack(t: torch.Tensor, dst_ptr: int, bits: int, encode_normal: bool) -> N.ImagePack:
+    """One row of a pbr_pack_images table: the (C,H,W) float32 device tensor `t`, read through its own strides."""
+    return N.ImagePack(t.data_ptr(), t.stride(0), t.stride(1), t.stride(2), dst_ptr, t.shape[0], bits, 1 if encode_normal else 0, 0)
+
+
+def _pack_images_call(device, rows, height: int, width: int) -> None:
+    """One call into pbr_pack_images: at most N.MAX_IMAGE_PACKS maps of one (height, width), one launch."""
+    table = (N.ImagePack * len(rows))(*rows)
+    launch(device, N.lib().pbr_pack_images, table, len(rows), height, width)
+
+
+def _float_map(t: torch.Tensor, what: str) -> torch.Tensor:
+    """The (C,H,W) float32 map the kernel reads.  A float16 map is converted to float32 FIRST: its samples are those of the float32
+    values (upstream would multiply in half precision and round the product to half before truncating)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        raise ValueError("%s takes a (C,H,W) map, got %s" % (what, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)))
+    if t.dtype == torch.float16:
+        t = t.float()
+    if t.dtype != torch.float32:
+        raise TypeError("%s supports float32 (float16 is converted to float32 first), got %s" % (what, t.dtype))
+    if not 1 <= t.shape[0] <= 4:
+        raise ValueError("%s: a map has 1 to 4 channels, got %d" % (what, t.shape[0]))
+    if min(t.shape) < 1:
+        raise ValueError("%s: empty map %s" % (what, tuple(t.shape)))
+    return t.detach()
+
+
+def pack_image(t: torch.Tensor, bits: int = 8, encode_normal: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MaterialBase.to_pil's arithmetic for ONE map (base.py:793-850) on the device: float32 (C,H,W) `t`, any strides -> the (H,W,C)
+    sample tensor on `t`'s device, uint8 (`bits` 8: torchvision's pic.mul(255).byte()) or uint16 (`bits` 16: base.py:837), a normal
+    map through (n + 1.0) * 0.5 first (`encode_normal`, 3 channels).  Inside [0, 1] upstream's samples bit for bit; outside it the
+    samples saturate and NaN gives 0 (include/pbr_hip.h, pbr_pack_images).  float32 only: a float16 map is converted to float32 first.
+    `out`: a contiguous (H,W,C) tensor of the sample type on `t`'s device.  A CPU tensor travels to the device and its samples back."""
+    if bits not in _SAMPLE_DTYPES:
+        raise TypeError("pack_image: bits must be 8 or 16, got %r" % (bits,))
+    t = _float_map(t, "pack_image")
+    C, H, W = t.shape
+    if encode_normal and C != 3:
+        raise ValueError("pack_image: a normal map has 3 channels, got %d" % C)
+    if not t.is_cuda:
+        if out is not None:
+            raise ValueError("pack_image: `out` goes with a map on a ROCm device")
+        return _staged(t, lambda d: pack_image(d, bits, encode_normal))
+    if out is None:
+        out = torch.empty((H, W, C), dtype=_SAMPLE_DTYPES[bits], device=t.device)
+    elif out.dtype != _SAMPLE_DTYPES[bits] or tuple(out.shape) != (H, W, C) or not out.is_contiguous() or out.device != t.device:
+        raise ValueError("pack_image: `out` must be a contiguous (H,W,C) %s tensor on the map's device" % _SAMPLE_DTYPES[bits])
+    _pack_images_call(t.device, [_image_pack(t, out.data_ptr(), bits, encode_normal)], H, W)
+    return out
+
+
+def download_samples(maps: dict, bits, normal_name: str = "normal") -> dict:
+    """name -> float (C,H,W) map on ONE ROCm device  ->  name -> numpy (H,W,C) samples on the host, uint8 or uint16 as `bits` says (an
+    int for all maps, or a dict name -> 8 | 16, 8 where it has no entry); the map called `normal_name` is encoded as a normal map.  The
+    samples of all maps are written into one device arena, each map 256-byte aligned, by ONE pbr_pack_images call per (H, W) group
+    (per N.MAX_IMAGE_PACKS maps of it), and come home in ONE device-to-host copy through `to_host` (page-locked, subject to
+    PINNED_RESULT_CAP).  The arrays are views of that one block: no per-map copy, no arithmetic on the host."""
+    names = [k for k, t in maps.items() if t is not None]
+    if not names:
+        return {}
+    ts = {k: _float_map(maps[k], "download_samples") for k in names}
+    dev = ts[names[0]].device
+    if dev.type != "cuda" or any(t.device != dev for t in ts.values()):
+        raise RuntimeError("download_samples needs every map on one ROCm device; there is no CPU path")
+    width = {k: (bits.get(k, 8) if isinstance(bits, dict) else bits) for k in names}
+    if any(b not in _SAMPLE_DTYPES for b in width.values()):
+        raise TypeError("download_samples: bits must be 8 or 16, got %r" % (bits,))
+    if normal_name in ts and ts[normal_name].shape[0] != 3:
+        raise ValueError("download_samples: a normal map has 3 channels, got %d" % ts[normal_name].shape[0])
+    offs, total = {}, 0
+    for k in names:
+        offs[k] = total
+        total += -(-ts[k].numel() * (width[k] // 8) // 256) * 256
+    arena = _aligned_arena(total, dev)
+    groups = {}
+    for k in names:
+        groups.setdefault(tuple(ts[k].shape[-2:]), []).append(k)
+    for (H, W), members in groups.items():
+        for i in range(0, len(members), N.MAX_IMAGE_PACKS):
+            rows = [_image_pack(ts[k], arena.data_ptr() + offs[k], width[k], k == normal_name) for k in members[i:i + N.MAX_IMAGE_PACKS]]
+            _pack_images_call(dev, rows, H, W)
+    host = to_host(arena).numpy()
+    out = {}
+    for k in names:
+        C, H, W = ts[k].shape
+        n = C * H * W * (width[k] // 8)
+        out[k] = host[offs[k]:offs[k] + n].view("uint8" if width[k] == 8 else "uint16").reshape(H, W, C)
     return out
 
 

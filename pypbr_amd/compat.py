@@ -15,8 +15,9 @@ forms, `Compose` running a chain of geometric stages as one kernel launch.  So d
 `RandomRotate`: one kernel launch per block of maps); the upstream NAMES `MaterialBase.rotate`, `transforms.Rotate` / `RandomRotate` and
 `functional.rotate` / `random_rotate` do not resolve through the aliases yet.  The Poisson reconstruction of a height
 map exists as `MaterialBase.compute_height_from_normal` and `pypbr_amd.functional.height_from_normal`; the function's upstream name
-`pypbr.utils.compute_height_from_normal` does not resolve yet either.  Everything else of PyPBR (out-of-bounds
-crops, saving, ...) is out of scope and raises ImportError/AttributeError as an absent module would."""
+`pypbr.utils.compute_height_from_normal` does not resolve yet either.  Saving exists: `MaterialBase.to_pil`, `to_numpy`,
+`save_to_folder` and `pypbr.io.save_material_to_folder` (the samples are made on the device, one kernel launch per map size).  Everything
+else of PyPBR (out-of-bounds crops, ...) is out of scope and raises ImportError/AttributeError as an absent module would."""
 import sys
 import types
 

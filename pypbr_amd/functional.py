@@ -21,7 +21,7 @@ This module is the public namespace of the tensor-level API and holds the render
 sibling modules, one per file of csrc/, and their names are imported back below, so `functional.<name>` resolves as it always did:
 
   _dispatch     what all families share: dtype codes, tensor checks, LAUNCHES, `launch` / `ptr`       (the C ABI: _native.py)
-  _upload       to_host, pack_maps, upload_packed, unpack_image, the staging areas                      csrc/unpack.hip
+  _upload       to_host, pack_maps, upload_packed, unpack_image, pack_image, download_samples           csrc/unpack.hip, pack_image.hip
   _map_ops      colour transfers, metallic <-> specular, resize, decode_normal                          csrc/map_ops.hip, resize.hip
   _normal_ops   normal_from_height, transform_normals                                                   csrc/normal_ops.hip
   _height_ops   height_from_normal (around torch.fft.rfft2 / irfft2)                                     csrc/height_ops.hip
@@ -48,7 +48,7 @@ from ._caches import CACHING, KeptPlan, ValueMemo, VersionMemo, host_values, set
 from ._dispatch import LAUNCHES, _DTYPES, _device_tensor, _grad_like, _needs_grad, _rows_dense, _stream_ptr, launch, ptr  # noqa: F401
 from ._upload import (  # noqa: F401
     ENCODED_DTYPES, _PINNED_OUT, _UPLOAD_STAGE, _aligned_arena, _dense_samples, _pack_material_major, _page_locked_range, _stage_copy, _staged,
-    _upload_stage, is_encoded, pack_maps, release_upload_stage, to_host, unpack_image, upload_packed)
+    _upload_stage, download_samples, is_encoded, pack_image, pack_maps, release_upload_stage, to_host, unpack_image, upload_packed)
 from ._map_ops import (  # noqa: F401
     _ColourFn, _DecodeNormalFn, _MetallicToSpecularFn, _ResizeFn, _SpecularToMetallicFn, _colour_raw, _decode_normal_raw, _ds2bm_raw, _m2ds_raw,
     _resize_raw, decode_normal, diffuse_specular_to_basecolor_metallic, linear_to_srgb, metallic_to_diffuse_specular, resize, srgb_to_linear)

@@ -1,7 +1,8 @@
 """Folder -> material loader, the call in front of the BRDF in examples/example_brdf.py:8
 (SURVEY.md 8f, row N1).  Mirrors pypbr.io.load_material_from_folder / select_material_class
 (/root/reference/pypbr/io.py:27-186): same file-name conventions, same PIL mode handling,
-same workflow selection and warnings.  Host-side only (PIL decode); no arithmetic."""
+same workflow selection and warnings.  Host-side only (PIL decode); no arithmetic.  `save_material_to_folder` (io.py:189-230) is the way
+back: the material's samples come from MaterialBase.to_pil (made on the device), PIL encodes the files."""
 import os
 import warnings
 from typing import Dict, List, Optional, Type
@@ -161,3 +162,21 @@ def load_material_from_folder(folder_path: str, map_names: Optional[Dict[str, Li
     kwargs = {k: v for k, v in loaded.items() if k not in ("basecolor", "diffuse")}
     kwargs["albedo"] = albedo
     return cls(**kwargs, albedo_is_srgb=is_srgb, specular_is_srgb=is_srgb)
+
+
+# map name -> file stem (io.py:207-216)
+DEFAULT_SAVE_NAMES: Dict[str, str] = {"albedo": "albedo", "normal": "normal", "height": "height", "roughness": "roughness",
+                                      "metallic": "metallic", "specular": "specular"}
+
+
+def save_material_to_folder(material: MaterialBase, folder_path: str, map_names: Optional[Dict[str, str]] = None, format: str = "png"):
+    """io.py:189-230: creates `folder_path` and writes <map_names.get(name, name)>.<format> for every map that is present, from
+    `material.to_pil()` with no `maps_mode` -- so every map is saved 8-bit, as upstream.  Leading underscores of a map's name are
+    dropped (io.py:225)."""
+    os.makedirs(folder_path, exist_ok=True)
+    names = DEFAULT_SAVE_NAMES if map_names is None else map_names
+    for map_type, image in material.to_pil().items():
+        if image is None:
+            continue
+        clean = map_type.lstrip("_")
+        image.save(os.path.join(folder_path, f"{names.get(clean, clean)}.{format}"))

@@ -420,6 +420,69 @@ class MaterialBase:
         self.materialize_tile()
         return dict(self._maps)
 
+    # -- export (base.py:781-878): the way out of the package.  The quantisation runs on the device, csrc/pack_image.hip
+    def to_numpy(self):
+        """base.py:781-791: name -> the float map as a numpy array (None stays None)."""
+        return {name: (None if t is None else t.cpu().numpy()) for name, t in self.as_dict().items()}
+
+    def to_pil(self, maps_mode=None):
+        """base.py:793-850: name -> PIL.Image (None stays None), in the maps' dict order.  Default modes are torchvision's to_pil_image
+        of the float map -- `mul(255).byte()`, 3 channels RGB, anything else L --; a map whose entry in `maps_mode` is a 16-bit mode
+        ("I", "I;16", "I;16B", "I;16L", "I;16N") becomes mode I;16 by (t * 65535).clip(0, 65535).astype(uint16); any other requested
+        mode is ignored, as upstream; the normal map passes through (n + 1.0) * 0.5 first.  A 16-bit mode on a map of more than one
+        channel raises ValueError (upstream fails inside PIL).
+
+        The samples are made ON THE DEVICE by one pbr_pack_images launch per map size and come home in one copy of a quarter (half) of
+        the float bytes (functional.download_samples); the images are built over that block, no arithmetic on the host.  A pending
+        lazy blend or tile is carried out first, as for as_dict.  Maps that live on the device stay there: the stored tensors are the
+        same objects afterwards.  A CPU-home map that is STILL an image's samples, asked for in its own width, is handed back as those
+        samples with no device work ((k / 255) * 255 truncates back to k for every k, and likewise for 65535: exact); the normal map
+        never is -- decode and encode do not round-trip, upstream's neither.  Outside [0, 1] the samples saturate and NaN gives 0
+        (numerical differences)."""
+        from PIL import Image
+        modes = {} if maps_mode is None else maps_mode
+        self.materialize_tile()
+        self.materialize_blend()
+        store, d = self._raw, self.__dict__
+        wide, direct, through = {}, {}, []
+        for name, t in store.items():
+            if t is None:
+                continue
+            if t.dim() != 3:
+                raise ValueError("to_pil takes (C,H,W) maps; map '%s' is %s" % (name, tuple(t.shape)))
+            channels = 3 if name == "normal" and d.get("_raw_normal") else t.shape[0]
+            wide[name] = modes.get(name, "RGB") in ("I", "I;16", "I;16B", "I;16L", "I;16N")
+            if wide[name] and channels != 1:
+                raise ValueError("Map '%s' has %d channels: a 16-bit mode takes a map of one channel." % (name, channels))
+            if name == "normal" and channels != 3:
+                raise ValueError("to_pil takes a normal map of 3 channels, got %d" % channels)
+            if F_.is_encoded(t) and name != "normal" and t.element_size() == (2 if wide[name] else 1):
+                direct[name] = t.permute(1, 2, 0).numpy()                 # PIL's own (H,W,C) array again
+            else:
+                through.append(name)
+        samples = dict(direct)
+        if through:
+            maps = self._resident(keep=False)
+            samples.update(F_.download_samples({k: maps[k] for k in through}, {k: 16 if wide[k] else 8 for k in through}))
+        images = {}
+        for name, t in store.items():
+            if t is None:
+                images[name] = None
+                continue
+            a = samples[name]
+            if a.shape[2] == 1:
+                images[name] = Image.fromarray(a[:, :, 0])                # uint8 -> L, uint16 -> I;16
+            elif a.shape[2] == 3:
+                images[name] = Image.fromarray(a)                         # RGB
+            else:
+                images[name] = Image.fromarray(a).convert("L")            # upstream: 2 channels LA, 4 RGBA, then convert("L")
+        return images
+
+    def save_to_folder(self, folder_path: str):
+        """base.py:869-878: every map that is present as <name>.png under `folder_path` (io.save_material_to_folder)."""
+        from .io import save_material_to_folder
+        save_material_to_folder(self, folder_path)
+
     @property
     def normal_rgb(self):
         """base.py:279-291: the normal map as colours, (normal + 1) * 0.5, or None -- one affine pass of csrc/packing.hip (n * 0.5 + 0.5

@@ -226,6 +226,11 @@ if want("map_ops"):
            timed(lambda: lib.pbr_unpack_image(rgb.data_ptr(), 8, 3, S, S, 1, 3 * S, 3, o3.data_ptr(), 0, stream)))
     report("unpack_image 4096^2 RGB uint8 normal map -> decoded unit normals (base.py:191-242 in the same pass)", "unpack_dense_kernel<unsigned char, 3, true>", 15 * PX,
            timed(lambda: lib.pbr_unpack_image(rgb.data_ptr(), 8, 3, S, S, 1, 3 * S, 3, o3.data_ptr(), 1, stream)))
+    # the way back: float planes -> samples (12 bytes per texel in, 3 out); both cases run the one table-driven kernel
+    for label, normal in (("RGB uint8 samples", 0), ("normal map through (n + 1) * 0.5 -> RGB uint8 samples", 1)):
+        table = (N.ImagePack * 1)(N.ImagePack(a.data_ptr(), PX, S, 1, rgb.data_ptr(), 3, 8, normal, 0))
+        report("pack_images 4096^2 3 float32 planes -> %s (12 B in, 3 B out per texel)" % label, "pack_images_kernel", 15 * PX,
+               timed(lambda: lib.pbr_pack_images(table, 1, S, S, stream)))
     report("blend_maps 3 ch 4096^2 (7 planes in, 3 out)", "blend_kernel<false>", 40 * PX,
            timed(lambda: lib.pbr_blend_maps(a.data_ptr(), n.data_ptr(), m.data_ptr(), o3.data_ptr(), 3, PX, 0, stream)))
     report("blend_maps normals 4096^2 (7 planes in, 3 out)", "blend_kernel<true>", 40 * PX,
