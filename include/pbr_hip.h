@@ -613,9 +613,9 @@ int pbr_resize_bilinear(const void *src, void *dst, int64_t planes, int32_t h_in
 /* Which kernel family pbr_resize_bilinear runs for these arguments under the current knobs (nothing is launched; -1 = the call would
  * fail): what a caller's test asserts when it compares two families bit for bit, what a profile's reader looks up.  ABI 8. */
 enum {
-    PBR_RESIZE_TWO_PASS = 0,            /* width pass, height pass through the workspace (more than 36 taps per axis) */
-    PBR_RESIZE_STRIP = 1,               /* one kernel, tile by tile through an LDS strip (csrc/resize.hip: resize_strip_kernel) */
-    PBR_RESIZE_TWO_TAP = 2,             /* up-scales on both axes, registers only (resize_up2_kernel) */
+    PBR_RESIZE_TWO_PASS = 0,            /* width pass, height pass through the workspace (more than 36 taps per axis; csrc/resize.hip) */
+    PBR_RESIZE_STRIP = 1,               /* one kernel, tile by tile through an LDS strip (csrc/resize_strip.hpp: resize_strip_kernel) */
+    PBR_RESIZE_TWO_TAP = 2,             /* up-scales on both axes, registers only (csrc/resize.hip: resize_up2_kernel) */
     PBR_RESIZE_BAND_WALK = 3,           /* antialiased whole factors 2 ... 8 | 16, registers only (csrc/resize_down.hpp) */
     PBR_RESIZE_ROW_WALK = 4             /* other antialiased down-scales from 7 x up, i.e. 17 ... 36 taps per axis (every one from 1.01 x to 17 x with the knob PBR_TUNE_RESIZE_UP2 at 2): every input row read once (csrc/resize_stream.hpp) */
 };
@@ -624,7 +624,7 @@ int pbr_resize_form(const void *src, const void *dst, int64_t planes, int32_t h_
 
 /*
  * Gradient of pbr_resize_bilinear w.r.t. its input (autograd through base.py:490-504 -> F.interpolate): the transposed tap
- * matrices, g_in = Wy^T g_out Wx, gathered by input index in a fixed order (deterministic, no atomics).  grad_out
+ * matrices, g_in = Wy^T g_out Wx, gathered by input index in a fixed order (deterministic, no atomics; csrc/resize_backward.hip).  grad_out
  * [planes][h_out][w_out] -> grad_in [planes][h_in][w_in], fp32; `workspace`: pbr_resize_backward_workspace_bytes(...) bytes.
  */
 size_t pbr_resize_backward_workspace_bytes(int64_t planes, int32_t h_in, int32_t w_in, int32_t h_out, int32_t w_out);

@@ -1,6 +1,6 @@
 """Stand-alone map operations with their backward kernels: the colour transfers (pypbr/utils/functions.py:31-66), the
 metallic <-> specular conversions (materials/metallic.py:98-108, materials/diffuse.py:128-147) and decode_normal (materials/base.py:191-242):
-csrc/map_ops.hip; MaterialBase.resize for one map (base.py:490-504): csrc/resize.hip."""
+csrc/map_ops.hip; MaterialBase.resize for one map (base.py:490-504): csrc/resize.hip, its gradient csrc/resize_backward.hip."""
 from typing import Optional
 
 import torch

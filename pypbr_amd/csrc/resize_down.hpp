@@ -2,10 +2,10 @@
 //
 // What MaterialBase.resize (/root/reference/pypbr/materials/base.py:490-504) does to a 1024^2 / 2048^2 / 4096^2 texture on its way to
 // 512^2: torchvision's resize = F.interpolate(mode="bilinear", antialias=True), i.e. ATen's separable triangle filter of support S
-// (resize.hip's header has the rule).  With n_in = S n_out the tap pattern is the same for every output index: output i reads the
+// (resize_taps.hpp has the rule).  With n_in = S n_out the tap pattern is the same for every output index: output i reads the
 // K = 2 S inputs S i - floor(S/2) ... S i - floor(S/2) + 2 S - 1 with the triangle's weights (an odd S: the last one is 0); only the FIRST and the LAST
 // output of an axis have a clipped window (the taps that fall outside are dropped; the rest are normalised by their own sum).  So there is nothing to
-// look up: the three weight vectors (interior, first, last -- the same for both axes) are formed on the host with resize.hip's own
+// look up: the three weight vectors (interior, first, last -- the same for both axes) are formed on the host with resize_taps.hpp's
 // tap_window / tap_weight arithmetic and travel as kernel arguments, i.e. in scalar registers.
 //
 // A lane owns C consecutive output columns of a BAND of output rows and walks down the band.  It streams the input rows that feed
@@ -16,6 +16,9 @@
 // is C K fma out of registers.  No tables, no LDS strip, no barriers: the strip kernel's three barrier-separated phases per tile kept
 // it at 0.70-0.74 of HBM on these shapes with every byte read once.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
 #include <type_traits>
 
 namespace pbr {
@@ -29,6 +32,9 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 struct DownTaps { float wi[32], wl[32], wr[32]; };       // K = 2 S normalised weights of an interior output, of output 0, of the last output; zero where the window is clipped
+// The launch (defined once, in resize.hip; the gradient of a whole power-of-two up-scale, resize_backward.hip, runs the same kernel with the transposed
+// two-tap weights): `small` = the side with 1 / S^2 of the elements.  False when the shape is not the kernel's; `dry` = decide, launch nothing.
+bool launch_down(const float *large, float *small, int64_t planes, int h_small, int w_small, int S, const DownTaps &taps, hipStream_t s, bool dry = false);
 
 template <int S, int R, int C, int D, bool NT = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 4))) void resize_down_kernel(const float *__restrict__ src, float *__restrict__ dst, int h_out, int w_out,

@@ -1,8 +1,8 @@
-// resize_stream.hpp -- antialiased down-scale by ANY factor 1.01 <= s < 17 on both axes: every input row read ONCE (round 6; the rule from 7 x up: resize.hip).
+// resize_stream.hpp -- antialiased down-scale by ANY factor 1.01 <= s < 17 on both axes: every input row read ONCE (round 6; the rule from 7 x up: resize.hip, resize_forward).
 //
 // What MaterialBase.resize (/root/reference/pypbr/materials/base.py:490-504) does when the target is not a whole fraction of the
 // texture (4096^2 -> 1365^2, -> 400^2, 2048^2 -> 1000^2 ...): torchvision's resize = F.interpolate(mode="bilinear", antialias=True), ATen's
-// separable triangle filter (resize.hip's header has the rule).  resize_strip_kernel serves these shapes tile by tile: per OUTPUT row
+// separable triangle filter (resize_taps.hpp has the rule).  resize_strip_kernel serves these shapes tile by tile: per OUTPUT row
 // of a tile it loads the row's K input rows, so every input row crosses L2 -> CU about twice, a tile's halo rows (102 read for the 82
 // owned at 10.24 x) leave HBM a second time (PMC: 1.15 x), and three barrier-separated phases share a workgroup's time.
 //
@@ -20,6 +20,9 @@
 #pragma once
 #include <type_traits>
 
+#include "resize_down.hpp"      // static_for
+#include "resize_taps.hpp"
+
 namespace pbr {
 
 struct StreamGeom { int h_out, w_out, h_in, w_in, kx, kt, oc, strips, bands, band_rows; uint32_t mapped; };
@@ -31,10 +34,8 @@ __global__ __launch_bounds__(256) void resize_stream_tables_kernel(float4 *__res
     if ((int)blockIdx.x >= groups_y) {
         const int c = ((int)blockIdx.x - groups_y) * 256 + (int)threadIdx.x;
         if (c >= w_out) return;
-        int xmin, n; float center, wsum = 0.0f;
-        tap_window(fw, c, xmin, n, center);
-        for (int j = 0; j < n; ++j) wsum += tap_weight(fw, j, xmin, center);
-        const float inv = wsum != 0.0f ? 1.0f / wsum : 0.0f;
+        int xmin, n; float center;
+        const float inv = window_norm(fw, c, xmin, n, center);
         for (int j = 0; j < kx; ++j) wx[(size_t)j * w_out + c] = j < n ? tap_weight(fw, j, xmin, center) * inv : 0.0f;
         xlo[c] = xmin; xn[c] = n < kx ? n : kx;
         return;

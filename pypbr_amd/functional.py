@@ -22,7 +22,7 @@ sibling modules, one per file of csrc/, and their names are imported back below,
 
   _dispatch     what all families share: dtype codes, tensor checks, LAUNCHES, `launch` / `ptr`       (the C ABI: _native.py)
   _upload       to_host, pack_maps, upload_packed, unpack_image, pack_image, download_samples           csrc/unpack.hip, pack_image.hip
-  _map_ops      colour transfers, metallic <-> specular, resize, decode_normal                          csrc/map_ops.hip, resize.hip
+  _map_ops      colour transfers, metallic <-> specular, resize, decode_normal                          csrc/map_ops.hip, resize.hip, resize_backward.hip
   _normal_ops   normal_from_height, transform_normals                                                   csrc/normal_ops.hip
   _height_ops   height_from_normal (around torch.fft.rfft2 / irfft2)                                     csrc/height_ops.hip
   _geometry     PlaneMap, fold_stages, check_crop, remap_planes                                         csrc/geometry.hip
