@@ -291,6 +291,27 @@ int pbr_cook_torrance_backward_params(const pbr_render_desc *desc, const void *g
 size_t pbr_mse_step_workspace_bytes(const pbr_render_desc *desc);
 int pbr_cook_torrance_mse_step(const pbr_render_desc *desc, const void *target, void *g_albedo, void *g_normal, void *g_roughness,
                                void *g_metallic, void *g_specular, void *loss, void *workspace, void *stream);
+/*
+ * A light stack (an extension: upstream has no counterpart beyond the tutorial's loss applied to L photographs): the L lights of `desc`
+ * -- 1 <= L <= PBR_MAX_LIGHTS, one light type, one view direction, one light_size -- are L IMAGES, not one summed image.  Image l is exactly
+ * what pbr_cook_torrance gives for light l alone (its own clamp, its own encode).  `desc` as for pbr_cook_torrance, but `desc->out` receives
+ * [B][L][3][height][width] fp32, contiguous.  The maps are read and decoded once, the light-independent terms formed once per pixel.
+ * Untiled maps (fp32 or fp16, all workflows, both light types, device_params), out_dtype PBR_F32 (else PBR_ERR_DTYPE), both out strides 0:
+ * anything else returns PBR_ERR_UNSUPPORTED before any launch.
+ */
+int pbr_cook_torrance_stack(const pbr_render_desc *desc, void *stream);
+/*
+ * The rendering-loss step over a light stack, as one pass: loss = nn.MSELoss()(stack(predicted material), targets) and its backward, a
+ * capture being L photographs from one camera position with the light moved between the shots.  `targets` is [B][L][3][H][W] fp32
+ * contiguous; *loss (a DEVICE float) = the mean over all 3 B L H W values; every non-NULL g_* receives the gradient SUMMED over the lights,
+ * contiguous, shaped like the map, in the maps' storage type, with torch's sub-gradient conventions as pbr_cook_torrance_mse_step applies
+ * them.  Maps read once, targets once, gradients written once: 64 + 12 L bytes per pixel (fp32) against 76 L + 96 (L - 1) for L steps
+ * and autograd's accumulation.  `workspace`: the block pbr_mse_step_workspace_bytes(desc) describes (one partial sum per workgroup, then the
+ * stage sums; finished in fp64 in a fixed order: deterministic).  `desc->out` is ignored.  Tiled maps: PBR_ERR_UNSUPPORTED (there is no
+ * streamed, tiled or blended form); a NULL targets / loss / workspace: PBR_ERR_NULL_MAP.  No gradients of the lights from this form.
+ */
+int pbr_cook_torrance_mse_stack_step(const pbr_render_desc *desc, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
+                                     void *g_metallic, void *g_specular, void *loss, void *workspace, void *stream);
 /* ABI 5: view / light / intensity from DEVICE memory.  `view_dir` [3], `lights` [n_lights][3], `intensities` [intensity_rows][3] with
  * intensity_rows = 1 (one intensity for every light) or n_lights: fp32 device pointers; a NULL pointer takes that parameter from the descriptor
  * (d->view_dir / d->lights / d->intensities: host values), so only what lives on the device needs to be there.  Writes `block` (pbr_device_params_bytes() bytes,

@@ -49,6 +49,7 @@ EXPORTS = (
     "pbr_normal_divergence", "pbr_normal_divergence_backward", "pbr_poisson_scale", "pbr_height_workspace_bytes", "pbr_height_stats",
     "pbr_height_normalize", "pbr_height_normalize_backward",
     "pbr_pack_images",
+    "pbr_cook_torrance_stack", "pbr_cook_torrance_mse_stack_step",
 )
 
 
@@ -187,6 +188,10 @@ def lib():
     L.pbr_mse_step_workspace_bytes.restype = ctypes.c_size_t
     L.pbr_cook_torrance_mse_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pbr_cook_torrance_mse_step.restype = ctypes.c_int
+    L.pbr_cook_torrance_stack.argtypes = [ctypes.POINTER(RenderDesc), vp]
+    L.pbr_cook_torrance_stack.restype = ctypes.c_int
+    L.pbr_cook_torrance_mse_stack_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pbr_cook_torrance_mse_stack_step.restype = ctypes.c_int
     L.pbr_scale_by_device_scalar.argtypes = [vp, sz, ctypes.c_int, vp, vp]
     L.pbr_scale_by_device_scalar.restype = ctypes.c_int
     L.pbr_scale_list_by_device_scalar.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_int, ctypes.c_int, vp, vp]

@@ -227,12 +227,36 @@ __device__ __forceinline__ void backprop_light(const PixelTermsT<R> &t, const Li
 //   `loss`: NoLoss -- the upstream gradient is `go`, as loaded; MseLoss<VEC> -- the fused rendering-loss step (ct_loss.hip): the
 //   upstream gradient of a pixel is formed HERE from the colour the forward re-evaluation just produced, 2 (out - target) * scale,
 //   and the squared differences are summed into loss.sq.
-struct NoLoss { static constexpr bool on = false; };
+//   StackMseLoss<VEC> -- the light-stack step (ct_stack.hip): every light is an image of its own with its own target, so the one-light form
+//   (clamp, encode, difference) runs INSIDE the light loop, once per light, and the adjoints of all lights add up in the shared accumulators
+//   before the light-independent tail runs once.  `stack` selects that: the light loop runs over a.n_lights although MULTI is false.
+struct NoLoss { static constexpr bool on = false, stack = false; };
 template <int VEC> struct MseLoss {
-    static constexpr bool on = true;
+    static constexpr bool on = true, stack = false;
     float tgt[3][VEC];      // the lane's pixels of the target image
     float scale;            // 2 / N  (d mean((out - target)^2) / d out = scale * (out - target))
     float sq;               // sum of squared differences over the lane's pixels
+};
+template <int VEC> struct StackMseLoss {
+    static constexpr bool on = true, stack = true;
+    float tgt[3][VEC];      // the lane's pixels of the CURRENT light's target image
+    float scale;            // 2 / N, N = 3 B L H W
+    float sq;               // sum of squared differences over the lane's pixels and all lights
+    float nxt[3][VEC];      // ... of the NEXT light's image: loaded one light ahead, so that their latency hides behind a light's arithmetic
+    const float *lane;      // the lane's first pixel in channel 0 of light 0's image of its material: targets + b L 3 HW + pix (64-bit, by the kernel)
+    int64_t plane;          // H W: the images' channel stride; light l's image starts 3 l planes further on
+    __device__ __forceinline__ void prefetch(int l) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Ld<float, VEC>::template load<true>(lane, ((int64_t)l * 3 + c) * plane, nxt[c]);
+    }
+    // light l begins: its pixels were loaded a light ago; the next light's leave now (the last light loads its own again: in bounds, no branch)
+    __device__ __forceinline__ void begin_light(int l, int n_lights) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) tgt[c][j] = nxt[c][j];
+        prefetch(l + 1 < n_lights ? l + 1 : l);
+    }
 };
 
 #ifndef PBR_MSE_PACKED
@@ -309,7 +333,7 @@ __device__ __forceinline__ void backward_body_to(const KArgs &a, const BArgs &b,
 
         // ---- adjoint of the linear colour before per-light clamps
         R g_col[3];
-        const int nl = MULTI ? a.n_lights : 1;
+        const int nl = (MULTI || Loss::stack) ? a.n_lights : 1;
         if (MULTI) {                                 // pass 1: the summed colour decides the outer clamp / encode slope
             R sum[3] = {splat<R>(0.0f), splat<R>(0.0f), splat<R>(0.0f)};
             for (int l = 0; l < nl; ++l) {
@@ -337,6 +361,7 @@ __device__ __forceinline__ void backward_body_to(const KArgs &a, const BArgs &b,
         for (int l = 0; l < nl; ++l) {
             const LightU lu = light_of(a, l);
             const LightGeomT<R> lg = light_geom<LIGHT, R>(lu, V, xs, ys);
+            if constexpr (Loss::stack) loss.begin_light(l, nl);
             LightEvalT<R> e;
             eval_light(pt, lg, lu.inten, e);
             if (!MULTI) {

@@ -1,5 +1,5 @@
 // ct_launch.hpp -- host side shared by the launchers of the render kernels (cook_torrance.hip, ct_batch.hip, ct_tiled.hip,
-// ct_backward.hip, ct_repeat_backward.hip, ct_blend.hip, ct_loss.hip): descriptor validation, the light x workflow dispatch
+// ct_backward.hip, ct_repeat_backward.hip, ct_blend.hip, ct_loss.hip, ct_stack.hip): descriptor validation, the light x workflow dispatch
 // (with_light_workflow), the 16-byte-path test, the workgroup-order rule and the translation of a pbr_render_desc into the
 // kernel-argument block.  Launch status, alignment test and CU count: launch_util.hpp (through stream_shape.hpp).  Tuning knobs
 // live in cook_torrance.hip (pbr_set_tuning).
@@ -282,6 +282,11 @@ int launch_repeat_backward(const pbr_render_desc *d, const void *upstream, void 
 // pbr_cook_torrance_blend_backward over tiled maps through the same walk (ct_repeat_backward.hip); kblend / g1 / g2: KBlend / BArgs / BBlend by address
 bool repeat_blend_backward_serves(const pbr_render_desc *d);
 int launch_repeat_blend_backward(const pbr_render_desc *d, const void *kblend, const void *grad_out, const void *g1, const void *g2, hipStream_t st);
+
+// ct_loss.hip, shared with the light-stack step (ct_stack.hip): pixels per lane of a loss step (no lane may count a pixel twice), and the step's
+// partial sums -> *loss = sum / count through the two reduction kernels (fp64, fixed order), the stage sums where pbr_mse_step_workspace_bytes put them
+int mse_vec(const pbr_render_desc *d);
+int mse_finish(const pbr_render_desc *d, float *partials, int64_t n_partials, double count, float *loss, hipStream_t st);
 
 // The repeat-inner kernels (cook_torrance_repeat_kernel, cook_torrance_repeat_backward_kernel) serve every tiled launch whose map rows hold a
 // 4-texel lane: the whole tiled image or a row band of it (a multi-GPU shard) of ANY height -- a band thinner than a period walks the window

@@ -164,7 +164,7 @@ int stream_run(const pbr_render_desc *d, const void *grad_out, void *const g[5])
 // four: with the target pixels on top the four-pixel body needs 256 VGPRs + 21 AGPRs (one wave per SIMD; held to two waves it
 // spills 72-88 bytes), and measured on a 4096^2 material it loses -- point light 295 against 228 us, directional 225 against 219
 // (tools/loss_step_probe.py, round 3).
-static int mse_vec(const pbr_render_desc *d) { return g_max_vec == 1 || (d->width & 1) ? 1 : 2; }
+int mse_vec(const pbr_render_desc *d) { return g_max_vec == 1 || (d->width & 1) ? 1 : 2; }
 
 // workspace: the step kernel's partial sums (fp32, one per workgroup), then kMseStageGroups stage sums (fp64, 8-byte aligned)
 static size_t mse_stage_offset(size_t tiles) { return (tiles * sizeof(float) + 7) & ~(size_t)7; }
@@ -189,6 +189,11 @@ static int finish_mse(float *partials, int64_t n_partials, StageTiles &&stage_of
         hipLaunchKernelGGL(mse_finish_kernel, dim3(1), dim3(256), 0, st, stage, 1.0 / count, loss);
     }
     return launch_status();
+}
+
+// For the light-stack step (ct_stack.hip): the same two reduction kernels over ITS partial sums, the stage block at the same place.
+int mse_finish(const pbr_render_desc *d, float *partials, int64_t n_partials, double count, float *loss, hipStream_t st) {
+    return finish_mse(partials, n_partials, [&] { return mse_tiles(d, 1); }, count, loss, st);
 }
 
 }  // namespace pbr

@@ -1,0 +1,188 @@
+// ct_stack.hip -- a light stack: L images of one material batch, one per light, out of ONE pass over the maps
+// (C ABI: pbr_cook_torrance_stack, pbr_cook_torrance_mse_stack_step).
+//
+// A capture for SVBRDF fitting is a stack of photographs from one camera position with the light moved between the shots (a flash walked
+// around a tripod, a light stage, photometric stereo); the loss is the mean squared error over ALL images.  Image l of the stack is exactly
+// what the one-light evaluation gives for light l alone -- every image has its own clamp and its own encode -- which is not what the
+// several-lights kernels compute: they sum the lights into one image.
+//
+// Layout: the stack is [B][L][3][H][W] fp32, contiguous; the lights share the view direction, the light type and light_size.
+//
+// Bytes per pixel (fp32 maps, metallic workflow).  L one-light loss steps read the eight map planes L times (32 L), their targets (12 L), write
+// eight gradient planes L times (32 L), and autograd adds the L gradient sets up (read, read, write over 32 B for every light after the first):
+// 76 L + 96 (L - 1).  Here the maps are read once, the L targets once, and the summed gradients are written once: 64 + 12 L.  At L = 8 that is
+// 160 against 1280.
+//
+// The step is backward_body_to (ct_backward.hpp) with the StackMseLoss policy: texels loaded and decoded once, pixel_terms once, then per light
+// eval_light -> encode with slope -> difference to THAT light's target -> backprop_light into the shared accumulators, and the light-independent
+// tail and the stores once.  No second pass over the lights: the summed-lights form needs one because the summed colour decides the outer clamp;
+// in a stack every image is clamped and encoded by itself.  Light l + 1's target pixels are loaded before light l's arithmetic.
+#include "ct_backward.hpp"
+#include "ct_launch.hpp"
+
+namespace pbr {
+
+// ------------------------------------------------------------------ forward: the stack itself
+// The several-lights branch of shade_and_store (ct_kernel.hpp) with the sum taken out: lights in the outer (uniform) loop, the lane's pixel
+// groups inside it, and each light's clamped colour (shade_light clamps) encoded and stored to its own image.  Packed arithmetic, as for
+// several lights everywhere; a.o_bs is the MATERIAL's stride in the stack (3 L planes), a.o_cs the plane.
+template <int LIGHT, int WF, typename TI, int VEC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8)))
+void cook_torrance_stack_kernel(const KArgs a) {
+    using R = typename RealOf<VEC, true>::type;
+    constexpr int NG = RealOf<VEC, true>::N;
+    const uint32_t tile = tile_of_workgroup(a, blockIdx.x);
+    const int ty = (int)a.div_tx.div(tile);
+    const LanePos p = lane_pos<VEC>(a, (int)tile - ty * a.tiles_x, ty);
+    if (!p.valid) return;
+    Texels<VEC> t;
+    load_texels<WF, TI, VEC, VEC != 1>(a, a.has_normal != 0, p, t);
+    decode_texels<WF, VEC, true>(a, t);
+    const Vec3 V = view_of(a);
+    float ys = 0.0f;
+    R xs[NG];
+    if (LIGHT == PBR_LIGHT_POINT) {
+        ys = linspace_at(a.y0, a.y1, a.ystep, a.H_total, p.y + a.y_offset);
+        x_grid<R, NG, VEC>(a, p.x, xs);
+    } else {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) xs[g] = splat<R>(0.0f);
+    }
+    PixelTermsT<R> pt[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) material_terms<WF, VEC, R>(t, g, V, pt[g]);
+    float *const first = static_cast<float *>(a.out) + ((int64_t)p.b * a.o_bs + p.pix);      // channel 0 of light 0's image, this lane's pixels
+    for (int l = 0; l < a.n_lights; ++l) {
+        const LightU lu = light_of(a, l);
+        R res[3][NG];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const LightGeomT<R> lg = light_geom<LIGHT, R>(lu, V, xs[g], ys);
+            R col[3];
+            shade_light(pt[g], lg, lu.inten, col);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) res[c][g] = a.out_srgb ? linear_to_srgb_unit(col[c]) : col[c];      // :179-180
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float o[VEC];
+#pragma unroll
+            for (int g = 0; g < NG; ++g) scatter(o, g, res[c][g]);
+            Ld<float, VEC>::template store<VEC != 1>(first, ((int64_t)l * 3 + c) * a.o_cs, o);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ the loss step over the stack
+// One-wave workgroups like cook_torrance_mse_step_kernel: one partial sum per workgroup, no LDS.  Lanes outside the map shade a clamped
+// position (every lane reaches the wave sum), store nothing and contribute nothing.
+// Registers: the two-pixel body lands on 184-216 VGPRs (two waves per SIMD), the one-pixel body on 95-114 (four); held to three waves (168)
+// every two-pixel instantiation spills 28-176 bytes per lane, so the allocation is left to the compiler.
+template <int LIGHT, int WF, int VEC, typename TM>
+__global__ __launch_bounds__(64)
+void cook_torrance_mse_stack_step_kernel(const KArgs a, const BArgs b, const float *__restrict__ targets, float scale, float *__restrict__ partials) {
+    const uint32_t tile = tile_of_workgroup(a, blockIdx.x);
+    const int ty = (int)a.div_tx.div(tile);
+    const LanePos p = lane_pos<VEC, true>(a, (int)tile - ty * a.tiles_x, ty);
+    // one pixel group per lane (a packed pair or one pixel): the body's light loop runs once, so the one-light-ahead target loads stay in step
+    static_assert(VEC == 1 || (VEC == 2 && PBR_MSE_PACKED), "StackMseLoss walks the lights once per lane");
+    Texels<VEC> t;
+    StackMseLoss<VEC> loss;
+    loss.scale = scale;
+    loss.sq = 0.0f;
+    loss.plane = a.o_cs;
+    loss.lane = targets + ((int64_t)p.b * a.n_lights * 3 * a.o_cs + p.pix);       // 64-bit: B L 3 H W passes 2^31 long before a plane does
+    float go[3][VEC];                                                              // unused by the loss policies
+    if constexpr (sizeof(TM) == 4) {
+        load_texels<WF, TM, VEC, true>(a, a.has_normal != 0, p, t);
+    } else if (p.sb) {
+        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, true, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, true, false>(a, p, t);
+    } else {
+        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, false, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, false, false>(a, p, t);
+    }
+    loss.prefetch(0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) go[c][j] = 0.0f;
+    backward_body_to<LIGHT, WF, VEC, false, TM, false>(a, b, p, t, go, nullptr, 0,
+        [&](float (&ga)[3][VEC], float (&gn)[3][VEC], float (&gr)[VEC], float (&gm)[VEC], float (&gs)[3][VEC]) {
+            if (p.valid) store_gradients<WF, VEC, TM>(a, b, p, ga, gn, gr, gm, gs);
+        }, loss);
+    const float mine = p.valid ? loss.sq : 0.0f;
+    const float total = wave_sum(mine);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
+using StackStepFn = void (*)(const KArgs, const BArgs, const float *, float, float *);
+
+template <int L, int W>
+static StackStepFn pick_stack_step(bool half_maps, int vec) {
+    if (half_maps) return vec == 2 ? cook_torrance_mse_stack_step_kernel<L, W, 2, __half> : cook_torrance_mse_stack_step_kernel<L, W, 1, __half>;
+    return vec == 2 ? cook_torrance_mse_stack_step_kernel<L, W, 2, float> : cook_torrance_mse_stack_step_kernel<L, W, 1, float>;
+}
+
+template <int L, int W>
+static KernelFn pick_stack(bool half_maps, int vec) {
+    if (half_maps) return vec == 4 ? cook_torrance_stack_kernel<L, W, __half, 4> : cook_torrance_stack_kernel<L, W, __half, 1>;
+    return vec == 4 ? cook_torrance_stack_kernel<L, W, float, 4> : cook_torrance_stack_kernel<L, W, float, 1>;
+}
+
+// What both entry points serve: untiled maps, an fp32 stack, contiguous.
+static int stack_serves(const pbr_render_desc *d) {
+    if (d->out_dtype != PBR_F32) return PBR_ERR_DTYPE;
+    if (is_tiled(d) || d->out_batch_stride != 0 || d->out_channel_stride != 0) return PBR_ERR_UNSUPPORTED;
+    return PBR_OK;
+}
+
+}  // namespace pbr
+
+extern "C" {
+
+int pbr_cook_torrance_stack(const pbr_render_desc *d, void *stream) {
+    using namespace pbr;
+    const TuningScope tuning(d);
+    int rc = validate(d);
+    if (rc == PBR_OK) rc = stack_serves(d);
+    if (rc != PBR_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t plane = (int64_t)d->height * d->width;
+    if (nan_light_size(d))       // every value of every image is NaN upstream (ct_launch.hpp: fill_result_nan); the stack is one contiguous block
+        return call_status(hipMemsetD32Async((hipDeviceptr_t)d->out, 0x7fc00000, (size_t)(plane * 3 * d->n_lights * d->batch), st));
+    const int vec = (g_max_vec == 1 || d->width < 4) ? 1 : 4;       // ragged widths: the last lane of a row overlaps its neighbour (lane_pos)
+    KArgs k;
+    fill_args(d, vec, k);
+    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
+    k.o_cs = plane; k.o_bs = 3 * plane * d->n_lights;
+    const bool half_maps = d->map_dtype == PBR_F16;
+    const KernelFn fn = with_light_workflow(d, [&](auto L, auto W) -> KernelFn { return pick_stack<L(), W()>(half_maps, vec); });
+    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), 0, st, k);
+    return launch_status();
+}
+
+int pbr_cook_torrance_mse_stack_step(const pbr_render_desc *d, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
+                                     void *g_metallic, void *g_specular, void *loss, void *workspace, void *stream) {
+    using namespace pbr;
+    const TuningScope tuning(d);
+    int rc = validate(d);
+    if (rc != PBR_OK) return rc;
+    if (!targets || !loss || !workspace) return PBR_ERR_NULL_MAP;
+    if (d->out_dtype != PBR_F32) return PBR_ERR_DTYPE;        // the target images and the colours they are compared with are fp32
+    if (is_tiled(d) || nan_light_size(d)) return PBR_ERR_UNSUPPORTED;
+    const int vec = mse_vec(d);                               // two pixels per lane for even widths, else one: no lane counts a pixel twice
+    KArgs k;
+    fill_args(d, vec, k, 6);                                  // one-wave workgroups: one partial sum per workgroup
+    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
+    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;     // gradient planes are contiguous; the targets' strides follow from o_cs and n_lights
+    const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *const partials = static_cast<float *>(workspace);
+    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
+    const bool half_maps = d->map_dtype == PBR_F16;
+    const StackStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> StackStepFn { return pick_stack_step<L(), W()>(half_maps, vec); });
+    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(targets), (float)(2.0 / count), partials);
+    const int e = launch_status();
+    return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
+}
+
+}  // extern "C"

@@ -28,7 +28,8 @@ sibling modules, one per file of csrc/, and their names are imported back below,
   _geometry     PlaneMap, fold_stages, check_crop, remap_planes                                         csrc/geometry.hip
   _packing      unpack_planes, pack_planes, the plane-op tables                                         csrc/packing.hip
   _rotate_ops   rotate_plan, rotate_indices, rotate_maps                                                csrc/rotation.hip
-  functional    descriptors, RenderPlan, cook_torrance, the autograd bridges, rendering_loss_mse        csrc/ct_*.hip/.hpp, torch_ops.cpp
+  functional    descriptors, RenderPlan, cook_torrance, the autograd bridges, rendering_loss_mse,       csrc/ct_*.hip/.hpp, torch_ops.cpp
+                light stacks (cook_torrance_stack, rendering_loss_mse_stack)
 
 Imports run one way: _native / _caches -> _dispatch -> _upload -> the family modules -> functional.
 """
@@ -795,6 +796,17 @@ class _StepNotServed(Exception):
     """pbr_cook_torrance_mse_step does not serve this descriptor as one pass (raised before anything is launched)."""
 
 
+def _scale_step_gradients(grads, grad_loss):
+    """The gradients a loss step kept, times the upstream gradient of the loss, in place: ONE launch for all of them (they share a dtype and
+    a device), on the device (pbr_scale_list_by_device_scalar: no host synchronisation, an early-out when the scalar is exactly 1)."""
+    live = [b for b in grads if b is not None]
+    if live:
+        k = grad_loss.detach().to(live[0].device, torch.float32).reshape(1).contiguous()
+        ptrs = (ctypes.c_void_p * len(live))(*[b.data_ptr() for b in live])
+        counts = (ctypes.c_size_t * len(live))(*[b.numel() for b in live])
+        launch(live[0].device, N.lib().pbr_scale_list_by_device_scalar, ptrs, counts, len(live), _DTYPES[live[0].dtype], k.data_ptr())
+
+
 class _MseStepFn(torch.autograd.Function):
     """loss = mean((cook_torrance(maps) - target)^2) with its gradients from ONE kernel (pbr_cook_torrance_mse_step): forward
     evaluates, compares and differentiates in a single pass over the maps (32 + 12 bytes read, 32 written per pixel) and keeps
@@ -910,12 +922,7 @@ class _MseStepFn(torch.autograd.Function):
             plan = plan_cook_torrance(*[None if t is None else t.detach() for t in maps], **ctx.kwargs)
             plan.out = None
             _, grads = _MseStepFn._launch(plan, saved[-1], maps, ctx.wanted)
-        live = [b for b in grads if b is not None]
-        if live:                                            # all gradients scaled in ONE launch (they share a dtype and a device)
-            k = grad_loss.detach().to(live[0].device, torch.float32).reshape(1).contiguous()
-            ptrs = (ctypes.c_void_p * len(live))(*[b.data_ptr() for b in live])
-            counts = (ctypes.c_size_t * len(live))(*[b.numel() for b in live])
-            launch(live[0].device, N.lib().pbr_scale_list_by_device_scalar, ptrs, counts, len(live), _DTYPES[live[0].dtype], k.data_ptr())
+        _scale_step_gradients(grads, grad_loss)
         return (*grads, None, None)
 
 
@@ -945,3 +952,142 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
             pass
     out = cook_torrance(albedo, normal, roughness, metallic, specular, **kwargs)
     return torch.nn.functional.mse_loss(out.float(), target.to(out.device, torch.float32).reshape(out.shape))
+
+
+# ------------------------------------------------------------------ light stacks: L images, one per light, out of one pass over the maps
+# An extension over the reference (csrc/ct_stack.hip): a capture for SVBRDF fitting is a stack of photographs from ONE camera position with the
+# light moved between the shots; image l of the stack is what `cook_torrance` gives for light l alone, and the loss is the MSE over all of them.
+STACK_LAUNCHES = {"cook_torrance_stack": 0, "mse_stack_step": 0}       # calls of the two stack entry points (the tests count launches)
+
+
+def _stack_lights(light, light_intensity) -> Tuple[int, int]:
+    """(L, intensity rows) of a light stack, from shapes alone -- no device work, no read-back.  Raises ValueError for anything but
+    1..MAX_LIGHTS lights of 3 components and 1 or L intensity rows."""
+    def rows(v, name):
+        n = v.numel() if isinstance(v, torch.Tensor) else torch.as_tensor(v, dtype=torch.float32).numel()
+        if n == 0 or n % 3:
+            raise ValueError("%s must be [3] or [L,3], got %d values" % (name, n))
+        return n // 3
+    L, R = rows(light, "light"), rows(light_intensity, "light_intensity")
+    if L > N.MAX_LIGHTS:
+        raise ValueError("a light stack holds between 1 and %d lights, got %d" % (N.MAX_LIGHTS, L))
+    if R not in (1, L):
+        raise ValueError("light_intensity must have 1 row or one per light (%d), got %d" % (L, R))
+    return L, R
+
+
+def _stack_plain(kw) -> bool:
+    """The keyword arguments of a call that pbr_cook_torrance_stack / pbr_cook_torrance_mse_stack_step serve: whole untiled maps, a fresh fp32 result."""
+    return (all(kw.get(k) is None for k in ("out", "blend", "blend_flags", "rows", "height_total")) and not kw.get("y_offset") and not kw.get("autotune")
+            and kw.get("out_dtype") in (None, torch.float32) and kw.get("tile", 1) in (1, (1, 1)))
+
+
+def cook_torrance_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], roughness: torch.Tensor,
+                        metallic: Optional[torch.Tensor] = None, specular: Optional[torch.Tensor] = None, *,
+                        view_dir: TensorLike, light: TensorLike, light_intensity: TensorLike, **kwargs) -> torch.Tensor:
+    """The L images of a light stack: `light` [L,3] (1 <= L <= 16, one light type, one view direction, one light_size), `light_intensity` [3] /
+    [1,3] for all lights or [L,3]; image l is exactly `cook_torrance(..., light=light[l], light_intensity=light_intensity[l])`.  Returns
+    [L,3,H,W], or [B,L,3,H,W] for batched maps, float32.  ONE launch (pbr_cook_torrance_stack: maps read and decoded once, the
+    light-independent terms formed once per pixel) when nothing requires grad and the maps are whole and untiled; otherwise -- gradients, `tile`,
+    `out_dtype` ... -- a torch.stack of L `cook_torrance` calls, differentiable like them.  Other keyword arguments as for `cook_torrance`."""
+    L, rows = _stack_lights(light, light_intensity)
+    if kwargs.get("out") is not None:
+        raise ValueError("cook_torrance_stack allocates its result: out= is not supported")
+    maps = (albedo, normal, roughness, metallic, specular)
+    if (_stack_plain(kwargs) and isinstance(albedo, torch.Tensor) and albedo.is_cuda and albedo.dim() in (3, 4) and albedo.numel() > 0
+            and not _needs_grad(*maps, view_dir, light, light_intensity)):
+        kw = {k: v for k, v in kwargs.items() if k in ("light_type", "light_size", "albedo_is_srgb", "specular_is_srgb", "return_srgb",
+                                                       "convert_to_diffuse_specular", "schedule", "tuning")}
+        B = 1 if albedo.dim() == 3 else albedo.shape[0]
+        stack = torch.empty((B, L, 3) + tuple(albedo.shape[-2:]), dtype=torch.float32, device=albedo.device)
+        # the plan describes ONE image per material; as `out` it gets the head of the stack's block -- contiguous, so the descriptor carries the
+        # block's address and no strides -- and the stack's entry point spaces the materials 3 L planes apart itself
+        plan = plan_cook_torrance(albedo, normal, roughness, metallic, specular, view_dir=view_dir, light=light, light_intensity=light_intensity,
+                                  out=stack.view(B * L, 3, *stack.shape[-2:])[:B], **kw)
+        launch(plan.device, N.lib().pbr_cook_torrance_stack, ctypes.byref(plan.desc))
+        STACK_LAUNCHES["cook_torrance_stack"] += 1
+        return stack[0] if albedo.dim() == 3 else stack
+    lt = (light if isinstance(light, torch.Tensor) else torch.as_tensor(light, dtype=torch.float32)).reshape(-1, 3)
+    it = (light_intensity if isinstance(light_intensity, torch.Tensor) else torch.as_tensor(light_intensity, dtype=torch.float32)).reshape(-1, 3)
+    images = [cook_torrance(albedo, normal, roughness, metallic, specular, view_dir=view_dir, light=lt[l], light_intensity=it[l if rows > 1 else 0],
+                            **kwargs) for l in range(L)]
+    return torch.stack(images, dim=-4)
+
+
+class _MseStackStepFn(torch.autograd.Function):
+    """loss = mean((cook_torrance_stack(maps) - targets)^2) with the gradients of the maps, summed over the lights, from ONE kernel
+    (pbr_cook_torrance_mse_stack_step): 64 + 12 L bytes per pixel instead of L loss steps and autograd's accumulation.  Forward keeps the
+    gradients, backward hands them over scaled by the upstream gradient on the device; a second backward evaluates again -- as _MseStepFn."""
+
+    @staticmethod
+    def _launch(maps, targets, kwargs, wanted):
+        plan = plan_cook_torrance(*[None if t is None else t.detach() for t in maps], **kwargs)
+        plan.out = None                                     # the colours are never written
+        d = plan.desc
+        dev = plan.device
+        tgt = targets.detach().to(dev, torch.float32).reshape(d.batch, d.n_lights, 3, d.height, d.width).contiguous()
+        gdtype = torch.float32 if d.map_dtype == N.F32 else torch.float16
+        present = (True, bool(d.normal.data), True, bool(d.metallic.data), bool(d.specular.data))
+        bufs = [torch.empty(tuple(maps[i].shape), dtype=gdtype, device=dev) if wanted[i] and present[i] else None for i in range(5)]
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        lib = N.lib()
+        ws_bytes = lib.pbr_mse_step_workspace_bytes(ctypes.byref(d))
+        if ws_bytes == 0:
+            raise _StepNotServed()
+        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=dev)
+        launch(dev, lib.pbr_cook_torrance_mse_stack_step, ctypes.byref(d), tgt.data_ptr(), *[ptr(b) for b in bufs], loss.data_ptr(), ws.data_ptr())
+        STACK_LAUNCHES["mse_stack_step"] += 1
+        return loss, bufs
+
+    @staticmethod
+    def forward(ctx, albedo, normal, roughness, metallic, specular, targets, kwargs):
+        maps = (albedo, normal, roughness, metallic, specular)
+        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
+        loss, bufs = _MseStackStepFn._launch(maps, targets, kwargs, wanted)
+        ctx.kwargs, ctx.wanted, ctx.grads = kwargs, wanted, bufs
+        ctx.present = [t is not None for t in maps]
+        ctx.save_for_backward(*[t for t in maps if t is not None], targets)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        saved = ctx.saved_tensors                           # in-place edits of the maps since forward are detected, as for any op
+        grads = ctx.grads
+        ctx.grads = None                                    # handed over below: autograd may keep the very buffers
+        if grads is None:                                   # differentiated again: the first call gave its buffers away
+            it = iter(saved[:-1])
+            maps = [next(it) if p else None for p in ctx.present]
+            _, grads = _MseStackStepFn._launch(maps, saved[-1], ctx.kwargs, ctx.wanted)
+        _scale_step_gradients(grads, grad_loss)
+        return (*grads, None, None)
+
+
+def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], roughness: torch.Tensor,
+                             metallic: Optional[torch.Tensor] = None, specular: Optional[torch.Tensor] = None, *,
+                             targets: torch.Tensor, **kwargs) -> torch.Tensor:
+    """`torch.nn.MSELoss()(cook_torrance_stack(albedo, normal, roughness, metallic | specular, **kwargs), targets)`: the rendering loss over a
+    stack of L photographs `targets` [L,3,H,W] / [B,L,3,H,W], as a 0-dim tensor on the maps' device; the gradient of each map is the sum over
+    the lights.  ONE pass over the maps (pbr_cook_torrance_mse_stack_step) under the conditions `rendering_loss_mse` uses -- a map requires
+    grad, light / view / targets do not, plain arguments, every map with its own planes, on a ROCm device -- and untiled maps; every other case
+    (tiled maps, maps shared by the batch, a light being fitted, no gradients wanted) is the stack followed by torch's MSE: same value to
+    fp32 rounding, same gradients, and a light being fitted receives its gradient."""
+    L, _ = _stack_lights(kwargs.get("light"), kwargs.get("light_intensity"))
+    if not isinstance(albedo, torch.Tensor) or albedo.dim() not in (3, 4):
+        raise ValueError("albedo must be [3,H,W] or [B,3,H,W]")
+    ny, nx = tile_counts(kwargs.get("tile", 1))
+    H = int(kwargs["rows"]) if kwargs.get("rows") is not None else ny * albedo.shape[-2] - (int(kwargs.get("y_offset") or 0) if (ny, nx) != (1, 1) else 0)
+    want = ((L, 3, H, nx * albedo.shape[-1]) if albedo.dim() == 3 else (albedo.shape[0], L, 3, H, nx * albedo.shape[-1]))
+    if not isinstance(targets, torch.Tensor) or tuple(targets.shape) != want:
+        raise ValueError("targets must be the stack %s, got %s" % (want, tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets)))
+    maps = (albedo, normal, roughness, metallic, specular)
+    params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
+    B = albedo.shape[0] if albedo.dim() == 4 else 1
+    shared = any(t is not None and B > 1 and (t.dim() == 3 or t.shape[0] == 1) for t in maps)
+    if _needs_grad(*maps) and not _needs_grad(*params, targets) and _stack_plain(kwargs) and not shared and albedo.is_cuda:
+        kw = {k: v for k, v in kwargs.items() if k not in ("out", "blend", "blend_flags", "out_dtype", "autotune", "rows", "height_total", "y_offset", "tile")}
+        try:
+            return _MseStackStepFn.apply(albedo, normal, roughness, metallic, specular, targets, kw)
+        except _StepNotServed:
+            pass
+    out = cook_torrance_stack(albedo, normal, roughness, metallic, specular, **kwargs)
+    return torch.nn.functional.mse_loss(out.float(), targets.to(out.device, torch.float32))

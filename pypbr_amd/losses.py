@@ -66,3 +66,67 @@ class RenderingLoss(nn.Module):
                                      tile=predicted_material.lazy_tile,      # a recorded tile(n): evaluated and differentiated at every repeat
                                      albedo_is_srgb=bool(predicted_material.albedo_is_srgb),
                                      specular_is_srgb=bool(getattr(predicted_material, "specular_is_srgb", True)))
+
+
+class MultiLightRenderingLoss(nn.Module):
+    """The same loss over a LIGHT STACK (an extension: upstream has only the tutorial's loss, applied here to L images): a capture of L
+    photographs from one camera position with the light moved between the shots.  `lights` [L,3] (1 <= L <= 16, one light type),
+    `light_intensities` [3] / [1,3] for all lights or [L,3], one `view_dir`, one `light_size`.  The loss is nn.MSELoss() over the L renderings
+    of the predicted material against `ground_truth` -- a material, rendered with ONE launch (functional.cook_torrance_stack), or the stack
+    of photographs itself ([L,3,H,W] / [B,L,3,H,W]).  When the ground truth is rendered differentiably, and when the predicted material takes
+    the one-pass form (functional.rendering_loss_mse_stack -> pbr_cook_torrance_mse_stack_step), follows RenderingLoss's rules."""
+
+    def __init__(self, light_type='point', view_dir=torch.tensor([0.0, 0.0, 1.0]), lights=torch.tensor([[0.1, 0.1, 1.0]]),
+                 light_intensities=torch.tensor([1.0, 1.0, 1.0]), light_size=None):
+        super().__init__()
+        self.n_lights, self._rows = F_._stack_lights(lights, light_intensities)          # ValueError before any device work
+        self.brdf = CookTorranceBRDF(light_type=light_type)
+        self.view_dir = view_dir
+        self.lights = lights
+        self.light_intensities = light_intensities
+        self.light_size = light_size
+
+    def _kwargs(self, material):
+        return dict(view_dir=self.view_dir, light=self.lights, light_intensity=self.light_intensities, light_type=self.brdf.light_type,
+                    light_size=self.light_size, tile=material.lazy_tile, albedo_is_srgb=bool(material.albedo_is_srgb),
+                    specular_is_srgb=bool(getattr(material, "specular_is_srgb", True)))
+
+    def _plain_maps(self, material):
+        """The five maps of a material the stack's entry points can read in place (RenderingLoss's `fusable`), else None."""
+        a, n, r, m, s = RenderingLoss._maps(material)
+        ok = (material.__dict__.get("_lazy_blend") is None
+              and torch.device(material.device).type == "cuda" and not material._has_pending()
+              and a is not None and r is not None and "normal" in material.__dict__.get("_store", {})
+              and (m is not None or s is not None) and all(t is None or t.is_cuda for t in (a, n, r, m, s))
+              and self.brdf.override_device is None)
+        return (a, n, r, m, None if m is not None else s) if ok else None
+
+    def _render(self, material):
+        """[L,3,H,W] / [B,L,3,H,W]: one launch where the maps can be read in place, else L calls of the BRDF module (CPU-resident maps,
+        a lazy blend, maps not yet decoded: whatever the module handles)."""
+        maps = self._plain_maps(material)
+        if maps is not None:
+            return F_.cook_torrance_stack(*maps, **self._kwargs(material))
+        lt = torch.as_tensor(self.lights, dtype=torch.float32).reshape(-1, 3)
+        it = torch.as_tensor(self.light_intensities, dtype=torch.float32).reshape(-1, 3)
+        return torch.stack([self.brdf(material, self.view_dir, lt[l], it[l if self._rows > 1 else 0], self.light_size)
+                            for l in range(self.n_lights)], dim=-4)
+
+    def forward(self, predicted_material, ground_truth):
+        """`ground_truth`: a material, or the stack of photographs ([L,3,H,W] / [B,L,3,H,W] tensor)."""
+        if isinstance(ground_truth, torch.Tensor):
+            targets = ground_truth
+        else:
+            gt_maps = list(ground_truth.__dict__.get("_store", {}).values())
+            pending = ground_truth.__dict__.get("_lazy_blend")
+            if pending is not None:
+                gt_maps += list(pending[0].values()) + [pending[1]]
+            differentiable = torch.is_grad_enabled() and any(
+                isinstance(t, torch.Tensor) and t.requires_grad for t in gt_maps + [self.view_dir, self.lights, self.light_intensities])
+            with torch.enable_grad() if differentiable else torch.no_grad():
+                targets = self._render(ground_truth)
+        maps = self._plain_maps(predicted_material)
+        if maps is None:
+            rendered = self._render(predicted_material)
+            return nn.MSELoss()(rendered, targets.to(rendered.device))
+        return F_.rendering_loss_mse_stack(*maps, targets=targets.to(maps[0].device), **self._kwargs(predicted_material))
