@@ -24,6 +24,12 @@ asserted to, so an fp32 evaluation cannot be on the other side.  Two readings th
     is settled by the agreement of the oracle's own float32 and float64 gradients (`well_conditioned`).
 
 All map values are exactly representable in fp16, so fp16 and fp32 kernels and the float64 oracle see the same inputs.
+
+STACK MODE (build(..., stack=True), STACK_ENTRY_CONFIGS; held by tests/test_light_stack_branches_host.py, run on the GPU by
+tests/test_gpu_light_stack_branches.py): the same inputs read as a LIGHT STACK (csrc/ct_stack.hip) -- L images, image l being the
+one-light evaluation for light l alone.  `render` gives [L,3,H,W], `gradients` differentiates the MSE over the stack (or sum(stack * W)),
+and `decisions` lists one encode knee per light (that light's own clamped colour) and no summed colour.  `split_lights`, stack mode
+only, puts three lights on different sides of the surface, so that the set of lit lights changes from pixel to pixel.
 """
 import functools
 import math
@@ -39,6 +45,7 @@ KNEE_DECODE, KNEE_ENCODE = 0.04045, 0.0031308
 ALBEDO_VALUES = (-0.2, 0.01, 0.03, 0.06, 0.5, 0.97, 1.3)
 
 CASE_NAMES = ("backlit", "backview", "half_clamp", "saturated", "dark", "albedo_range", "closed_ends")
+STACK_CASE_NAMES = CASE_NAMES + ("split_lights",)          # `split_lights` exists in stack mode only
 
 # name -> the variants of the case that the tests run (keyword arguments of `build`)
 VARIANTS = {
@@ -54,6 +61,7 @@ VARIANTS = {
         dict(workflow="converted", quirk=True, albedo_is_srgb=True), dict(workflow="converted", quirk=False, albedo_is_srgb=True),
         dict(workflow="converted", quirk=True, albedo_is_srgb=False))],
     "closed_ends": [dict()],
+    "split_lights": [dict(return_srgb=True), dict(return_srgb=False)],
 }
 
 
@@ -75,9 +83,34 @@ ENTRY_CONFIGS = {
 }
 
 
+# Stack mode: (h, w, light type, lights, fp16 maps) of every entry point of the LIGHT STACK (csrc/ct_stack.hip) -- the smallest shapes at
+# which the angle grid still fills every branch of every case to 10 %
+STACK_ENTRY_CONFIGS = {
+    "stack-pairs": (24, 40, "directional", 3, False),         # two pixels per lane in the step, four-pixel lanes in the forward
+    "stack-pairs-point": (24, 40, "point", 3, False),         # the x grid and row position per light
+    "stack-one-pixel": (23, 37, "point", 3, False),           # odd width: one pixel per lane in the step, the forward's overlapping last lane
+    "stack-fp16": (16, 64, "directional", 3, True),           # the __half instantiations
+    "stack-fp16-point": (16, 64, "point", 3, True),
+}
+
+
 def build_for(entry, name, kw, seed=0):
+    if entry in STACK_ENTRY_CONFIGS:
+        h, w, light_type, n_lights, _ = STACK_ENTRY_CONFIGS[entry]
+        return build(name, h, w, light_type=light_type, n_lights=n_lights, seed=seed, stack=True, **kw)
     h, w, light_type, n_lights, tile = ENTRY_CONFIGS[entry]
     return build(name, h, w, light_type=light_type, n_lights=n_lights, tile=tile, seed=seed, **kw)
+
+
+def stack_target(entry, name, kw, seed=0):
+    """The MSE target of the stack tests for build_for(entry, name, kw, seed): the oracle's stack of ANOTHER material of the same case
+    (seed ^ 1: other patterns, and the tilts mirrored, so a light behind the surface here is lit there and its target is not 0),
+    [L,3,H,W] float32.  `dark`: lights 1 and 2 are behind every pixel of every seed, so their own images are 0 everywhere; light 1 takes
+    light 0's image as its target instead, so that a light that must be masked has an upstream gradient that is not 0."""
+    target = render(build_for(entry, name, kw, seed=seed ^ 1)).float()
+    if name == "dark":
+        target[1] = target[0]
+    return target
 
 
 def crop(case, width):
@@ -101,6 +134,10 @@ def all_variants():
     return [(n, kw) for n in CASE_NAMES for kw in VARIANTS[n]]
 
 
+def all_stack_variants():
+    return [(n, kw) for n in STACK_CASE_NAMES for kw in VARIANTS[n]]
+
+
 def _h(t):
     """Round to fp16-exact values."""
     return t.to(torch.float16).to(torch.float64)
@@ -108,7 +145,9 @@ def _h(t):
 
 class Case:
     """One set of inputs.  Maps are float64 tensors holding fp16-exact values: albedo [3,h,w], normal [3,h,w], roughness [1,h,w],
-    metallic [1,h,w] | specular [3,h,w]; view [3]; lights, intensities [L,3]; weight [3,H,W] with (H, W) = tile * (h, w)."""
+    metallic [1,h,w] | specular [3,h,w]; view [3]; lights, intensities [L,3]; weight [3,H,W] with (H, W) = tile * (h, w).
+    `stack`: the case is a LIGHT STACK -- L images, one per light, each with its own clamp and encode, instead of one image of the
+    summed lights; weight is then [L,3,H,W]."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -172,6 +211,9 @@ def render(case, maps=None, view=None, lights=None, intens=None, dtype=torch.flo
     lights = (case.lights if lights is None else lights).to(dtype)
     intens = (case.intensities if intens is None else intens).to(dtype)
     a, n, r, m, s, kw = _render_inputs(case, maps, view, lights, intens)
+    if case.stack:          # [L,3,H,W]: image l is the one-light evaluation for light l alone
+        return torch.stack([O.cook_torrance(a, n, r, m, s, light=lights[l], intensity=intens[l], return_srgb=case.return_srgb, **kw)
+                            for l in range(lights.shape[0])])
     if lights.shape[0] == 1:
         return O.cook_torrance(a, n, r, m, s, light=lights[0], intensity=intens[0], return_srgb=case.return_srgb, **kw)
     return O.cook_torrance_multi(a, n, r, m, s, lights=lights, intensities=intens, return_srgb=case.return_srgb, **kw)
@@ -255,6 +297,10 @@ def decisions(case, maps=None):
     for name, x in decoded:
         for thr in (0.0, KNEE_DECODE, 1.0):
             out.append(("%s vs %g" % (name, thr), x, thr, None, thr != KNEE_DECODE and case.name == "closed_ends"))
+    if case.stack:          # every image is clamped and encoded by itself: no summed colour, one knee per light
+        if case.return_srgb:      # a light decided behind has colour exactly 0 in any precision, more than MARGIN under the knee
+            out += [("colour[%d] vs knee" % l, t["u"][l].clamp(0, 1), KNEE_ENCODE, None, False) for l in range(case.n_lights)]
+        return out
     colour = t["u"][0].clamp(0, 1)
     if case.n_lights > 1:
         total = sum(u.clamp(0, 1) for u in t["u"])
@@ -330,9 +376,15 @@ def backlit(case):
     return _fold_all(m, case.tile)
 
 
+def behind(case):
+    """[L,H,W] bool on the output grid: light l is DECIDED behind the surface (N.L <= -MARGIN): its contribution, and in a stack its
+    whole image, is exactly 0 in any precision."""
+    return torch.stack([x[0] <= -MARGIN for x in _terms(case)["ndl"]])
+
+
 def branches(case):
     """-> dict name -> [H,W] bool on the output grid; 'named' is the branch the case is for, 'complement' the other side,
-    further entries are sub-branches that the case promises too."""
+    further entries are sub-branches that the case promises too.  Stack mode: `saturated` and `dark` read every light's OWN colour."""
     t = _terms(case)
     L = case.n_lights
     ndv, ndl, ndh, u = t["ndv"][0], [x[0] for x in t["ndl"]], [x[0] for x in t["ndh"]], t["u"]
@@ -346,6 +398,24 @@ def branches(case):
         # and on the complementary branch only if no light has, while some light is lit with N.H > 0
         named = functools.reduce(torch.logical_or, [(h < 0) & (l > 0) for h, l in zip(ndh, ndl)])
         return dict(named=named, complement=functools.reduce(torch.logical_or, [(h > 0) & (l > 0) for h, l in zip(ndh, ndl)]) & ~named)
+    if name == "split_lights":
+        n_lit = sum((x > 0).long() for x in ndl)
+        res = dict(named=(n_lit >= 1) & (n_lit < L), complement=n_lit == L, one_lit=n_lit == 1, two_lit=n_lit == 2)
+        res.update({"behind_%d" % l: x < 0 for l, x in enumerate(ndl)})
+        return res
+    if name == "saturated" and case.stack:
+        # the lights of one pixel on different sides of the clamp at 1: some light's own colour exceeds 1 in a channel while
+        # another light's stays below 1 in every channel
+        over = [(x > 1).any(dim=0) for x in u]
+        below = [(x < 1).all(dim=0) for x in u]
+        any_over = functools.reduce(torch.logical_or, over)
+        return dict(named=any_over & functools.reduce(torch.logical_or, below), complement=~any_over)
+    if name == "dark" and case.stack:      # per light, over the lit lights only (a light behind renders exactly 0)
+        lit = [x > 0 for x in ndl]
+        under = [(((x.clamp(0, 1) > 0) & (x.clamp(0, 1) < KNEE_ENCODE)).any(dim=0)) & k for x, k in zip(u, lit)]
+        above = [(x.clamp(0, 1) > KNEE_ENCODE).all(dim=0) | ~k for x, k in zip(u, lit)]
+        return dict(named=functools.reduce(torch.logical_or, under),
+                    complement=functools.reduce(torch.logical_and, above) & functools.reduce(torch.logical_or, lit))
     if name == "saturated":
         alone = functools.reduce(torch.logical_or, [(x > 1).any(dim=0) for x in u])
         some_not = functools.reduce(torch.logical_or, [((x < 1).any(dim=0)) for x in u])
@@ -462,10 +532,26 @@ def _weight(H, W, seed):
 ROUGHNESS_VALUES = (0.4, 0.55, 0.7, 0.85)
 
 
+# What two cases are lit with in stack mode ONLY (directions, view and maps are the summed-lights case's; every other case keeps its
+# intensities too).  Each image of a stack has its own clamp at 1:
+#   saturated    the summed-lights intensities saturate all three lights in the same pixels; here light 0 saturates (red) where lights 1
+#                and 2 stay below 1, so the lights of one pixel sit on different sides of the clamp
+#   closed_ends  every image has its own encode knee; under the summed-lights intensities a channel with albedo 0 is so dim under the two
+#                weaker lights that its colour is within MARGIN of the knee on 4.6-7.3 % of the pixels, over the 5 % cap: all three lights
+#                are brighter here (0.1-0.5 % undecided)
+STACK_INTENSITIES = {
+    "saturated": [[9.0, 1.2, 2.4], [2.0, 0.6, 0.5], [2.0, 0.5, 0.6]],
+    "closed_ends": [[4.5, 3.75, 5.25], [4.0, 4.5, 3.5], [3.5, 4.0, 4.5]],
+}
+
+
 def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, workflow="metallic", albedo_is_srgb=True,
-          return_srgb=True, quirk=True):
-    """The case `name` on an h x w map (output tile*h x tile*w), one or three lights of one type."""
-    assert name in CASE_NAMES and n_lights in (1, 3)
+          return_srgb=True, quirk=True, stack=False):
+    """The case `name` on an h x w map (output tile*h x tile*w), one or three lights of one type.  stack=True: the same inputs read as a
+    light stack (untiled); `split_lights` exists only so."""
+    assert name in STACK_CASE_NAMES and n_lights in (1, 3)
+    assert not stack or tile == 1
+    assert name != "split_lights" or (stack and n_lights == 3)
     specular_is_srgb = albedo_is_srgb
     # per case: view, light directions (the first is the case's own), intensities, tilt range, colours
     behind = [[0.1, -0.2, -1.0], [-0.3, 0.1, -0.9]]                      # lights under the surface: N.L < 0 at every tilt used with them
@@ -484,6 +570,11 @@ def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, w
         view, dirs = [-0.99, 0.0, 0.141], [[0.3, 0.0, 0.954], [0.35, 0.1, 0.93], [0.25, -0.1, 0.96]]
         intens = [[4.0, 3.5, 4.5]] * 3
         max_y = 40.0
+    elif name == "split_lights":
+        # three lights on different sides of the surface: which of them are lit changes from pixel to pixel
+        view, dirs = [0.1, 0.05, 1.0], [[0.8, 0.1, 0.5], [-0.8, 0.1, 0.5], [0.1, 0.8, 0.5]]
+        intens = [[4.0, 3.5, 4.5], [3.0, 4.0, 3.5], [3.5, 3.0, 4.0]]
+        max_y = 60.0
     elif name == "saturated":
         view, dirs = [0.1, -0.1, 1.0], [[0.2, 0.1, 1.0], [-0.2, 0.2, 1.0], [0.1, -0.3, 1.0]]
         intens = [[9.0, 1.2, 2.4], [7.0, 0.6, 0.5], [7.0, 0.5, 0.6]]
@@ -506,6 +597,8 @@ def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, w
         rough_values = (0.55, 0.7, 0.85)
     if name == "saturated" and n_lights == 1:
         intens = [[9.0, 1.2, 2.4]]
+    if stack and name in STACK_INTENSITIES:
+        intens = STACK_INTENSITIES[name]
     lights, intensities = _lights(dirs[:n_lights], intens[:n_lights], light_type, point_distance)
     lights, intensities = lights.float().double(), intensities.float().double()          # fp32-exact: the kernels take them as floats
     view = torch.tensor(view, dtype=torch.float32).double()
@@ -543,7 +636,8 @@ def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, w
     H, W = h * tile, w * tile
     case = Case(name=name, albedo=albedo, normal=normal, roughness=rough, metallic=metallic, specular=specular, view=view, lights=lights,
                 intensities=intensities, light_type=light_type, light_size=light_size, workflow=workflow, albedo_is_srgb=albedo_is_srgb,
-                specular_is_srgb=specular_is_srgb, return_srgb=return_srgb, quirk=quirk, tile=tile, weight=_weight(H, W, 1000 + seed))
+                specular_is_srgb=specular_is_srgb, return_srgb=return_srgb, quirk=quirk, tile=tile, stack=stack,
+                weight=_weight(H, W, 1000 + seed) if not stack else torch.stack([_weight(H, W, 1000 + seed + 100 * l) for l in range(n_lights)]))
     if name == "dark":
         case = _solve_dark(case, seed)
     return case

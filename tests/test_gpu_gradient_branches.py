@@ -16,7 +16,10 @@ gradients agree within half the band on every such texel (torch's clamp passes t
 and (1.0 + 0.055) / 1.055 raised to 2.4 does not exceed 1), so none of them is left out of the comparison.
 
 fp16 maps: the kernel does the same fp32 arithmetic and rounds each gradient once to fp16, so the bound is the band plus the
-rule of test_gradients_of_fp16_maps, 1e-3 (1e-3 + |g64|) (2^-11 relative, subnormal floor)."""
+rule of test_gradients_of_fp16_maps, 1e-3 (1e-3 + |g64|) (2^-11 relative, subnormal floor).
+
+Several lights here are SUMMED into one image.  The light stack (one image, clamp and encode per light) runs on the fixture's stack
+mode in tests/test_gpu_light_stack_branches.py, which shares _check_maps below."""
 import pytest
 import torch
 

@@ -29,8 +29,11 @@ CASES = [
     ("specular", "point", 2, 1, 12, 48, torch.float16),          # fp16 maps, specular workflow
     ("metallic", "point", 1, 1, 20, 48, torch.float32),          # a single light
     ("metallic", "directional", 16, 1, 12, 32, torch.float32),   # the maximum light count
+    ("metallic", "point", 3, 1, 14, 44, torch.float32),          # normal=None: the kernels shade +Z (NO_NORMAL below)
 ]
-IDS = ["%s-%s-L%d-B%d-%dx%d-%s" % (c[0], c[1], c[2], c[3], c[4], c[5], "f16" if c[6] == torch.float16 else "f32") for c in CASES]
+NO_NORMAL = (len(CASES) - 1,)
+IDS = ["%s-%s-L%d-B%d-%dx%d-%s%s" % (c[0], c[1], c[2], c[3], c[4], c[5], "f16" if c[6] == torch.float16 else "f32", "-nonormal" if i in NO_NORMAL else "")
+       for i, c in enumerate(CASES)]
 NAMES = ("albedo", "normal", "roughness", "metallic", "specular")
 
 
@@ -45,6 +48,8 @@ def _case(i):
     workflow, light_type, L, B, H, W, dtype = CASES[i]
     g = torch.Generator().manual_seed(1000 + H * W + L)          # test_gpu_loss_step's own seeding rule
     maps = [None if t is None else t.to(dtype).float() for t in _maps(g, B, H, W, workflow)]        # the values the device sees
+    if i in NO_NORMAL:
+        maps[1] = None                                                                              # the oracle takes +Z
     targets = torch.rand(B, L, 3, H, W, generator=g)                                                # a different image per light
     view = torch.tensor([0.05, 0.1, 0.9])
     ang = torch.arange(L, dtype=torch.float32) * (2 * math.pi / max(L, 3)) + 0.3
