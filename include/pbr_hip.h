@@ -309,9 +309,25 @@ int pbr_cook_torrance_stack(const pbr_render_desc *desc, void *stream);
  * and autograd's accumulation.  `workspace`: the block pbr_mse_step_workspace_bytes(desc) describes (one partial sum per workgroup, then the
  * stage sums; finished in fp64 in a fixed order: deterministic).  `desc->out` is ignored.  Tiled maps: PBR_ERR_UNSUPPORTED (there is no
  * streamed, tiled or blended form); a NULL targets / loss / workspace: PBR_ERR_NULL_MAP.  No gradients of the lights from this form.
+ * (They come from pbr_cook_torrance_mse_stack_fit_step, below.)
  */
 int pbr_cook_torrance_mse_stack_step(const pbr_render_desc *desc, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
                                      void *g_metallic, void *g_specular, void *loss, void *workspace, void *stream);
+/*
+ * The same step with the gradients of the lights and the view, for captures whose light positions, per-shot intensities or camera axis are
+ * fitted along with (or instead of) the maps: everything pbr_cook_torrance_mse_stack_step does, plus `g_params` -- (3 + 6 L) floats of DEVICE
+ * memory in pbr_cook_torrance_backward_params's order and meaning: [d/d view_dir (3) | d/d lights (L x 3) | d/d intensities (L x 3)] of the
+ * mean over all 3 B L H W values, w.r.t. the values in the descriptor or the device_params block (view and directional lights un-normalised:
+ * the F.normalize Jacobian is applied); light_size has no gradient.  Still one pass over the maps; the per-workgroup rows are added up in fp64
+ * in a fixed order (deterministic).  Any or all of the g_* maps may be NULL (only the lights are fitted).  `workspace`:
+ * pbr_mse_stack_fit_workspace_bytes(desc) bytes of device memory -- the loss partials and stage sums as pbr_mse_step_workspace_bytes lays them
+ * out, then one row of 3 + 6 L floats per workgroup (8-byte aligned), then their stage sums; 0 where the call does not serve the descriptor.
+ * Before any launch: a NULL g_params / targets / loss / workspace PBR_ERR_NULL_MAP; out_dtype not PBR_F32 PBR_ERR_DTYPE; tiled maps or a NaN
+ * light_size PBR_ERR_UNSUPPORTED; more workgroups than the size query promised PBR_ERR_SHAPE.
+ */
+size_t pbr_mse_stack_fit_workspace_bytes(const pbr_render_desc *desc);
+int pbr_cook_torrance_mse_stack_fit_step(const pbr_render_desc *desc, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
+                                         void *g_metallic, void *g_specular, void *g_params, void *loss, void *workspace, void *stream);
 /* ABI 5: view / light / intensity from DEVICE memory.  `view_dir` [3], `lights` [n_lights][3], `intensities` [intensity_rows][3] with
  * intensity_rows = 1 (one intensity for every light) or n_lights: fp32 device pointers; a NULL pointer takes that parameter from the descriptor
  * (d->view_dir / d->lights / d->intensities: host values), so only what lives on the device needs to be there.  Writes `block` (pbr_device_params_bytes() bytes,

@@ -50,6 +50,7 @@ EXPORTS = (
     "pbr_height_normalize", "pbr_height_normalize_backward",
     "pbr_pack_images",
     "pbr_cook_torrance_stack", "pbr_cook_torrance_mse_stack_step",
+    "pbr_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_mse_stack_fit_step",
 )
 
 
@@ -192,6 +193,10 @@ def lib():
     L.pbr_cook_torrance_stack.restype = ctypes.c_int
     L.pbr_cook_torrance_mse_stack_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pbr_cook_torrance_mse_stack_step.restype = ctypes.c_int
+    L.pbr_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
+    L.pbr_mse_stack_fit_workspace_bytes.restype = ctypes.c_size_t
+    L.pbr_cook_torrance_mse_stack_fit_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pbr_cook_torrance_mse_stack_fit_step.restype = ctypes.c_int
     L.pbr_scale_by_device_scalar.argtypes = [vp, sz, ctypes.c_int, vp, vp]
     L.pbr_scale_by_device_scalar.restype = ctypes.c_int
     L.pbr_scale_list_by_device_scalar.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_int, ctypes.c_int, vp, vp]

@@ -58,7 +58,7 @@ int stream_run(const pbr_render_desc *d, const void *grad_out, void *const g[5])
 // Tiles of the decomposition with the smallest tiles -- one pixel per lane, 64-lane workgroups: the most any launch of
 // this descriptor can have whatever the tuning knobs say (more pixels per lane or larger workgroups only merge tiles).
 // Same geometry as fill_args: bx = lanes along x (a power of two covering the row, at most 64), 64 / bx rows per tile.
-static int64_t max_tiles(const pbr_render_desc *d) {
+int64_t max_tiles(const pbr_render_desc *d) {
     int lg = 0;
     while ((1 << lg) < d->width && lg < 6) ++lg;
     const int64_t bx = 1ll << lg, by = 64 >> lg, rows = (int64_t)d->batch * d->height;
@@ -67,9 +67,29 @@ static int64_t max_tiles(const pbr_render_desc *d) {
 }
 
 // Workspace of the light / view gradients: max_tiles rows of partial sums (fp32), then kParamStageRows rows of stage sums (fp64).
-static size_t stage_offset_bytes(const pbr_render_desc *d) {
+size_t param_rows_bytes(const pbr_render_desc *d) {
     const size_t rows = (size_t)max_tiles(d) * (size_t)(3 + 6 * d->n_lights) * sizeof(float);
     return (rows + 7) & ~(size_t)7;
+}
+size_t param_stage_bytes(const pbr_render_desc *d) { return (size_t)kParamStageRows * (size_t)(3 + 6 * d->n_lights) * sizeof(double); }
+
+// The finish of the light / view gradients, for every kernel that leaves rows (pbr_cook_torrance_backward_params, the stack-fit step of
+// ct_stack.hip): `rows` = n_rows rows of 3 + 6 L partial sums with their stage block param_rows_bytes(d) further on -> g_params, through the two
+// reduction kernels (fp64, fixed order, the F.normalize Jacobians; `dev`: KArgs::dev, the parameters in device memory).
+int param_grad_finish(const pbr_render_desc *d, const float *rows, int n_rows, uint64_t dev, float *g_params, hipStream_t st) {
+    ParamFinishArgs f;
+    std::memset(&f, 0, sizeof(f));
+    const int n_param = 3 + 6 * d->n_lights;
+    double *stage = reinterpret_cast<double *>(reinterpret_cast<char *>(const_cast<float *>(rows)) + param_rows_bytes(d));
+    hipLaunchKernelGGL(param_grad_stage_kernel, dim3(kParamStageRows), dim3(256), 0, st, rows, stage, n_rows, n_param);
+    f.stage = stage; f.out = g_params;
+    f.n_rows = kParamStageRows; f.n_lights = d->n_lights; f.light_type = d->light_type;
+    f.dev = dev;
+    for (int c = 0; c < 3; ++c) f.view[c] = d->view_dir[c];
+    for (int i = 0; i < d->n_lights; ++i)
+        for (int c = 0; c < 3; ++c) f.lights[i][c] = d->lights[i][c];
+    hipLaunchKernelGGL(param_grad_finish_kernel, dim3(1u + 2u * (unsigned)d->n_lights), dim3(256), 0, st, f);
+    return launch_status();
 }
 
 static int launch_backward(const pbr_render_desc *d, const void *grad_out, void *g_albedo, void *g_normal, void *g_roughness,
@@ -124,20 +144,7 @@ static int launch_backward(const pbr_render_desc *d, const void *grad_out, void 
     hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), 0, st, k, b);
     const int e = launch_status();
     if (e != PBR_OK || !g_params) return e;
-    ParamFinishArgs f;
-    std::memset(&f, 0, sizeof(f));
-    const int n_param = 3 + 6 * d->n_lights;
-    double *stage = reinterpret_cast<double *>(static_cast<char *>(workspace) + stage_offset_bytes(d));
-    hipLaunchKernelGGL(param_grad_stage_kernel, dim3(kParamStageRows), dim3(256), 0, st, static_cast<const float *>(workspace), stage,
-                       (int)k.n_tiles, n_param);
-    f.stage = stage; f.out = static_cast<float *>(g_params);
-    f.n_rows = kParamStageRows; f.n_lights = d->n_lights; f.light_type = d->light_type;
-    f.dev = k.dev;
-    for (int c = 0; c < 3; ++c) f.view[c] = d->view_dir[c];
-    for (int i = 0; i < d->n_lights; ++i)
-        for (int c = 0; c < 3; ++c) f.lights[i][c] = d->lights[i][c];
-    hipLaunchKernelGGL(param_grad_finish_kernel, dim3(1u + 2u * (unsigned)d->n_lights), dim3(256), 0, st, f);
-    return launch_status();
+    return param_grad_finish(d, static_cast<const float *>(workspace), (int)k.n_tiles, k.dev, static_cast<float *>(g_params), st);
 }
 
 }  // namespace pbr
@@ -154,7 +161,7 @@ size_t pbr_param_grad_workspace_bytes(const pbr_render_desc *d) {
     const pbr::TuningScope tuning(d);
     if (pbr::validate(d) != PBR_OK) return 0;
     const int64_t tiles = pbr::max_tiles(d);
-    return tiles < 0 ? 0 : pbr::stage_offset_bytes(d) + (size_t)pbr::kParamStageRows * (size_t)(3 + 6 * d->n_lights) * sizeof(double);
+    return tiles < 0 ? 0 : pbr::param_rows_bytes(d) + pbr::param_stage_bytes(d);
 }
 
 int pbr_cook_torrance_backward_params(const pbr_render_desc *d, const void *grad_out, void *g_albedo, void *g_normal,

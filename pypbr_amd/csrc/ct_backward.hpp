@@ -230,6 +230,7 @@ __device__ __forceinline__ void backprop_light(const PixelTermsT<R> &t, const Li
 //   StackMseLoss<VEC> -- the light-stack step (ct_stack.hip): every light is an image of its own with its own target, so the one-light form
 //   (clamp, encode, difference) runs INSIDE the light loop, once per light, and the adjoints of all lights add up in the shared accumulators
 //   before the light-independent tail runs once.  `stack` selects that: the light loop runs over a.n_lights although MULTI is false.
+//   With PGRAD (the stack-fit step) light l's six sums leave the lane inside the loop, as for MULTI; a lane outside the map carries scale = 0.
 struct NoLoss { static constexpr bool on = false, stack = false; };
 template <int VEC> struct MseLoss {
     static constexpr bool on = true, stack = false;
@@ -374,7 +375,7 @@ __device__ __forceinline__ void backward_body_to(const KArgs &a, const BArgs &b,
             backprop_light<LIGHT, PGRAD>(pt, lg, lu.inten, e, g_col, adj, V, pa);
             if constexpr (PGRAD) {
                 accV[0] += hsum(pa.g_V.x); accV[1] += hsum(pa.g_V.y); accV[2] += hsum(pa.g_V.z);
-                if constexpr (MULTI) {        // per-light sums leave the lane here: the light loop is a run-time loop
+                if constexpr (MULTI || Loss::stack) {        // per-light sums leave the lane here: the light loop is a run-time loop
                     float v8[8] = {hsum(pa.g_L.x), hsum(pa.g_L.y), hsum(pa.g_L.z), hsum(pa.g_I[0]), hsum(pa.g_I[1]), hsum(pa.g_I[2]), 0.0f, 0.0f};
                     const float w = wave_sum8(v8);
                     const int j = (threadIdx.x >> 3) & 7;                    // the value this lane holds the wave total of
@@ -421,12 +422,13 @@ __device__ __forceinline__ void backward_body_to(const KArgs &a, const BArgs &b,
     }
     if constexpr (PGRAD) {
         {   // slots 0..2 = V; one light: 3..5 = L, 6..8 = I (n_param = 9), so values 0..7 of the first batch map to slots 0..7
-            float v8[8] = {accV[0], accV[1], accV[2], MULTI ? 0.0f : accL[0], MULTI ? 0.0f : accL[1], MULTI ? 0.0f : accL[2],
-                           MULTI ? 0.0f : accI[0], MULTI ? 0.0f : accI[1]};
+            constexpr bool kPerLight = MULTI || Loss::stack;          // the lights' sums left inside the loop: only V remains
+            float v8[8] = {accV[0], accV[1], accV[2], kPerLight ? 0.0f : accL[0], kPerLight ? 0.0f : accL[1], kPerLight ? 0.0f : accL[2],
+                           kPerLight ? 0.0f : accI[0], kPerLight ? 0.0f : accI[1]};
             const float w = wave_sum8(v8);
             const int j = (threadIdx.x >> 3) & 7;
-            if ((threadIdx.x & 7) == 0 && j < (MULTI ? 3 : 8)) atomicAdd(&s_param[j], w);
-            if constexpr (!MULTI) {
+            if ((threadIdx.x & 7) == 0 && j < (kPerLight ? 3 : 8)) atomicAdd(&s_param[j], w);
+            if constexpr (!kPerLight) {
                 const float wi = wave_sum(accI[2]);
                 if ((threadIdx.x & 63) == 0) atomicAdd(&s_param[8], wi);
             }

@@ -288,6 +288,13 @@ int launch_repeat_blend_backward(const pbr_render_desc *d, const void *kblend, c
 int mse_vec(const pbr_render_desc *d);
 int mse_finish(const pbr_render_desc *d, float *partials, int64_t n_partials, double count, float *loss, hipStream_t st);
 
+// ct_backward.hip, shared with the stack-fit step (ct_stack.hip): the most workgroups any launch of the descriptor has (one row of light / view
+// partial sums each), the bytes of those rows (8-byte aligned) and of the stage sums behind them, and rows -> g_params (the two reduction kernels)
+int64_t max_tiles(const pbr_render_desc *d);
+size_t param_rows_bytes(const pbr_render_desc *d);
+size_t param_stage_bytes(const pbr_render_desc *d);
+int param_grad_finish(const pbr_render_desc *d, const float *rows, int n_rows, uint64_t dev, float *g_params, hipStream_t st);
+
 // The repeat-inner kernels (cook_torrance_repeat_kernel, cook_torrance_repeat_backward_kernel) serve every tiled launch whose map rows hold a
 // 4-texel lane: the whole tiled image or a row band of it (a multi-GPU shard) of ANY height -- a band thinner than a period walks the window
 // of source rows it touches -- and ragged map widths (the last lane of a row moves back and overlaps its neighbour, as everywhere).  Until

@@ -1,5 +1,5 @@
 // ct_stack.hip -- a light stack: L images of one material batch, one per light, out of ONE pass over the maps
-// (C ABI: pbr_cook_torrance_stack, pbr_cook_torrance_mse_stack_step).
+// (C ABI: pbr_cook_torrance_stack, pbr_cook_torrance_mse_stack_step, pbr_cook_torrance_mse_stack_fit_step).
 //
 // A capture for SVBRDF fitting is a stack of photographs from one camera position with the light moved between the shots (a flash walked
 // around a tripod, a light stage, photometric stereo); the loss is the mean squared error over ALL images.  Image l of the stack is exactly
@@ -114,7 +114,60 @@ void cook_torrance_mse_stack_step_kernel(const KArgs a, const BArgs b, const flo
     if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
+// ------------------------------------------------------------------ the loss step over the stack, with the lights' and the view's gradients
+// The stack step with PGRAD: backward_body_to also forms the adjoints of view, light l and intensity l (backprop_light<LIGHT, true>), light l's
+// six sums leave the lane inside the run-time light loop (wave_sum8 -> the workgroup's LDS row), the view's three after the tail, and the row --
+// 3 + 6 L floats: view, lights L x 3, intensities L x 3, the layout of pbr_cook_torrance_backward_params -- goes to b.g_param_partials.  One wave
+// per workgroup: the order of additions is fixed.  Lanes outside the map shade a clamped position and here, unlike in the backward kernels, would
+// form a real upstream gradient from a real target: their scale is 0, so every adjoint they hold is exactly 0.
+// Pixels per lane: mse_vec, as the stack step.  Registers: the two-pixel body lands on 200-236 VGPRs (two waves per SIMD, as the stack step's
+// 184-216), the one-pixel body on 125-146 (three or four); no instantiation has scratch.
+template <int LIGHT, int WF, int VEC, typename TM>
+__global__ __launch_bounds__(64)
+void cook_torrance_mse_stack_fit_step_kernel(const KArgs a, const BArgs b, const float *__restrict__ targets, float scale, float *__restrict__ partials) {
+    const uint32_t tile = tile_of_workgroup(a, blockIdx.x);
+    const int ty = (int)a.div_tx.div(tile);
+    const LanePos p = lane_pos<VEC, true>(a, (int)tile - ty * a.tiles_x, ty);
+    static_assert(VEC == 1 || (VEC == 2 && PBR_MSE_PACKED), "StackMseLoss walks the lights once per lane");
+    __shared__ float s_param[3 + 6 * PBR_MAX_LIGHTS];
+    const int n_param = 3 + 6 * a.n_lights;
+    for (int i = threadIdx.x; i < n_param; i += 64) s_param[i] = 0.0f;      // a 16-light row holds 99 floats: more than the wave has lanes
+    __syncthreads();
+    Texels<VEC> t;
+    StackMseLoss<VEC> loss;
+    loss.scale = p.valid ? scale : 0.0f;
+    loss.sq = 0.0f;
+    loss.plane = a.o_cs;
+    loss.lane = targets + ((int64_t)p.b * a.n_lights * 3 * a.o_cs + p.pix);
+    float go[3][VEC];                                                              // unused by the loss policies
+    if constexpr (sizeof(TM) == 4) {
+        load_texels<WF, TM, VEC, true>(a, a.has_normal != 0, p, t);
+    } else if (p.sb) {
+        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, true, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, true, false>(a, p, t);
+    } else {
+        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, false, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, false, false>(a, p, t);
+    }
+    loss.prefetch(0);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) go[c][j] = 0.0f;
+    backward_body_to<LIGHT, WF, VEC, false, TM, true>(a, b, p, t, go, s_param, n_param,
+        [&](float (&ga)[3][VEC], float (&gn)[3][VEC], float (&gr)[VEC], float (&gm)[VEC], float (&gs)[3][VEC]) {
+            store_gradients<WF, VEC, TM>(a, b, p, ga, gn, gr, gm, gs);             // (the body returns before the sink for lanes outside the map)
+        }, loss);
+    const float mine = p.valid ? loss.sq : 0.0f;
+    const float total = wave_sum(mine);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
 using StackStepFn = void (*)(const KArgs, const BArgs, const float *, float, float *);
+
+template <int L, int W>
+static StackStepFn pick_stack_fit_step(bool half_maps, int vec) {
+    if (half_maps) return vec == 2 ? cook_torrance_mse_stack_fit_step_kernel<L, W, 2, __half> : cook_torrance_mse_stack_fit_step_kernel<L, W, 1, __half>;
+    return vec == 2 ? cook_torrance_mse_stack_fit_step_kernel<L, W, 2, float> : cook_torrance_mse_stack_fit_step_kernel<L, W, 1, float>;
+}
 
 template <int L, int W>
 static StackStepFn pick_stack_step(bool half_maps, int vec) {
@@ -182,6 +235,42 @@ int pbr_cook_torrance_mse_stack_step(const pbr_render_desc *d, const void *targe
     const StackStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> StackStepFn { return pick_stack_step<L(), W()>(half_maps, vec); });
     hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(targets), (float)(2.0 / count), partials);
     const int e = launch_status();
+    return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
+}
+
+size_t pbr_mse_stack_fit_workspace_bytes(const pbr_render_desc *d) {
+    using namespace pbr;
+    const TuningScope tuning(d);
+    if (validate(d) != PBR_OK || d->out_dtype != PBR_F32 || is_tiled(d) || nan_light_size(d)) return 0;
+    const size_t loss_part = pbr_mse_step_workspace_bytes(d);      // the loss partials and their stage sums, then the rows, then their stage sums
+    return loss_part == 0 ? 0 : loss_part + param_rows_bytes(d) + param_stage_bytes(d);
+}
+
+int pbr_cook_torrance_mse_stack_fit_step(const pbr_render_desc *d, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
+                                         void *g_metallic, void *g_specular, void *g_params, void *loss, void *workspace, void *stream) {
+    using namespace pbr;
+    const TuningScope tuning(d);
+    int rc = validate(d);
+    if (rc != PBR_OK) return rc;
+    if (!g_params || !targets || !loss || !workspace) return PBR_ERR_NULL_MAP;
+    if (d->out_dtype != PBR_F32) return PBR_ERR_DTYPE;
+    if (is_tiled(d) || nan_light_size(d)) return PBR_ERR_UNSUPPORTED;
+    const bool half_maps = d->map_dtype == PBR_F16;
+    const int vec = mse_vec(d);                               // sums over pixels: no lane may count a pixel twice
+    KArgs k;
+    fill_args(d, vec, k, 6);                                  // one-wave workgroups: one partial sum and one parameter row per workgroup
+    const int64_t most = max_tiles(d);
+    if (k.n_tiles < 0 || most < 0 || k.n_tiles > most) return PBR_ERR_SHAPE;      // never past what the size query promised
+    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
+    const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *const partials = static_cast<float *>(workspace);
+    float *const rows = reinterpret_cast<float *>(static_cast<char *>(workspace) + pbr_mse_step_workspace_bytes(d));
+    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, rows};
+    const StackStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> StackStepFn { return pick_stack_fit_step<L(), W()>(half_maps, vec); });
+    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(targets), (float)(2.0 / count), partials);
+    int e = launch_status();
+    if (e == PBR_OK) e = param_grad_finish(d, rows, k.n_tiles, k.dev, static_cast<float *>(g_params), st);
     return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
 }
 

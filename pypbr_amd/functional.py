@@ -957,7 +957,7 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
 # ------------------------------------------------------------------ light stacks: L images, one per light, out of one pass over the maps
 # An extension over the reference (csrc/ct_stack.hip): a capture for SVBRDF fitting is a stack of photographs from ONE camera position with the
 # light moved between the shots; image l of the stack is what `cook_torrance` gives for light l alone, and the loss is the MSE over all of them.
-STACK_LAUNCHES = {"cook_torrance_stack": 0, "mse_stack_step": 0}       # calls of the two stack entry points (the tests count launches)
+STACK_LAUNCHES = {"cook_torrance_stack": 0, "mse_stack_step": 0, "mse_stack_fit_step": 0}       # calls of the stack entry points (the tests count launches)
 
 
 def _stack_lights(light, light_intensity) -> Tuple[int, int]:
@@ -1062,15 +1062,99 @@ class _MseStackStepFn(torch.autograd.Function):
         return (*grads, None, None)
 
 
+class _MseStackFitFn(torch.autograd.Function):
+    """_MseStackStepFn with view_dir / light / light_intensity as differentiable inputs: ONE kernel (pbr_cook_torrance_mse_stack_fit_step) gives
+    the loss, the map gradients and the (3 + 6 L) gradients of view, lights and intensities -- a capture whose light positions, per-shot
+    intensities or camera axis are fitted, with or without the maps.  Parameters that live on the device are read there (device_params): no
+    read-back, so a whole step captures into a graph; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
+
+    @staticmethod
+    def _launch(maps, params, targets, kwargs, wanted):
+        view, light, inten = params
+        plan = plan_cook_torrance(*[None if t is None else t.detach() for t in maps], view_dir=view, light=light, light_intensity=inten, **kwargs)
+        plan.out = None                                     # the colours are never written
+        d = plan.desc
+        dev = plan.device
+        tgt = targets.detach().to(dev, torch.float32).reshape(d.batch, d.n_lights, 3, d.height, d.width).contiguous()
+        gdtype = torch.float32 if d.map_dtype == N.F32 else torch.float16
+        present = (True, bool(d.normal.data), True, bool(d.metallic.data), bool(d.specular.data))
+        bufs = [torch.empty(tuple(maps[i].shape), dtype=gdtype, device=dev) if wanted[i] and present[i] else None for i in range(5)]
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        gp = torch.empty(3 + 6 * d.n_lights, dtype=torch.float32, device=dev)
+        lib = N.lib()
+        ws_bytes = lib.pbr_mse_stack_fit_workspace_bytes(ctypes.byref(d))
+        if ws_bytes == 0:
+            raise _StepNotServed()
+        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)       # (every part of the block is a multiple of 8 bytes)
+        launch(dev, lib.pbr_cook_torrance_mse_stack_fit_step, ctypes.byref(d), tgt.data_ptr(), *[ptr(b) for b in bufs], gp.data_ptr(),
+               loss.data_ptr(), ws.data_ptr())
+        STACK_LAUNCHES["mse_stack_fit_step"] += 1
+        return loss, bufs, gp
+
+    @staticmethod
+    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs):
+        maps, params = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity)
+        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
+        loss, bufs, gp = _MseStackFitFn._launch(maps, params, targets, kwargs, wanted)
+        ctx.kwargs, ctx.wanted, ctx.grads, ctx.params = kwargs, wanted, (bufs, gp), params
+        ctx.present = [t is not None for t in maps]
+        ctx.save_for_backward(*[t for t in maps if t is not None], targets)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        saved = ctx.saved_tensors                           # in-place edits of the maps since forward are detected, as for any op
+        kept = ctx.grads
+        ctx.grads = None                                    # handed over below: autograd may keep the very buffers
+        if kept is None:                                    # differentiated again: the first call gave its buffers away
+            it = iter(saved[:-1])
+            maps = [next(it) if p else None for p in ctx.present]
+            _, *kept = _MseStackFitFn._launch(maps, ctx.params, saved[-1], ctx.kwargs, ctx.wanted)
+        grads, gp = kept
+        _scale_step_gradients(grads, grad_loss)
+        k = grad_loss.detach().to(gp.device, torch.float32).reshape(1).contiguous()
+        launch(gp.device, N.lib().pbr_scale_by_device_scalar, gp.data_ptr(), gp.numel(), N.F32, k.data_ptr())
+        L = (gp.numel() - 3) // 6
+        need = [ctx.needs_input_grad[5 + i] for i in range(3)]
+        host = gp.cpu() if any(n and not p.is_cuda for n, p in zip(need, ctx.params)) else None      # ONE copy for every parameter held on the CPU
+
+        def part(i, first, rows):
+            if not need[i]:
+                return None
+            g = (gp if ctx.params[i].is_cuda else host)[first:first + 3 * rows]
+            return _param_grad(g if i == 0 else g.reshape(rows, 3), ctx.params[i], L if i == 2 else 1)
+        pgrads = [part(0, 0, 1), part(1, 3, L), part(2, 3 + 3 * L, L)]
+        return (*grads, *pgrads, None, None)
+
+
+def _stack_route(maps, params, targets, kwargs, on_device=None):
+    """Which one-pass form serves a rendering_loss_mse_stack call: "fit" (_MseStackFitFn: view, a light or an intensity requires grad, with or
+    without the maps), "step" (_MseStackStepFn: only maps do) or None (the composition).  Both need plain arguments, untiled maps, every map with
+    its own planes, targets that need no grad and maps on a ROCm device (`on_device`: None = ask the albedo).  No rule by L: the fit step was
+    ahead of the composition at every L measured (profiles/light_stack_fit_step.json)."""
+    albedo = maps[0]
+    B = albedo.shape[0] if albedo.dim() == 4 else 1
+    shared = any(t is not None and B > 1 and (t.dim() == 3 or t.shape[0] == 1) for t in maps)
+    if on_device is None:
+        on_device = albedo.is_cuda
+    if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets):
+        return None
+    if _needs_grad(*params):
+        return "fit"
+    return "step" if _needs_grad(*maps) else None
+
+
 def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], roughness: torch.Tensor,
                              metallic: Optional[torch.Tensor] = None, specular: Optional[torch.Tensor] = None, *,
                              targets: torch.Tensor, **kwargs) -> torch.Tensor:
     """`torch.nn.MSELoss()(cook_torrance_stack(albedo, normal, roughness, metallic | specular, **kwargs), targets)`: the rendering loss over a
     stack of L photographs `targets` [L,3,H,W] / [B,L,3,H,W], as a 0-dim tensor on the maps' device; the gradient of each map is the sum over
-    the lights.  ONE pass over the maps (pbr_cook_torrance_mse_stack_step) under the conditions `rendering_loss_mse` uses -- a map requires
-    grad, light / view / targets do not, plain arguments, every map with its own planes, on a ROCm device -- and untiled maps; every other case
-    (tiled maps, maps shared by the batch, a light being fitted, no gradients wanted) is the stack followed by torch's MSE: same value to
-    fp32 rounding, same gradients, and a light being fitted receives its gradient."""
+    the lights.  ONE pass over the maps under the conditions `rendering_loss_mse` uses -- something requires grad, the targets do not, plain
+    arguments, every map with its own planes, on a ROCm device -- and untiled maps: pbr_cook_torrance_mse_stack_step when only maps require
+    grad, pbr_cook_torrance_mse_stack_fit_step when `view_dir`, `light` or `light_intensity` does (lights, per-shot intensities or the camera
+    axis being fitted, with or without the maps: their gradients come out of the same pass; a [3] / [1,3] intensity owns the sum over the
+    lights, a parameter on the CPU receives a CPU gradient).  Every other case (tiled maps, maps shared by the batch, targets that require grad,
+    no gradients wanted) is the stack followed by torch's MSE: same value to fp32 rounding, same gradients."""
     L, _ = _stack_lights(kwargs.get("light"), kwargs.get("light_intensity"))
     if not isinstance(albedo, torch.Tensor) or albedo.dim() not in (3, 4):
         raise ValueError("albedo must be [3,H,W] or [B,3,H,W]")
@@ -1081,11 +1165,13 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
         raise ValueError("targets must be the stack %s, got %s" % (want, tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets)))
     maps = (albedo, normal, roughness, metallic, specular)
     params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
-    B = albedo.shape[0] if albedo.dim() == 4 else 1
-    shared = any(t is not None and B > 1 and (t.dim() == 3 or t.shape[0] == 1) for t in maps)
-    if _needs_grad(*maps) and not _needs_grad(*params, targets) and _stack_plain(kwargs) and not shared and albedo.is_cuda:
+    route = _stack_route(maps, params, targets, kwargs)
+    if route is not None:
         kw = {k: v for k, v in kwargs.items() if k not in ("out", "blend", "blend_flags", "out_dtype", "autotune", "rows", "height_total", "y_offset", "tile")}
         try:
+            if route == "fit":
+                kw = {k: v for k, v in kw.items() if k not in _PARAM_KEYS}
+                return _MseStackFitFn.apply(albedo, normal, roughness, metallic, specular, *params, targets, kw)
             return _MseStackStepFn.apply(albedo, normal, roughness, metallic, specular, targets, kw)
         except _StepNotServed:
             pass

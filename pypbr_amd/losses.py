@@ -74,7 +74,10 @@ class MultiLightRenderingLoss(nn.Module):
     `light_intensities` [3] / [1,3] for all lights or [L,3], one `view_dir`, one `light_size`.  The loss is nn.MSELoss() over the L renderings
     of the predicted material against `ground_truth` -- a material, rendered with ONE launch (functional.cook_torrance_stack), or the stack
     of photographs itself ([L,3,H,W] / [B,L,3,H,W]).  When the ground truth is rendered differentiably, and when the predicted material takes
-    the one-pass form (functional.rendering_loss_mse_stack -> pbr_cook_torrance_mse_stack_step), follows RenderingLoss's rules."""
+    the one-pass form (functional.rendering_loss_mse_stack -> pbr_cook_torrance_mse_stack_step), follows RenderingLoss's rules.
+    With photographs as `ground_truth`, `lights`, `light_intensities` or `view_dir` that require grad -- plain tensors, or nn.Parameters,
+    which nn.Module registers on assignment so that `loss.parameters()` yields them -- are fitted in the same pass
+    (pbr_cook_torrance_mse_stack_fit_step); through a differentiably rendered ground truth they take the composition."""
 
     def __init__(self, light_type='point', view_dir=torch.tensor([0.0, 0.0, 1.0]), lights=torch.tensor([[0.1, 0.1, 1.0]]),
                  light_intensities=torch.tensor([1.0, 1.0, 1.0]), light_size=None):
