@@ -30,6 +30,9 @@ tests/test_gpu_light_stack_branches.py): the same inputs read as a LIGHT STACK (
 one-light evaluation for light l alone.  `render` gives [L,3,H,W], `gradients` differentiates the MSE over the stack (or sum(stack * W)),
 and `decisions` lists one encode knee per light (that light's own clamped colour) and no summed colour.  `split_lights`, stack mode
 only, puts three lights on different sides of the surface, so that the set of lit lights changes from pixel to pixel.
+
+BLEND MODE (build_blend, BLEND_ENTRY_CONFIGS; held by tests/test_blend_branches_host.py, run on the GPU by tests/test_gpu_blend_branches.py):
+two materials and a mask whose BLEND is the case, for the fused blend's backward (csrc/ct_blend_backward.hpp); see the section at the end.
 """
 import functools
 import math
@@ -37,6 +40,7 @@ import math
 import torch
 import torch.nn.functional as TF
 
+import blend_oracle as BO
 import torch_oracle as O
 
 MARGIN = 1e-3
@@ -170,7 +174,7 @@ class Case:
         d = dict(self.__dict__)
         d.update(kw)
         d.pop("_cache", None)
-        return Case(**d)
+        return type(self)(**d)
 
     def product_kwargs(self):
         """Keyword arguments of pypbr_amd.functional.cook_torrance for this case (view / light tensors are added by the caller)."""
@@ -222,7 +226,10 @@ def render(case, maps=None, view=None, lights=None, intens=None, dtype=torch.flo
 def gradients(case, dtype=torch.float64, params=False, loss_target=None):
     """Autograd through the oracle of sum(out * weight) -- or of mse_loss(out, loss_target) -- in `dtype`.
     -> dict: map name -> gradient (map-sized: a tiled map owns the sum over its repeats), 'out' -> the rendering, and with
-    params=True also 'view', 'lights', 'intensities'."""
+    params=True also 'view', 'lights', 'intensities'.  A blend case: see _blend_gradients."""
+    if getattr(case, "blend", False):
+        assert not params and loss_target is None
+        return _blend_gradients(case, dtype)
     leaves = [None if t is None else t.to(dtype).clone().requires_grad_(True) for t in case.maps()]
     P = [t.to(dtype).clone().requires_grad_(params) for t in (case.view, case.lights, case.intensities)]
     out = render(case, leaves, P[0], P[1], P[2], dtype)
@@ -363,8 +370,9 @@ def well_conditioned(case):
 
 @_cached
 def decided(case):
-    """[h,w] bool on the MAP grid: threshold-decided at every repeat, and well conditioned."""
-    return _fold_all(threshold_decided(case), case.tile) & well_conditioned(case)
+    """[h,w] bool on the MAP grid: threshold-decided at every repeat, and well conditioned.  A blend case: and not `degenerate`."""
+    ok = _fold_all(threshold_decided(case), case.tile) & well_conditioned(case)
+    return ok & ~case.degenerate if getattr(case, "blend", False) else ok
 
 
 def backlit(case):
@@ -457,16 +465,17 @@ def _pattern(values, C, h, w, seed, step=(1, 3, 5)):
     return _h(v[idx])
 
 
-def _tilted_normals(h, w, max_x, max_y, case_geom, reverse):
+def _tilted_normals(h, w, max_x, max_y, case_geom, reverse, min_x=None, keep=None):
     """Unit normals tilted about both axes on a grid of angles (degrees): columns sweep the tilt towards +-x over
     [-max_x, max_x], rows the tilt towards +-y over [-max_y, max_y].  Where a raw dot product with the view, a light or a
     half vector would be within 0.02 of zero the angle is SKIPPED: the pixel moves on along the grid by 3 degrees until all
     are clear.  N.L is kept further from zero (|N.L| >= 0.15): a lit pixel at a grazing light is so dim that its colour sits within
-    MARGIN of the contribution's clamp at 0 or of the encode knee.  fp16-exact."""
-    ax = torch.linspace(-max_x, max_x, w, dtype=torch.float64).view(1, w).expand(h, w).clone()
+    MARGIN of the contribution's clamp at 0 or of the encode knee.  fp16-exact.
+    `min_x`: the columns sweep [min_x, max_x] instead; `keep(n) -> [h,w] bool`: angles whose normal it rejects are skipped too."""
+    ax = torch.linspace(-max_x if min_x is None else min_x, max_x, w, dtype=torch.float64).view(1, w).expand(h, w).clone()
     ay = torch.linspace(-max_y, max_y, h, dtype=torch.float64).view(h, 1).expand(h, w).clone()
     if reverse:
-        ax = -ax
+        ax = -ax if min_x is None else ax.flip(1)
 
     def make(ax, ay):
         rx, ry = torch.deg2rad(ax), torch.deg2rad(ay)
@@ -479,6 +488,8 @@ def _tilted_normals(h, w, max_x, max_y, case_geom, reverse):
         floor = torch.full((dots.shape[0], 1, 1), 0.02, dtype=torch.float64)
         floor[1::2] = 0.15                               # rows 1, 3, 5 ...: N.L of each light
         near = (dots < floor).any(dim=0)
+        if keep is not None:
+            near = near | ~keep(n)
         if not bool(near.any()):
             break
         shift = 3.0 * ((step + 1) // 2) * (1 if step % 2 else -1)
@@ -546,10 +557,12 @@ STACK_INTENSITIES = {
 
 
 def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, workflow="metallic", albedo_is_srgb=True,
-          return_srgb=True, quirk=True, stack=False):
+          return_srgb=True, quirk=True, stack=False, flat=False):
     """The case `name` on an h x w map (output tile*h x tile*w), one or three lights of one type.  stack=True: the same inputs read as a
-    light stack (untiled); `split_lights` exists only so."""
+    light stack (untiled); `split_lights` exists only so.  flat=True (build_blend only): every normal is one that a [0,1]-ENCODED map
+    with three positive components decodes to (_flat_reachable); `backlit` is then lit and seen from the mirrored side."""
     assert name in STACK_CASE_NAMES and n_lights in (1, 3)
+    assert not flat or (name != "half_clamp" and not stack)
     assert not stack or tile == 1
     assert name != "split_lights" or (stack and n_lights == 3)
     specular_is_srgb = albedo_is_srgb
@@ -597,6 +610,13 @@ def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, w
         rough_values = (0.55, 0.7, 0.85)
     if name == "saturated" and n_lights == 1:
         intens = [[9.0, 1.2, 2.4]]
+    min_x = None
+    if flat and name in ("backlit", "backview"):
+        # tilts towards -x beyond about 50 degrees have no encoding with three positive components: the columns sweep [-35, 80] and the
+        # rows +-35; `backlit`'s lights (and view) are mirrored in x, so that the lights are behind at the tilts towards +x
+        min_x, max_y = -35.0, 35.0
+        if name == "backlit":
+            view, dirs = [-view[0], view[1], view[2]], [[-d[0], d[1], d[2]] for d in dirs]
     if stack and name in STACK_INTENSITIES:
         intens = STACK_INTENSITIES[name]
     lights, intensities = _lights(dirs[:n_lights], intens[:n_lights], light_type, point_distance)
@@ -605,7 +625,8 @@ def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, w
     light_size = 1.0 if light_type == "point" else None
     # half_clamp's branch lives at the steepest tilts towards +x: they come FIRST, so that cutting a map's last columns keeps them
     reverse = (seed % 2 == 1) != (name == "half_clamp")
-    normal = _tilted_normals(h, w, max_x, max_y, _geom_dots(view, lights, light_type, light_size, tile), reverse)
+    normal = _tilted_normals(h, w, max_x, max_y, _geom_dots(view, lights, light_type, light_size, tile), reverse,
+                             min_x=min_x, keep=_flat_reachable if flat else None)
     rough = _pattern(rough_values, 1, h, w, seed + 1, step=(3, 1, 0))
     albedo = _pattern(albedo_values, 3, h, w, seed)
     metallic = _pattern(metal_values, 1, h, w, seed + 2, step=(1, 2, 0)) if workflow != "specular" else None
@@ -692,3 +713,185 @@ def report(case):
         case.name, case.albedo.shape[1], case.albedo.shape[2], case.tile, case.light_type, case.n_lights, case.workflow, ", ".join(parts),
         100 * float((~d).double().mean()), 100 * float((~_fold_all(threshold_decided(case), case.tile)).double().mean()),
         100 * float((~well_conditioned(case)).double().mean()))
+
+
+# ------------------------------------------------------------------------------------------------ blend mode
+# BLEND MODE (build_blend, BLEND_ENTRY_CONFIGS; held by tests/test_blend_branches_host.py, run on the GPU by tests/test_gpu_blend_branches.py):
+# two materials and a mask whose BLEND (blend_oracle.blend_materials: lerp of the plain maps, normalize / lerp / normalize of the normals, the
+# blended normal decoded again when the whole map has no negative component) is the case `name`.  The case object carries the blended maps in
+# float64 as its own maps, so `decisions`, `threshold_decided`, `branches` and `backlit` read the blend from the oracle alone; `gradients`
+# differentiates sum(out * W) through the blend and the render for both materials' maps and the mask, `well_conditioned` compares all of them.
+# Inputs are fp32-exact (the fused blend is fp32 only).
+MAP_NAMES = ("albedo", "normal", "roughness", "metallic", "specular")
+MASK_VALUES = (0.0, 0.25, 0.5, 0.75, 1.0, 0.5)
+THETA_VALUES = (6.0, -9.0, 12.0, -5.0)            # degrees between the two materials' normals
+DELTA_VALUES = (0.1, -0.15, 0.2, -0.05)           # material 1 - material 2 of a plain map (roughness: half of it)
+STORED_LENGTHS = (0.75, 1.25)                     # the two normals are stored un-normalised, at different lengths
+
+# (h, w, light type, lights, tile): the smallest shapes that still fill every branch to 10 %
+BLEND_ENTRY_CONFIGS = {
+    "blend-pairs": (24, 40, "directional", 1, 1),             # two pixels per lane
+    "blend-pairs-point": (24, 40, "point", 1, 1),
+    "blend-one-pixel": (23, 37, "point", 1, 1),               # odd width: one pixel per lane
+    "blend-multi-point": (24, 40, "point", 3, 1),             # MULTI
+    "blend-multi-directional": (24, 40, "directional", 3, 1),
+    "blend-tiled": (12, 16, "directional", 1, 2),             # the fused tiled backward (ct_repeat_backward.hpp)
+    "blend-tiled-point": (12, 16, "point", 1, 2),
+    "blend-pieces": (24, 40, "point", 1, 1),                  # the unfused differentiable pieces, called directly
+}
+
+
+def all_blend_variants():
+    """Every variant signed (the blended normal map has negative components: kept as it is), every case but `half_clamp` flat (every
+    component positive everywhere: decoded again), and one dedicated variant with `degenerate` texels."""
+    out = [(n, dict(kw)) for n, kw in all_variants()]
+    out += [(n, dict(kw, flat=True)) for n, kw in all_variants() if n != "half_clamp"]
+    out.append(("backview", dict(degenerate=True)))
+    return out
+
+
+class BlendCase(Case):
+    """A Case whose maps are the float64 BLEND of `first` and `second` (dicts name -> [C,h,w] float64 of fp32-exact values) under `mask`
+    [1,h,w]; `flat`: the blended normal map counts as [0,1]-encoded; `degenerate` [h,w] bool: texels kept out of every comparison."""
+    blend = True
+
+    def map_names(self):
+        """The names of the gradients: '1.albedo' ... '2.metallic', 'mask'."""
+        return ["%d.%s" % (i, n) for i, m in ((1, self.first), (2, self.second)) for n in MAP_NAMES if m.get(n) is not None] + ["mask"]
+
+
+def _f(t):
+    """Round to fp32-exact values."""
+    return t.float().double()
+
+
+def _flat_encode(nn):
+    """Unit normals -> the unit vectors o with normalize(2 o - 1) = nn:  o = (1 + s nn) / 2,  s = -sigma + sqrt(sigma^2 + 1),
+    sigma = nn_x + nn_y + nn_z  (|o| = 1 is a quadratic in s)."""
+    sigma = nn.sum(dim=0, keepdim=True)
+    return (1 + (-sigma + torch.sqrt(sigma * sigma + 1)) * nn) / 2
+
+
+def _flat_reachable(n):
+    """[h,w] bool: the encoding of this normal has three components of at least 0.05 (positive with room for the blend's own error)."""
+    return (_flat_encode(TF.normalize(n, dim=0)) >= 0.05).all(dim=0)
+
+
+def blended_maps(first, second, mask, dtype=torch.float64):
+    """The oracle's blend of two materials, as the five maps of a Case."""
+    bl = BO.blend_materials({k: v.to(dtype) for k, v in first.items()}, {k: v.to(dtype) for k, v in second.items()}, mask.to(dtype))
+    return [bl.get(n) for n in MAP_NAMES]
+
+
+def blend_is_flat(case):
+    """The whole-map flag, from the oracle: no component of the blended normal map (before it is assigned) is negative or zero."""
+    return bool(BO.blend_normals(case.first["normal"], case.second["normal"], case.mask).min() > 0)
+
+
+DEGENERATE_BLOCKS = ((6, 8), (14, 24))            # (row, column) of two 2 x 4 blocks: opposed normals under mask 0.5; a stored (0, 0, 0)
+
+
+def _split(x, seed, flat, degenerate):
+    """x = w m1 + (1 - w) m2 for every plain map (m1 = x + (1 - w) d, m2 = x - w d), and for the normal a^ = cos((1-w) th) n + sin((1-w) th) t,
+    b^ = cos(w th) n - sin(w th) t with t a tangent: the two unit normals th degrees apart, their blend along n.  flat: n is the ENCODING of the
+    case's normal.  `closed_ends`: where x is exactly 0.0 or 1.0 both materials hold that value (d = 0), so the blend is that number in any precision."""
+    h, w = x.albedo.shape[1:]
+    mask = _pattern(MASK_VALUES, 1, h, w, 7 + seed, step=(1, 2, 0))
+    deg = torch.zeros(h, w, dtype=torch.bool)
+    if degenerate:
+        assert 16 <= 0.02 * h * w, "the degenerate class is at most 2 % of the texels"
+        for y0, x0 in DEGENERATE_BLOCKS:
+            deg[y0:y0 + 2, x0:x0 + 4] = True
+        y0, x0 = DEGENERATE_BLOCKS[0]
+        mask[:, y0:y0 + 2, x0:x0 + 4] = 0.5
+    first, second = {}, {}
+    for i, (name, t) in enumerate(zip(MAP_NAMES, x.maps())):
+        if t is None:
+            continue
+        if name == "normal":
+            n = TF.normalize(t, dim=0)
+            if flat:
+                n = TF.normalize(_flat_encode(n), dim=0)
+            axis = torch.tensor([0.3, 0.9, 0.2], dtype=torch.float64).view(3, 1, 1).expand_as(n)
+            tang = TF.normalize(torch.cross(n, axis, dim=0), dim=0)
+            th = torch.deg2rad(_pattern(THETA_VALUES, 1, h, w, seed + 9, step=(1, 1, 0)))
+            a = n * torch.cos((1 - mask) * th) + tang * torch.sin((1 - mask) * th)
+            b = n * torch.cos(mask * th) - tang * torch.sin(mask * th)
+            first[name], second[name] = _f(a * STORED_LENGTHS[0]), _f(b * STORED_LENGTHS[1])
+            if degenerate:
+                (y0, x0), (y1, x1) = DEGENERATE_BLOCKS
+                up = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64).view(3, 1, 1)
+                first[name][:, y0:y0 + 2, x0:x0 + 4] = up * STORED_LENGTHS[0]          # exactly opposed: the blend has length 0
+                second[name][:, y0:y0 + 2, x0:x0 + 4] = -up * STORED_LENGTHS[1]
+                second[name][:, y1:y1 + 2, x1:x1 + 4] = 0.0
+        else:
+            d = _pattern(DELTA_VALUES, t.shape[0], h, w, seed + 11 + i) * (0.5 if name == "roughness" else 1.0)
+            if x.name == "closed_ends":
+                d = torch.where((t == 0) | (t == 1), torch.zeros_like(d), d)
+            first[name], second[name] = _f(t + (1 - mask) * d), _f(t - mask * d)
+    return first, second, mask, deg
+
+
+def _first_for(x, shared, flat):
+    """Material 1 whose blend with ANOTHER blend case's material 2 and mask is x (a batch of first materials against one second material):
+    m1 = (x - (1 - w) m2) / w, and for the normal the unit a^ with w a^ + (1 - w) b^ along n.  Where the mask is 0 the blend is material 2."""
+    w = shared.mask
+    safe = torch.where(w > 0, w, torch.ones_like(w))
+    first = {}
+    for name, t in zip(MAP_NAMES, x.maps()):
+        if t is None:
+            continue
+        m2 = shared.second[name]
+        if name == "normal":
+            n = TF.normalize(t, dim=0)
+            if flat:
+                n = TF.normalize(_flat_encode(n), dim=0)
+            b = TF.normalize(m2, dim=0)
+            c = (1 - w) * (n * b).sum(dim=0, keepdim=True)
+            lam = c + torch.sqrt((c * c - (1 - w) ** 2 + w ** 2).clamp_min(0.0))          # |lam n - (1 - w) b^| = w
+            first[name] = _f(torch.where(w > 0, (lam * n - (1 - w) * b) / safe, n))
+        else:
+            first[name] = _f(torch.where(w > 0, (t - (1 - w) * m2) / safe, t))
+    return first
+
+
+def build_blend(name, h, w, *, flat=False, degenerate=False, shared=None, seed=0, **kw):
+    """Two materials and a mask whose blend is the case `name` (keyword arguments of `build`).  flat=True: every component of the blended
+    normal map is positive, so it is decoded again.  shared=<blend case>: its material 2 and mask, and the material 1 that blends to this case."""
+    x = build(name, h, w, seed=seed, flat=flat, **kw)
+    if shared is None:
+        first, second, mask, deg = _split(x, seed, flat, degenerate)
+    else:
+        first, second, mask, deg = _first_for(x, shared, flat), shared.second, shared.mask, shared.degenerate
+    d = dict(x.__dict__)
+    d.pop("_cache", None)
+    d.update(zip(MAP_NAMES, blended_maps(first, second, mask)))
+    return BlendCase(**dict(d, first=first, second=second, mask=mask, flat=flat, degenerate=deg))
+
+
+def build_blend_for(entry, name, kw, seed=0, shared=None):
+    h, w, light_type, n_lights, tile = BLEND_ENTRY_CONFIGS[entry]
+    return build_blend(name, h, w, light_type=light_type, n_lights=n_lights, tile=tile, seed=seed, shared=shared, **kw)
+
+
+def _blend_gradients(case, dtype):
+    """Autograd of sum(out * weight) through blend_oracle.blend_materials and the render, in `dtype`.
+    -> dict: '1.<map>' / '2.<map>' / 'mask' -> gradient (map-sized), 'out' -> the rendering."""
+    r1 = {k: v.to(dtype).clone().requires_grad_(True) for k, v in case.first.items()}
+    r2 = {k: v.to(dtype).clone().requires_grad_(True) for k, v in case.second.items()}
+    rm = case.mask.to(dtype).clone().requires_grad_(True)
+    bl = BO.blend_materials(r1, r2, rm)
+    out = render(case, [bl.get(n) for n in MAP_NAMES], dtype=dtype)
+    (out * case.weight.to(dtype)).sum().backward()
+    res = {"%d.%s" % (i, k): v.grad for i, m in ((1, r1), (2, r2)) for k, v in m.items()}
+    res.update(mask=rm.grad, out=out.detach())
+    return res
+
+
+# A batch of two first materials (seeds 0 and 2) against ONE second material and ONE mask (those of seed 0), one per light type
+BLEND_BATCH_CASES = (("blend-pairs", "backlit", dict()), ("blend-pairs-point", "saturated", dict(flat=True)))
+
+
+def build_blend_batch(entry, name, kw):
+    first = build_blend_for(entry, name, kw, seed=0)
+    return [first, build_blend_for(entry, name, kw, seed=2, shared=first)]
