@@ -55,6 +55,26 @@ int stream_run(const pbr_render_desc *d, const void *grad_out, void *const g[5])
     return g_bwd_run > 0 ? g_bwd_run : 4;          // 4096^2: 1 round 144-146 us, 2: 140-141, 4: 137-139, 6: 138, 8: 139-140 (tools/bwd_stream_ab.sh)
 }
 
+// The shape of a streamed launch that stream_run admitted, for the backward kernel and the loss step alike: `k` for two pixels per lane with
+// contiguous upstream / target and gradient planes; g = the five gradient pointers (NULL = not wanted).
+StreamLaunch stream_launch_shape(const pbr_render_desc *d, void *const g[5], int rounds, KArgs &k) {
+    fill_args(d, 2, k, 6);
+    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
+    StreamLaunch s;
+    s.tiles = (int)(k.o_cs / 128);
+    const bool spec = d->workflow == PBR_WORKFLOW_SPECULAR;
+    s.n_stores = (g[0] ? 3 : 0) + (g[1] && d->normal.data ? 3 : 0) + (g[2] ? 1 : 0) + (spec ? (g[4] ? 3 : 0) : (g[3] ? 1 : 0));
+    // every run-time flag on and every gradient wanted: the instantiation without flag branches
+    s.full = d->albedo_is_srgb && d->return_srgb && d->normal.data && g[0] && g[1] && g[2] &&
+             (spec ? (g[4] && d->specular_is_srgb) : (g[3] && (d->workflow == PBR_WORKFLOW_METALLIC || d->specular_is_srgb)));
+    // one-wave workgroups, kStreamWavesPerSimd of them per SIMD: the grid covers the chip `rounds` times, split over the materials
+    const int64_t slots = (int64_t)resident_cus() * 4 * kStreamWavesPerSimd * rounds;
+    s.per_material = (slots + d->batch - 1) / d->batch;
+    if (s.per_material > s.tiles) s.per_material = s.tiles;
+    if (s.per_material < 1) s.per_material = 1;
+    return s;
+}
+
 // Tiles of the decomposition with the smallest tiles -- one pixel per lane, 64-lane workgroups: the most any launch of
 // this descriptor can have whatever the tuning knobs say (more pixels per lane or larger workgroups only merge tiles).
 // Same geometry as fill_args: bx = lanes along x (a power of two covering the row, at most 64), 64 / bx rows per tile.
@@ -113,23 +133,10 @@ static int launch_backward(const pbr_render_desc *d, const void *grad_out, void 
     KArgs k;
     void *const gs[5] = {g_albedo, g_normal, g_roughness, g_metallic, g_specular};
     if (const int rounds = g_params ? 0 : stream_run(d, grad_out, gs)) {
-        fill_args(d, 2, k, 6);
-        k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
+        const StreamLaunch s = stream_launch_shape(d, gs, rounds, k);
         const BArgs b = {grad_out, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
-        const int tiles = (int)(k.o_cs / 128);
-        const bool spec = d->workflow == PBR_WORKFLOW_SPECULAR;
-        const int n_stores = (g_albedo ? 3 : 0) + (g_normal && d->normal.data ? 3 : 0) + (g_roughness ? 1 : 0) +
-                             (spec ? (g_specular ? 3 : 0) : (g_metallic ? 1 : 0));
-        // every run-time flag on and every gradient wanted: the instantiation without flag branches
-        const bool full = d->albedo_is_srgb && d->return_srgb && d->normal.data && g_albedo && g_normal && g_roughness &&
-                          (spec ? (g_specular && d->specular_is_srgb) : (g_metallic && (d->workflow == PBR_WORKFLOW_METALLIC || d->specular_is_srgb)));
-        // one-wave workgroups, kStreamWavesPerSimd of them per SIMD: the grid covers the chip `rounds` times, split over the materials
-        const int64_t slots = (int64_t)resident_cus() * 4 * kStreamWavesPerSimd * rounds;
-        int64_t per_material = (slots + d->batch - 1) / d->batch;
-        if (per_material > tiles) per_material = tiles;
-        if (per_material < 1) per_material = 1;
-        hipLaunchKernelGGL(pick_bwd_stream(d, full), dim3((unsigned)per_material, (unsigned)d->batch, 1), dim3(64, 1, 1), 0,
-                               static_cast<hipStream_t>(stream), k, b, tiles, n_stores);
+        hipLaunchKernelGGL(pick_bwd_stream(d, s.full), dim3((unsigned)s.per_material, (unsigned)d->batch, 1), dim3(64, 1, 1), 0,
+                               static_cast<hipStream_t>(stream), k, b, s.tiles, s.n_stores);
         return launch_status();
     }
     // Light / view adjoints: a workgroup adds its waves' sums into LDS with atomics -- with ONE wave per workgroup the

@@ -481,6 +481,36 @@ __device__ __forceinline__ void backward_body(const KArgs &a, const BArgs &b, co
         });
 }
 
+// The frame of every one-wave loss step (cook_torrance_mse_step_kernel in ct_loss.hip, cook_torrance_mse_stack_step_kernel in ct_stack.hip):
+// the workgroup's tile -> the lane's position (lanes outside the map shade a clamped position: every lane reaches the wave sum, stores
+// nothing and contributes nothing) -> the texels -> `first_targets(p, loss)`, the kernel's own part: it fills the policy's fields and issues
+// the loads of the first target pixels, behind the texels' -> backward_body_to with the storing sink -> the wave's sum of squared differences,
+// one partial per workgroup, no LDS reduction.  PGRAD: the kernel owns the LDS row s_param[n_param], zeroed before the call; the body
+// returns before the sink for lanes outside the map, so the sink needs no guard of its own.
+template <int LIGHT, int WF, int VEC, bool MULTI, typename TM, bool PGRAD, class Loss, class FirstTargets>
+__device__ __forceinline__ void loss_step(const KArgs &a, const BArgs &b, float *s_param, int n_param, float *partials, FirstTargets &&first_targets) {
+    const uint32_t tile = tile_of_workgroup(a, blockIdx.x);
+    const int ty = (int)a.div_tx.div(tile);
+    const LanePos p = lane_pos<VEC, true>(a, (int)tile - ty * a.tiles_x, ty);
+    Texels<VEC> t;
+    Loss loss;
+    loss.sq = 0.0f;
+    float go[3][VEC];                                                              // unused by the loss policies
+    load_texels<WF, TM, VEC, true>(a, a.has_normal != 0, p, t);
+    first_targets(p, loss);
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) go[c][j] = 0.0f;
+    backward_body_to<LIGHT, WF, VEC, MULTI, TM, PGRAD>(a, b, p, t, go, s_param, n_param,
+        [&](float (&ga)[3][VEC], float (&gn)[3][VEC], float (&gr)[VEC], float (&gm)[VEC], float (&gs)[3][VEC]) {
+            if (PGRAD || p.valid) store_gradients<WF, VEC, TM>(a, b, p, ga, gn, gr, gm, gs);
+        }, loss);
+    const float mine = p.valid ? loss.sq : 0.0f;
+    const float total = wave_sum(mine);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+}
+
 //   LIGHT: PBR_LIGHT_*    WF: PBR_WORKFLOW_*    VEC: 4 | 2 | 1    TM: storage type of the maps AND of their gradients
 //   (float | __half; arithmetic and the upstream gradient are fp32)
 //   PGRAD: also the adjoints of view / light / intensity, summed over the workgroup's pixels into b.g_param_partials

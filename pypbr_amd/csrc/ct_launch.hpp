@@ -2,7 +2,8 @@
 // ct_backward.hip, ct_repeat_backward.hip, ct_blend.hip, ct_loss.hip, ct_stack.hip): descriptor validation, the light x workflow dispatch
 // (with_light_workflow), the 16-byte-path test, the workgroup-order rule and the translation of a pbr_render_desc into the
 // kernel-argument block.  Launch status, alignment test and CU count: launch_util.hpp (through stream_shape.hpp).  Tuning knobs
-// live in cook_torrance.hip (pbr_set_tuning).
+// live in cook_torrance.hip (pbr_set_tuning).  Also the declarations of the host pieces several launchers call: the loss steps' gate, launch and
+// finish (ct_loss.hip), the streamed form's launch shape and the light / view gradients' finish (ct_backward.hip), the repeat-inner walks.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -283,10 +284,27 @@ int launch_repeat_backward(const pbr_render_desc *d, const void *upstream, void 
 bool repeat_blend_backward_serves(const pbr_render_desc *d);
 int launch_repeat_blend_backward(const pbr_render_desc *d, const void *kblend, const void *grad_out, const void *g1, const void *g2, hipStream_t st);
 
-// ct_loss.hip, shared with the light-stack step (ct_stack.hip): pixels per lane of a loss step (no lane may count a pixel twice), and the step's
-// partial sums -> *loss = sum / count through the two reduction kernels (fp64, fixed order), the stage sums where pbr_mse_step_workspace_bytes put them
+// The loss steps (ct_loss.hip; the light-stack steps of ct_stack.hip are built from the same pieces).  An entry point is: mse_gate, pick the
+// kernel, launch_loss_step, mse_finish.
+//   mse_gate: valid descriptor, the caller's pointers, fp32 result, no NaN grid, untiled maps unless the step has a tiled form that serves them
+//   mse_vec: pixels per lane of a loss step (no lane may count a pixel twice)
+//   launch_loss_step: the one-wave launch of a kernel over ct_backward.hpp's loss_step frame; leaves its KArgs in `k`
+//   mse_finish: the step's partial sums -> *loss = sum / count through the reduction kernels (fp64, fixed order), the stage sums where
+//   pbr_mse_step_workspace_bytes put them
+struct BArgs;
+using LossStepFn = void (*)(const KArgs, const BArgs, const float *, float, float *);
+int mse_gate(const pbr_render_desc *d, bool pointers_given, bool tiled_form);
 int mse_vec(const pbr_render_desc *d);
+int launch_loss_step(const pbr_render_desc *d, LossStepFn fn, int vec, const BArgs &b, const void *targets, double count, float *partials,
+                     hipStream_t st, KArgs &k);
 int mse_finish(const pbr_render_desc *d, float *partials, int64_t n_partials, double count, float *loss, hipStream_t st);
+
+// ct_backward.hip: the streamed form (fp16 maps, one light), shared by the backward launcher and the loss step.  stream_run: rounds of the
+// streamed kernel, 0 = the launch does not qualify.  stream_launch_shape: fills `k` and gives the 128-pixel tiles of a material, the gradient
+// planes a tile stores, whether the instantiation without flag branches serves, and the grid's x (one-wave workgroups per material).
+struct StreamLaunch { int tiles, n_stores; bool full; int64_t per_material; };
+int stream_run(const pbr_render_desc *d, const void *grad_out, void *const g[5]);
+StreamLaunch stream_launch_shape(const pbr_render_desc *d, void *const g[5], int rounds, KArgs &k);
 
 // ct_backward.hip, shared with the stack-fit step (ct_stack.hip): the most workgroups any launch of the descriptor has (one row of light / view
 // partial sums each), the bytes of those rows (8-byte aligned) and of the stage sums behind them, and rows -> g_params (the two reduction kernels)

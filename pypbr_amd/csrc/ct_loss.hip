@@ -12,6 +12,10 @@
 //
 // The loss itself: every workgroup (one wave) leaves its sum of squared differences in a workspace row; a second small kernel
 // adds the rows in fp64 in a fixed order (deterministic) and writes mean = sum / N.
+//
+// This file is also the home of what every loss step shares on the host -- this one and the two over light stacks (ct_stack.hip): an entry
+// point is mse_gate, pick the kernel, launch_loss_step, mse_finish (declared in ct_launch.hpp).  What they share on the device is the frame
+// loss_step (ct_backward.hpp, beside the loss policies): a step kernel is that frame with its policy and its first target loads.
 #include "ct_backward.hpp"
 #include "ct_launch.hpp"
 
@@ -26,35 +30,12 @@ constexpr int mse_min_waves() { return VEC == 2 && !MULTI && sizeof(TM) == 2 ? 3
 template <int LIGHT, int WF, int VEC, bool MULTI, typename TM>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(mse_min_waves<VEC, MULTI, TM>())))
 void cook_torrance_mse_step_kernel(const KArgs a, const BArgs b, const float *__restrict__ target, float scale, float *__restrict__ partials) {
-    const uint32_t tile = tile_of_workgroup(a, blockIdx.x);
-    const int ty = (int)a.div_tx.div(tile);
-    const LanePos p = lane_pos<VEC, true>(a, (int)tile - ty * a.tiles_x, ty);      // lanes outside the map shade a clamped position: every lane reaches the sum
-    Texels<VEC> t;
-    MseLoss<VEC> loss;
-    loss.scale = scale;
-    loss.sq = 0.0f;
-    float go[3][VEC];                                                              // unused by the MseLoss policy
-    const int64_t opix = p.b * a.o_bs + p.pix;
-    if constexpr (sizeof(TM) == 4) {
-        load_texels<WF, TM, VEC, true>(a, a.has_normal != 0, p, t);
-    } else if (p.sb) {
-        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, true, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, true, false>(a, p, t);
-    } else {
-        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, false, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, false, false>(a, p, t);
-    }
+    loss_step<LIGHT, WF, VEC, MULTI, TM, false, MseLoss<VEC>>(a, b, nullptr, 0, partials, [&](const LanePos &p, MseLoss<VEC> &loss) {
+        loss.scale = scale;
+        const int64_t opix = p.b * a.o_bs + p.pix;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        Ld<float, VEC>::template load<true>(target, opix + c * a.o_cs, loss.tgt[c]);
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) go[c][j] = 0.0f;
-    }
-    backward_body_to<LIGHT, WF, VEC, MULTI, TM, false>(a, b, p, t, go, nullptr, 0,
-        [&](float (&ga)[3][VEC], float (&gn)[3][VEC], float (&gr)[VEC], float (&gm)[VEC], float (&gs)[3][VEC]) {
-            if (p.valid) store_gradients<WF, VEC, TM>(a, b, p, ga, gn, gr, gm, gs);
-        }, loss);
-    const float mine = p.valid ? loss.sq : 0.0f;
-    const float total = wave_sum(mine);
-    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+        for (int c = 0; c < 3; ++c) Ld<float, VEC>::template load<true>(target, opix + c * a.o_cs, loss.tgt[c]);
+    });
 }
 
 // The streamed form (fp16 maps, one light, whole 128-pixel tiles: ct_backward.hip stream_run): cook_torrance_backward_stream_kernel's schedule --
@@ -139,10 +120,8 @@ __global__ __launch_bounds__(256) void scale_list_kernel(ScaleList l, const floa
     }
 }
 
-using MseFn = void (*)(const KArgs, const BArgs, const float *, float, float *);
-
 template <int L, int W>
-static MseFn pick_mse(bool half_maps, int vec, bool multi) {
+static LossStepFn pick_mse(bool half_maps, int vec, bool multi) {
     if (half_maps) {
         if (vec == 2) return multi ? cook_torrance_mse_step_kernel<L, W, 2, true, __half> : cook_torrance_mse_step_kernel<L, W, 2, false, __half>;
         return multi ? cook_torrance_mse_step_kernel<L, W, 1, true, __half> : cook_torrance_mse_step_kernel<L, W, 1, false, __half>;
@@ -157,8 +136,6 @@ static MseStreamFn pick_mse_stream(const pbr_render_desc *d, bool full) {
         return full ? cook_torrance_mse_stream_kernel<L(), W(), true> : cook_torrance_mse_stream_kernel<L(), W(), false>;
     });
 }
-int stream_run(const pbr_render_desc *d, const void *grad_out, void *const g[5]);      // ct_backward.hip: rounds of the streamed form, 0 = does not qualify
-
 // Pixels per lane: the loss is a sum over pixels, so no lane may see a pixel twice (the overlapping last lane of a ragged row,
 // lane_pos: dup): two when the width is even, else one.  Two also for fp32 maps with one light, where the backward kernel takes
 // four: with the target pixels on top the four-pixel body needs 256 VGPRs + 21 AGPRs (one wave per SIMD; held to two waves it
@@ -191,9 +168,38 @@ static int finish_mse(float *partials, int64_t n_partials, StageTiles &&stage_of
     return launch_status();
 }
 
-// For the light-stack step (ct_stack.hip): the same two reduction kernels over ITS partial sums, the stage block at the same place.
+// For untiled maps, the light-stack steps (ct_stack.hip) included: the stage block behind the partials of one pixel per lane, the most workgroups
+// any launch of this descriptor has.
 int mse_finish(const pbr_render_desc *d, float *partials, int64_t n_partials, double count, float *loss, hipStream_t st) {
     return finish_mse(partials, n_partials, [&] { return mse_tiles(d, 1); }, count, loss, st);
+}
+
+// What every loss step asks before anything else, in this order: a valid descriptor, the caller's pointers, an fp32 result (the target image and
+// the colour it is compared with are fp32), no NaN grid, and untiled maps -- unless the step has a tiled form (`tiled_form`) that serves them.
+int mse_gate(const pbr_render_desc *d, bool pointers_given, bool tiled_form) {
+    const int rc = validate(d);
+    if (rc != PBR_OK) return rc;
+    if (!pointers_given) return PBR_ERR_NULL_MAP;
+    if (d->out_dtype != PBR_F32) return PBR_ERR_DTYPE;
+    if (nan_light_size(d) || (is_tiled(d) && !(tiled_form && repeat_loss_serves(d)))) return PBR_ERR_UNSUPPORTED;
+    return PBR_OK;
+}
+
+// The launch of a one-wave loss step (ct_backward.hpp: loss_step): `vec` pixels per lane (mse_vec) in 64-lane workgroups, one partial sum per
+// workgroup, no LDS reduction; target and gradient planes are contiguous (the stack's strides follow from o_cs and n_lights); scale = 2 / count.
+// With a row of light / view sums per workgroup (b.g_param_partials) never more workgroups than the size query promised.  Leaves the launch's
+// KArgs in `k` (n_tiles = the partial sums to finish, dev for param_grad_finish).
+int launch_loss_step(const pbr_render_desc *d, LossStepFn fn, int vec, const BArgs &b, const void *targets, double count, float *partials,
+                     hipStream_t st, KArgs &k) {
+    fill_args(d, vec, k, 6);
+    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
+    if (b.g_param_partials) {
+        const int64_t most = max_tiles(d);
+        if (most < 0 || k.n_tiles > most) return PBR_ERR_SHAPE;
+    }
+    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
+    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(targets), (float)(2.0 / count), partials);
+    return launch_status();
 }
 
 }  // namespace pbr
@@ -213,12 +219,8 @@ int pbr_cook_torrance_mse_step(const pbr_render_desc *d, const void *target, voi
                                void *g_metallic, void *g_specular, void *loss, void *workspace, void *stream) {
     const pbr::TuningScope tuning(d);
     using namespace pbr;
-    const int rc = validate(d);
+    const int rc = mse_gate(d, target && loss && workspace, true);
     if (rc != PBR_OK) return rc;
-    if (!target || !loss || !workspace) return PBR_ERR_NULL_MAP;
-    if (d->out_dtype != PBR_F32) return PBR_ERR_DTYPE;        // the target image and the colour it is compared with are fp32
-    if (nan_light_size(d)) return PBR_ERR_UNSUPPORTED;
-    const int vec = mse_vec(d);
     KArgs k;
     const double count = 3.0 * (double)d->batch * (double)d->height * (double)d->width;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -226,7 +228,6 @@ int pbr_cook_torrance_mse_step(const pbr_render_desc *d, const void *target, voi
     if (is_tiled(d)) {
         // MaterialBase.tile fused (base.py:524-537): the repeat-inner kernel walks the maps, compares every repeat with the target and leaves
         // MAP-sized gradients (ct_repeat_backward.hpp); launches it does not serve are the caller's to split (render, loss, folded backward)
-        if (!repeat_loss_serves(d)) return PBR_ERR_UNSUPPORTED;
         const int64_t tiles = repeat_backward_tiles(d);
         if (tiles < 0) return PBR_ERR_SHAPE;
         const int e = launch_repeat_backward(d, target, g_albedo, g_normal, g_roughness, g_metallic, g_specular, true, (float)(2.0 / count),
@@ -234,39 +235,26 @@ int pbr_cook_torrance_mse_step(const pbr_render_desc *d, const void *target, voi
         if (e != PBR_OK) return e;
         return finish_mse(partials, tiles, [&] { return tiles; }, count, static_cast<float *>(loss), st);      // (tiles = repeat_backward_tiles(d))
     }
-    const auto largest = [&] { return mse_tiles(d, 1); };      // one pixel per lane: the most workgroups any launch of this descriptor has
     void *const gs[5] = {g_albedo, g_normal, g_roughness, g_metallic, g_specular};
+    int e;
+    int64_t n_partials;
     if (const int rounds = g_mse_stream ? stream_run(d, target, gs) : 0) {      // fp16 maps, one light: the streamed form
-        fill_args(d, 2, k, 6);
-        k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
-        const BArgs b = {target, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
-        const int tiles = (int)(k.o_cs / 128);
-        const bool spec = d->workflow == PBR_WORKFLOW_SPECULAR;
-        const int n_stores = (g_albedo ? 3 : 0) + (g_normal && d->normal.data ? 3 : 0) + (g_roughness ? 1 : 0) +
-                             (spec ? (g_specular ? 3 : 0) : (g_metallic ? 1 : 0));
-        // every run-time flag on and every gradient wanted: the instantiation without flag branches (as in ct_backward.hip)
-        const bool full = d->albedo_is_srgb && d->return_srgb && d->normal.data && g_albedo && g_normal && g_roughness &&
-                          (spec ? (g_specular && d->specular_is_srgb) : (g_metallic && (d->workflow == PBR_WORKFLOW_METALLIC || d->specular_is_srgb)));
         // (the allocator is ALLOWED two waves per SIMD and lands on 138-167 VGPRs: three fit, and the grid is sized for three)
-        int64_t per_material = ((int64_t)resident_cus() * 4 * kStreamWavesPerSimd * rounds + d->batch - 1) / d->batch;
-        if (per_material > tiles) per_material = tiles;
-        if (per_material < 1) per_material = 1;
-        const int64_t n_partials = per_material * d->batch;             // <= tiles * batch <= the workgroups of the one-tile form
-        hipLaunchKernelGGL(pick_mse_stream(d, full), dim3((unsigned)per_material, (unsigned)d->batch, 1), dim3(64, 1, 1), 0, st, k, b, tiles, n_stores,
-                           (float)(2.0 / count), partials);
-        const int e = launch_status();
-        return e != PBR_OK ? e : finish_mse(partials, n_partials, largest, count, static_cast<float *>(loss), st);
+        const StreamLaunch s = stream_launch_shape(d, gs, rounds, k);
+        const BArgs b = {target, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
+        n_partials = s.per_material * d->batch;                         // <= tiles * batch <= the workgroups of the one-tile form
+        hipLaunchKernelGGL(pick_mse_stream(d, s.full), dim3((unsigned)s.per_material, (unsigned)d->batch, 1), dim3(64, 1, 1), 0, st, k, b, s.tiles,
+                           s.n_stores, (float)(2.0 / count), partials);
+        e = launch_status();
+    } else {
+        const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
+        const int vec = mse_vec(d);
+        const bool multi = d->n_lights > 1, half_maps = d->map_dtype == PBR_F16;
+        const LossStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> LossStepFn { return pick_mse<L(), W()>(half_maps, vec, multi); });
+        e = launch_loss_step(d, fn, vec, b, target, count, partials, st, k);
+        n_partials = k.n_tiles;
     }
-    fill_args(d, vec, k, 6);                                  // one-wave workgroups: one partial sum per workgroup, no LDS reduction
-    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
-    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;     // target and gradient planes are contiguous
-    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
-    const bool multi = d->n_lights > 1, half_maps = d->map_dtype == PBR_F16;
-    const MseFn fn = with_light_workflow(d, [&](auto L, auto W) -> MseFn { return pick_mse<L(), W()>(half_maps, vec, multi); });
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(target),
-                       (float)(2.0 / count), partials);
-    const int e = launch_status();
-    return e != PBR_OK ? e : finish_mse(partials, k.n_tiles, largest, count, static_cast<float *>(loss), st);
+    return e != PBR_OK ? e : mse_finish(d, partials, n_partials, count, static_cast<float *>(loss), st);
 }
 
 int pbr_scale_by_device_scalar(void *data, size_t n, int dtype, const void *scalar, void *stream) {

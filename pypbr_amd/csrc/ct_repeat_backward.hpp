@@ -164,6 +164,8 @@ __device__ __forceinline__ void repeat_backward_body(const KArgs &a, const BArgs
     const int PH = a.map_h;                                                        // the period of the map's rows
     if (!LOSS && a.H != PH) repeat_window(a, p);                                   // a thin band: the walk's rows are a cyclic window of the map's (ct_kernel.hpp)
     Texels<VEC> t;
+    // load_texels' dispatch, written out: with the call in its place the register allocation of the fp16 bodies moves -- the point / metallic
+    // loss instantiation spills 12 bytes per lane, two blend-free ones gain 2-4 VGPRs -- for no other change
     if constexpr (sizeof(TM) == 4) {
         load_texels<WF, TM, VEC, true>(a, a.has_normal != 0, p, t);
     } else if (p.sb) {

@@ -13,7 +13,8 @@
 // 76 L + 96 (L - 1).  Here the maps are read once, the L targets once, and the summed gradients are written once: 64 + 12 L.  At L = 8 that is
 // 160 against 1280.
 //
-// The step is backward_body_to (ct_backward.hpp) with the StackMseLoss policy: texels loaded and decoded once, pixel_terms once, then per light
+// The step is the frame of the one-wave loss steps (ct_backward.hpp: loss_step; host side ct_loss.hip: mse_gate, launch_loss_step, mse_finish)
+// around backward_body_to with the StackMseLoss policy: texels loaded and decoded once, pixel_terms once, then per light
 // eval_light -> encode with slope -> difference to THAT light's target -> backprop_light into the shared accumulators, and the light-independent
 // tail and the stores once.  No second pass over the lights: the summed-lights form needs one because the summed colour decides the outer clamp;
 // in a stack every image is clamped and encoded by itself.  Light l + 1's target pixels are loaded before light l's arithmetic.
@@ -74,105 +75,46 @@ void cook_torrance_stack_kernel(const KArgs a) {
 }
 
 // ------------------------------------------------------------------ the loss step over the stack
-// One-wave workgroups like cook_torrance_mse_step_kernel: one partial sum per workgroup, no LDS.  Lanes outside the map shade a clamped
-// position (every lane reaches the wave sum), store nothing and contribute nothing.
-// Registers: the two-pixel body lands on 184-216 VGPRs (two waves per SIMD), the one-pixel body on 95-114 (four); held to three waves (168)
-// every two-pixel instantiation spills 28-176 bytes per lane, so the allocation is left to the compiler.
-template <int LIGHT, int WF, int VEC, typename TM>
+// One kernel over the frame of the one-wave loss steps (ct_backward.hpp: loss_step) with the StackMseLoss policy: one partial sum per workgroup,
+// no LDS reduction; lanes outside the map shade a clamped position (every lane reaches the wave sum), store nothing and contribute nothing.
+// Pixels per lane: mse_vec.
+//   PGRAD = false, the stack step.  Registers: the two-pixel body lands on 184-216 VGPRs (two waves per SIMD), the one-pixel body on 95-114
+//   (four); held to three waves (168) every two-pixel instantiation spills 28-176 bytes per lane, so the allocation is left to the compiler
+//   (DESIGN.md 3.14).
+//   PGRAD = true, the stack-fit step: backward_body_to also forms the adjoints of view, light l and intensity l (backprop_light<LIGHT, true>),
+//   light l's six sums leave the lane inside the run-time light loop (wave_sum8 -> the workgroup's LDS row), the view's three after the tail,
+//   and the row -- 3 + 6 L floats: view, lights L x 3, intensities L x 3, the layout of pbr_cook_torrance_backward_params -- goes to
+//   b.g_param_partials.  One wave per workgroup: the order of additions is fixed.  Lanes outside the map shade a clamped position and here,
+//   unlike in the backward kernels, would form a real upstream gradient from a real target: their scale is 0, so every adjoint they hold is
+//   exactly 0.  Registers: the two-pixel body lands on 200-236 VGPRs (two waves per SIMD, as the stack step's 184-216), the one-pixel body on
+//   125-146 (three or four); no instantiation has scratch.
+template <int LIGHT, int WF, int VEC, typename TM, bool PGRAD>
 __global__ __launch_bounds__(64)
 void cook_torrance_mse_stack_step_kernel(const KArgs a, const BArgs b, const float *__restrict__ targets, float scale, float *__restrict__ partials) {
-    const uint32_t tile = tile_of_workgroup(a, blockIdx.x);
-    const int ty = (int)a.div_tx.div(tile);
-    const LanePos p = lane_pos<VEC, true>(a, (int)tile - ty * a.tiles_x, ty);
     // one pixel group per lane (a packed pair or one pixel): the body's light loop runs once, so the one-light-ahead target loads stay in step
     static_assert(VEC == 1 || (VEC == 2 && PBR_MSE_PACKED), "StackMseLoss walks the lights once per lane");
-    Texels<VEC> t;
-    StackMseLoss<VEC> loss;
-    loss.scale = scale;
-    loss.sq = 0.0f;
-    loss.plane = a.o_cs;
-    loss.lane = targets + ((int64_t)p.b * a.n_lights * 3 * a.o_cs + p.pix);       // 64-bit: B L 3 H W passes 2^31 long before a plane does
-    float go[3][VEC];                                                              // unused by the loss policies
-    if constexpr (sizeof(TM) == 4) {
-        load_texels<WF, TM, VEC, true>(a, a.has_normal != 0, p, t);
-    } else if (p.sb) {
-        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, true, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, true, false>(a, p, t);
-    } else {
-        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, false, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, false, false>(a, p, t);
+    float *s_param = nullptr;
+    int n_param = 0;
+    if constexpr (PGRAD) {
+        __shared__ float s_row[3 + 6 * PBR_MAX_LIGHTS];
+        s_param = s_row;
+        n_param = 3 + 6 * a.n_lights;
+        for (int i = threadIdx.x; i < n_param; i += 64) s_param[i] = 0.0f;      // a 16-light row holds 99 floats: more than the wave has lanes
+        __syncthreads();
     }
-    loss.prefetch(0);
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) go[c][j] = 0.0f;
-    backward_body_to<LIGHT, WF, VEC, false, TM, false>(a, b, p, t, go, nullptr, 0,
-        [&](float (&ga)[3][VEC], float (&gn)[3][VEC], float (&gr)[VEC], float (&gm)[VEC], float (&gs)[3][VEC]) {
-            if (p.valid) store_gradients<WF, VEC, TM>(a, b, p, ga, gn, gr, gm, gs);
-        }, loss);
-    const float mine = p.valid ? loss.sq : 0.0f;
-    const float total = wave_sum(mine);
-    if (threadIdx.x == 0) partials[blockIdx.x] = total;
+    loss_step<LIGHT, WF, VEC, false, TM, PGRAD, StackMseLoss<VEC>>(a, b, s_param, n_param, partials, [&](const LanePos &p, StackMseLoss<VEC> &loss) {
+        loss.scale = scale;
+        if constexpr (PGRAD) loss.scale = p.valid ? scale : 0.0f;                  // a lane outside the map: every adjoint it holds is exactly 0
+        loss.plane = a.o_cs;
+        loss.lane = targets + ((int64_t)p.b * a.n_lights * 3 * a.o_cs + p.pix);   // 64-bit: B L 3 H W passes 2^31 long before a plane does
+        loss.prefetch(0);
+    });
 }
 
-// ------------------------------------------------------------------ the loss step over the stack, with the lights' and the view's gradients
-// The stack step with PGRAD: backward_body_to also forms the adjoints of view, light l and intensity l (backprop_light<LIGHT, true>), light l's
-// six sums leave the lane inside the run-time light loop (wave_sum8 -> the workgroup's LDS row), the view's three after the tail, and the row --
-// 3 + 6 L floats: view, lights L x 3, intensities L x 3, the layout of pbr_cook_torrance_backward_params -- goes to b.g_param_partials.  One wave
-// per workgroup: the order of additions is fixed.  Lanes outside the map shade a clamped position and here, unlike in the backward kernels, would
-// form a real upstream gradient from a real target: their scale is 0, so every adjoint they hold is exactly 0.
-// Pixels per lane: mse_vec, as the stack step.  Registers: the two-pixel body lands on 200-236 VGPRs (two waves per SIMD, as the stack step's
-// 184-216), the one-pixel body on 125-146 (three or four); no instantiation has scratch.
-template <int LIGHT, int WF, int VEC, typename TM>
-__global__ __launch_bounds__(64)
-void cook_torrance_mse_stack_fit_step_kernel(const KArgs a, const BArgs b, const float *__restrict__ targets, float scale, float *__restrict__ partials) {
-    const uint32_t tile = tile_of_workgroup(a, blockIdx.x);
-    const int ty = (int)a.div_tx.div(tile);
-    const LanePos p = lane_pos<VEC, true>(a, (int)tile - ty * a.tiles_x, ty);
-    static_assert(VEC == 1 || (VEC == 2 && PBR_MSE_PACKED), "StackMseLoss walks the lights once per lane");
-    __shared__ float s_param[3 + 6 * PBR_MAX_LIGHTS];
-    const int n_param = 3 + 6 * a.n_lights;
-    for (int i = threadIdx.x; i < n_param; i += 64) s_param[i] = 0.0f;      // a 16-light row holds 99 floats: more than the wave has lanes
-    __syncthreads();
-    Texels<VEC> t;
-    StackMseLoss<VEC> loss;
-    loss.scale = p.valid ? scale : 0.0f;
-    loss.sq = 0.0f;
-    loss.plane = a.o_cs;
-    loss.lane = targets + ((int64_t)p.b * a.n_lights * 3 * a.o_cs + p.pix);
-    float go[3][VEC];                                                              // unused by the loss policies
-    if constexpr (sizeof(TM) == 4) {
-        load_texels<WF, TM, VEC, true>(a, a.has_normal != 0, p, t);
-    } else if (p.sb) {
-        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, true, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, true, false>(a, p, t);
-    } else {
-        if (a.has_normal) load_texels_fixed<WF, TM, VEC, true, false, true>(a, p, t); else load_texels_fixed<WF, TM, VEC, true, false, false>(a, p, t);
-    }
-    loss.prefetch(0);
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) go[c][j] = 0.0f;
-    backward_body_to<LIGHT, WF, VEC, false, TM, true>(a, b, p, t, go, s_param, n_param,
-        [&](float (&ga)[3][VEC], float (&gn)[3][VEC], float (&gr)[VEC], float (&gm)[VEC], float (&gs)[3][VEC]) {
-            store_gradients<WF, VEC, TM>(a, b, p, ga, gn, gr, gm, gs);             // (the body returns before the sink for lanes outside the map)
-        }, loss);
-    const float mine = p.valid ? loss.sq : 0.0f;
-    const float total = wave_sum(mine);
-    if (threadIdx.x == 0) partials[blockIdx.x] = total;
-}
-
-using StackStepFn = void (*)(const KArgs, const BArgs, const float *, float, float *);
-
-template <int L, int W>
-static StackStepFn pick_stack_fit_step(bool half_maps, int vec) {
-    if (half_maps) return vec == 2 ? cook_torrance_mse_stack_fit_step_kernel<L, W, 2, __half> : cook_torrance_mse_stack_fit_step_kernel<L, W, 1, __half>;
-    return vec == 2 ? cook_torrance_mse_stack_fit_step_kernel<L, W, 2, float> : cook_torrance_mse_stack_fit_step_kernel<L, W, 1, float>;
-}
-
-template <int L, int W>
-static StackStepFn pick_stack_step(bool half_maps, int vec) {
-    if (half_maps) return vec == 2 ? cook_torrance_mse_stack_step_kernel<L, W, 2, __half> : cook_torrance_mse_stack_step_kernel<L, W, 1, __half>;
-    return vec == 2 ? cook_torrance_mse_stack_step_kernel<L, W, 2, float> : cook_torrance_mse_stack_step_kernel<L, W, 1, float>;
+template <int L, int W, bool PGRAD>
+static LossStepFn pick_stack_step(bool half_maps, int vec) {
+    if (half_maps) return vec == 2 ? cook_torrance_mse_stack_step_kernel<L, W, 2, __half, PGRAD> : cook_torrance_mse_stack_step_kernel<L, W, 1, __half, PGRAD>;
+    return vec == 2 ? cook_torrance_mse_stack_step_kernel<L, W, 2, float, PGRAD> : cook_torrance_mse_stack_step_kernel<L, W, 1, float, PGRAD>;
 }
 
 template <int L, int W>
@@ -217,31 +159,24 @@ int pbr_cook_torrance_mse_stack_step(const pbr_render_desc *d, const void *targe
                                      void *g_metallic, void *g_specular, void *loss, void *workspace, void *stream) {
     using namespace pbr;
     const TuningScope tuning(d);
-    int rc = validate(d);
+    const int rc = mse_gate(d, targets && loss && workspace, false);
     if (rc != PBR_OK) return rc;
-    if (!targets || !loss || !workspace) return PBR_ERR_NULL_MAP;
-    if (d->out_dtype != PBR_F32) return PBR_ERR_DTYPE;        // the target images and the colours they are compared with are fp32
-    if (is_tiled(d) || nan_light_size(d)) return PBR_ERR_UNSUPPORTED;
-    const int vec = mse_vec(d);                               // two pixels per lane for even widths, else one: no lane counts a pixel twice
-    KArgs k;
-    fill_args(d, vec, k, 6);                                  // one-wave workgroups: one partial sum per workgroup
-    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
-    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;     // gradient planes are contiguous; the targets' strides follow from o_cs and n_lights
+    const int vec = mse_vec(d);
+    const bool half_maps = d->map_dtype == PBR_F16;
+    const LossStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> LossStepFn { return pick_stack_step<L(), W(), false>(half_maps, vec); });
     const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *const partials = static_cast<float *>(workspace);
     const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const StackStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> StackStepFn { return pick_stack_step<L(), W()>(half_maps, vec); });
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(targets), (float)(2.0 / count), partials);
-    const int e = launch_status();
+    KArgs k;
+    const int e = launch_loss_step(d, fn, vec, b, targets, count, partials, st, k);
     return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
 }
 
 size_t pbr_mse_stack_fit_workspace_bytes(const pbr_render_desc *d) {
     using namespace pbr;
     const TuningScope tuning(d);
-    if (validate(d) != PBR_OK || d->out_dtype != PBR_F32 || is_tiled(d) || nan_light_size(d)) return 0;
+    if (mse_gate(d, true, false) != PBR_OK) return 0;
     const size_t loss_part = pbr_mse_step_workspace_bytes(d);      // the loss partials and their stage sums, then the rows, then their stage sums
     return loss_part == 0 ? 0 : loss_part + param_rows_bytes(d) + param_stage_bytes(d);
 }
@@ -250,26 +185,18 @@ int pbr_cook_torrance_mse_stack_fit_step(const pbr_render_desc *d, const void *t
                                          void *g_metallic, void *g_specular, void *g_params, void *loss, void *workspace, void *stream) {
     using namespace pbr;
     const TuningScope tuning(d);
-    int rc = validate(d);
+    const int rc = mse_gate(d, g_params && targets && loss && workspace, false);
     if (rc != PBR_OK) return rc;
-    if (!g_params || !targets || !loss || !workspace) return PBR_ERR_NULL_MAP;
-    if (d->out_dtype != PBR_F32) return PBR_ERR_DTYPE;
-    if (is_tiled(d) || nan_light_size(d)) return PBR_ERR_UNSUPPORTED;
+    const int vec = mse_vec(d);
     const bool half_maps = d->map_dtype == PBR_F16;
-    const int vec = mse_vec(d);                               // sums over pixels: no lane may count a pixel twice
-    KArgs k;
-    fill_args(d, vec, k, 6);                                  // one-wave workgroups: one partial sum and one parameter row per workgroup
-    const int64_t most = max_tiles(d);
-    if (k.n_tiles < 0 || most < 0 || k.n_tiles > most) return PBR_ERR_SHAPE;      // never past what the size query promised
-    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
+    const LossStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> LossStepFn { return pick_stack_step<L(), W(), true>(half_maps, vec); });
     const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *const partials = static_cast<float *>(workspace);
-    float *const rows = reinterpret_cast<float *>(static_cast<char *>(workspace) + pbr_mse_step_workspace_bytes(d));
+    float *const rows = reinterpret_cast<float *>(static_cast<char *>(workspace) + pbr_mse_step_workspace_bytes(d));      // one row per workgroup
     const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, rows};
-    const StackStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> StackStepFn { return pick_stack_fit_step<L(), W()>(half_maps, vec); });
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(targets), (float)(2.0 / count), partials);
-    int e = launch_status();
+    KArgs k;
+    int e = launch_loss_step(d, fn, vec, b, targets, count, partials, st, k);
     if (e == PBR_OK) e = param_grad_finish(d, rows, k.n_tiles, k.dev, static_cast<float *>(g_params), st);
     return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
 }

@@ -31,6 +31,10 @@ sibling modules, one per file of csrc/, and their names are imported back below,
   functional    descriptors, RenderPlan, cook_torrance, the autograd bridges, rendering_loss_mse,       csrc/ct_*.hip/.hpp, torch_ops.cpp
                 light stacks (cook_torrance_stack, rendering_loss_mse_stack)
 
+The one-pass loss steps (_MseStepFn, _MseStackStepFn, _MseStackFitFn) are three autograd classes over one frame, said once in front of
+_MseStepFn: two predicates for the callers (_shared_by_batch, _plain_kwargs), one launch (_step_plan, _launch_loss_step), one ctx idiom
+(_keep_step, _kept_step) and the one scaling launch (_scale_step_gradients).
+
 Imports run one way: _native / _caches -> _dispatch -> _upload -> the family modules -> functional.
 """
 # Settings are assigned on the module that READS them.  USE_TORCH_OPS and DEVICE_PARAMETERS are read here.  PINNED_RESULT_CAP,
@@ -526,7 +530,7 @@ def _fused_blend_backward_can_take(albedo, kw) -> bool:
         # the library answers the rest when the plan exists (pbr_blend_backward_serves: one light, map rows of whole 4-texel groups, a whole
         # output or a band that holds a period of the map's rows) -- _FusedBlendFn.forward raises _StepNotServed and the unfused pieces run
         B = albedo.shape[0] if albedo.dim() == 4 else 1
-        if B > 1 and any(t.dim() < 4 or t.shape[0] == 1 for t in tensors):
+        if any(_shared_by_batch(t, B) for t in tensors):
             return False
     return True
 
@@ -792,8 +796,102 @@ class _CookTorranceFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------ the rendering-loss step as one kernel
+# The three steps -- _MseStepFn (one image per material), _MseStackStepFn (a stack of L images), _MseStackFitFn (the stack, with the gradients of
+# view / lights / intensities) -- share one frame:
+#   _shared_by_batch, _plain_kwargs   what the callers ask before they route a call to a step
+#   _step_plan, _launch_loss_step     plan without a result; targets, gradient buffers, loss, workspace and the ONE launch
+#   _keep_step, _kept_step            forward keeps the gradients in ctx; backward hands them over, or evaluates again when they are gone
+#   _scale_step_gradients             the gradients times the upstream gradient of the loss, on the device
+# A step class is its forward (which plan, which inputs are differentiable) and what its backward returns.
 class _StepNotServed(Exception):
     """pbr_cook_torrance_mse_step does not serve this descriptor as one pass (raised before anything is launched)."""
+
+
+def _shared_by_batch(t, B: int) -> bool:
+    """A map (or mask) that B > 1 materials share: it has no batch dimension, or one of size 1.  Its gradient is a sum over the batch, which
+    the one-pass steps do not form."""
+    return t is not None and B > 1 and (t.dim() < 4 or t.shape[0] == 1)
+
+
+# what a keyword argument may be for a one-pass step to serve the call; anything else (an explicit result, a blend, a row band ...) is not plain
+_PLAIN = {"out": (None,), "blend": (None,), "blend_flags": (None,), "rows": (None,), "height_total": (None,), "y_offset": (None, 0),
+          "autotune": (None, False), "out_dtype": (None, torch.float32), "tile": (1, (1, 1))}
+
+
+def _plain_kwargs(kw, excluded) -> bool:
+    """The keyword arguments are plain for a one-pass step: each of the keys the caller excludes -- it drops them before it plans -- is absent
+    or says nothing."""
+    for k in excluded:
+        if k in kw and kw[k] not in _PLAIN[k]:
+            return False
+    return True
+
+
+_STEP_EXCLUDED = ("out", "blend", "out_dtype", "autotune", "rows")                       # rendering_loss_mse: tiles and row bands are the library's to answer
+_STACK_EXCLUDED = _STEP_EXCLUDED + ("blend_flags", "height_total", "y_offset", "tile")   # light stacks: whole untiled maps
+
+
+def _step_plan(maps, kwargs, params=None):
+    """The plan of a loss step: the colours are never written."""
+    if params is not None:
+        kwargs = dict(kwargs, view_dir=params[0], light=params[1], light_intensity=params[2])
+    plan = plan_cook_torrance(*[None if t is None else t.detach() for t in maps], **kwargs)
+    plan.out = None
+    return plan
+
+
+# kind -> (entry point, workspace query); the stack kinds take [B,L,3,H,W] targets, "fit" also leaves the 3 + 6 L parameter gradients
+_STEP_KINDS = {"step": ("pbr_cook_torrance_mse_step", "pbr_mse_step_workspace_bytes"),
+               "stack": ("pbr_cook_torrance_mse_stack_step", "pbr_mse_step_workspace_bytes"),
+               "fit": ("pbr_cook_torrance_mse_stack_fit_step", "pbr_mse_stack_fit_workspace_bytes")}
+
+
+def _launch_loss_step(kind, plan, maps, targets, wanted):
+    """ONE launch of a loss step -> (gradient buffers | None per map, parameter gradients [3 + 6 L] | None, loss).  Raises _StepNotServed
+    before anything is launched when the library does not serve the descriptor as one pass (e.g. tiled maps with several lights)."""
+    entry, query = _STEP_KINDS[kind]
+    d = plan.desc
+    dev = plan.device                                       # the maps' device: targets handed over on the CPU, or on another GPU, are brought here
+    lights = () if kind == "step" else (d.n_lights,)
+    tgt = targets.detach().to(dev, torch.float32).reshape(d.batch, *lights, 3, d.height, d.width).contiguous()    # H x W: the OUTPUT (tiled maps: all repeats)
+    gdtype = torch.float32 if d.map_dtype == N.F32 else torch.float16
+    present = (True, bool(d.normal.data), True, bool(d.metallic.data), bool(d.specular.data))
+    # in the map's OWN shape ([C,H,W] or [B,C,H,W]: the same memory layout), so that backward returns the buffer itself, not a view of
+    # it -- autograd takes ownership of such a gradient instead of cloning it (a 4096^2 fp16 albedo: 73 us per step)
+    bufs = [torch.empty(tuple(maps[i].shape), dtype=gdtype, device=dev) if wanted[i] and present[i] else None for i in range(5)]
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    gp = torch.empty(3 + 6 * d.n_lights, dtype=torch.float32, device=dev) if kind == "fit" else None
+    lib = N.lib()
+    ws_bytes = getattr(lib, query)(ctypes.byref(d))
+    if ws_bytes == 0:
+        raise _StepNotServed()
+    ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev)      # at least the bytes asked for, 8-byte aligned
+    launch(dev, getattr(lib, entry), ctypes.byref(d), tgt.data_ptr(), *[ptr(b) for b in bufs], *([] if gp is None else [gp.data_ptr()]),
+           loss.data_ptr(), ws.data_ptr())
+    if kind != "step":
+        STACK_LAUNCHES[entry[len("pbr_cook_torrance_"):]] += 1
+    return bufs, gp, loss
+
+
+def _keep_step(ctx, kind, maps, targets, kwargs, wanted, kept, params=None):
+    """Forward's bookkeeping: the gradients the launch left stay in ctx until backward hands them over.  The plan (descriptor + strong
+    references to every map) is NOT kept: a second backward rebuilds it from the saved tensors."""
+    ctx.kind, ctx.kwargs, ctx.wanted, ctx.grads, ctx.params = kind, kwargs, wanted, kept, params
+    ctx.present = [t is not None for t in maps]
+    ctx.save_for_backward(*[t for t in maps if t is not None], targets)
+
+
+def _kept_step(ctx):
+    """Backward's side: (gradient buffers, parameter gradients | None), given away -- autograd may keep the very buffers (e.g. as .grad).
+    Differentiated again (retain_graph=True on the earlier backward) the first call gave them away, so the step is evaluated once more for
+    fresh ones: the common single backward never pays for a copy."""
+    saved = ctx.saved_tensors                               # in-place edits of the maps since forward are detected, as for any op
+    kept, ctx.grads = ctx.grads, None
+    if kept is None:
+        it = iter(saved[:-1])
+        maps = [next(it) if p else None for p in ctx.present]
+        kept = _launch_loss_step(ctx.kind, _step_plan(maps, ctx.kwargs, ctx.params), maps, saved[-1], ctx.wanted)[:2]
+    return kept
 
 
 def _scale_step_gradients(grads, grad_loss):
@@ -812,26 +910,6 @@ class _MseStepFn(torch.autograd.Function):
     evaluates, compares and differentiates in a single pass over the maps (32 + 12 bytes read, 32 written per pixel) and keeps
     the four gradients; backward hands them over, scaled by the upstream gradient on the device (no host synchronisation; a
     scalar of exactly 1 -- `loss.backward()` -- costs one early-out launch per map)."""
-
-    @staticmethod
-    def _launch(plan, target, maps, wanted):
-        """One pbr_cook_torrance_mse_step: -> (loss, gradient buffers in the maps' own shapes | None)."""
-        d = plan.desc
-        B, H, W = d.batch, d.height, d.width
-        dev = plan.device                                   # the maps' device: a target handed over on the CPU, or on another GPU, is brought here
-        tgt = target.detach().to(dev, torch.float32).reshape(B, 3, H, W).contiguous()       # H x W: the OUTPUT (tiled maps: all repeats)
-        gdtype = torch.float32 if d.map_dtype == N.F32 else torch.float16
-        # in the map's OWN shape ([C,H,W] or [B,C,H,W]: the same memory layout), so that backward returns the buffer itself, not a view of
-        # it -- autograd takes ownership of such a gradient instead of cloning it (a 4096^2 fp16 albedo: 73 us per step)
-        bufs = [torch.empty(tuple(maps[i].shape), dtype=gdtype, device=dev) if wanted[i] else None for i in range(5)]
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        lib = N.lib()
-        ws_bytes = lib.pbr_mse_step_workspace_bytes(ctypes.byref(d))
-        if ws_bytes == 0:                                   # e.g. tiled maps with several lights or ragged map rows: not one pass (pbr_hip.h)
-            raise _StepNotServed()
-        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=dev)
-        launch(dev, lib.pbr_cook_torrance_mse_step, ctypes.byref(d), tgt.data_ptr(), *[ptr(b) for b in bufs], loss.data_ptr(), ws.data_ptr())
-        return loss, bufs
 
     # A training loop calls the step with the SAME leaf tensors every iteration (the optimiser updates them in place): the filled
     # descriptor of the last step is kept -- pointers, never values of maps -- keyed on the very tensors (weakly held: a dropped material
@@ -882,13 +960,10 @@ class _MseStepFn(torch.autograd.Function):
                             del _MseStepFn._PLANS[key]
             kept = plan is not None
             if plan is None:
-                plan = plan_cook_torrance(*[None if t is None else t.detach() for t in maps], **kwargs)
-                plan.out = None                                 # the colour is never written
-            d = plan.desc
-            present = (True, bool(d.normal.data), True, bool(d.metallic.data), bool(d.specular.data))
-            wanted = [bool(ctx.needs_input_grad[i] and present[i] and maps[i] is not None) for i in range(5)]
+                plan = _step_plan(maps, kwargs)
+            wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
             try:
-                loss, bufs = _MseStepFn._launch(plan, target, maps, wanted)
+                bufs, _, loss = _launch_loss_step("step", plan, maps, target, wanted)
             except _StepNotServed:
                 if kept:                                        # never again through the cache: the fallback must not meet it on every call
                     with _MseStepFn._LOCK:
@@ -903,25 +978,12 @@ class _MseStepFn(torch.autograd.Function):
         finally:
             if hit is not None:
                 hit.release()
-        # the plan (descriptor + strong references to every map) is NOT kept: a second backward rebuilds it from the saved tensors
-        ctx.kwargs, ctx.wanted, ctx.grads = kwargs, wanted, bufs
-        ctx.present = [t is not None for t in maps]
-        ctx.save_for_backward(*[t for t in maps if t is not None], target)
+        _keep_step(ctx, "step", maps, target, kwargs, wanted, (bufs, None))
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
-        saved = ctx.saved_tensors                           # in-place edits of the maps since forward are detected, as for any op
-        grads = ctx.grads
-        ctx.grads = None                                    # handed over below: autograd may keep the very buffers (e.g. as .grad)
-        if grads is None:
-            # differentiated again (retain_graph=True on the earlier backward): the first call gave its buffers away, so the step is
-            # evaluated once more for fresh ones -- the common single backward never pays for a copy
-            it = iter(saved[:-1])
-            maps = [next(it) if p else None for p in ctx.present]
-            plan = plan_cook_torrance(*[None if t is None else t.detach() for t in maps], **ctx.kwargs)
-            plan.out = None
-            _, grads = _MseStepFn._launch(plan, saved[-1], maps, ctx.wanted)
+        grads, _ = _kept_step(ctx)
         _scale_step_gradients(grads, grad_loss)
         return (*grads, None, None)
 
@@ -939,13 +1001,11 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
     grad_maps = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in maps)
     grad_other = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in params + (target,))
     B = albedo.shape[0] if albedo.dim() == 4 else 1
-    shared = any(t is not None and B > 1 and (t.dim() == 3 or t.shape[0] == 1) for t in maps)
-    plain = all(kwargs.get(k) in (None, d) for k, d in (("out", None), ("blend", None), ("out_dtype", torch.float32))) and \
-        kwargs.get("rows") is None and not kwargs.get("autotune")
-    if grad_maps and not grad_other and plain and not shared and albedo.is_cuda:
+    shared = B > 1 and any(_shared_by_batch(t, B) for t in maps)
+    if grad_maps and not grad_other and _plain_kwargs(kwargs, _STEP_EXCLUDED) and not shared and albedo.is_cuda:
         # tiled maps (tile=n: MaterialBase.tile fused) take the one pass too -- the repeat-inner kernel leaves map-sized gradients -- where
         # the library serves them (one light, map rows of whole 4-texel groups); otherwise the three steps below
-        kw = {k: v for k, v in kwargs.items() if k not in ("out", "blend", "out_dtype", "autotune", "rows")}
+        kw = {k: v for k, v in kwargs.items() if k not in _STEP_EXCLUDED}
         try:
             return _MseStepFn.apply(albedo, normal, roughness, metallic, specular, target, kw)
         except _StepNotServed:
@@ -978,8 +1038,7 @@ def _stack_lights(light, light_intensity) -> Tuple[int, int]:
 
 def _stack_plain(kw) -> bool:
     """The keyword arguments of a call that pbr_cook_torrance_stack / pbr_cook_torrance_mse_stack_step serve: whole untiled maps, a fresh fp32 result."""
-    return (all(kw.get(k) is None for k in ("out", "blend", "blend_flags", "rows", "height_total")) and not kw.get("y_offset") and not kw.get("autotune")
-            and kw.get("out_dtype") in (None, torch.float32) and kw.get("tile", 1) in (1, (1, 1)))
+    return _plain_kwargs(kw, _STACK_EXCLUDED)
 
 
 def cook_torrance_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], roughness: torch.Tensor,
@@ -1020,44 +1079,16 @@ class _MseStackStepFn(torch.autograd.Function):
     gradients, backward hands them over scaled by the upstream gradient on the device; a second backward evaluates again -- as _MseStepFn."""
 
     @staticmethod
-    def _launch(maps, targets, kwargs, wanted):
-        plan = plan_cook_torrance(*[None if t is None else t.detach() for t in maps], **kwargs)
-        plan.out = None                                     # the colours are never written
-        d = plan.desc
-        dev = plan.device
-        tgt = targets.detach().to(dev, torch.float32).reshape(d.batch, d.n_lights, 3, d.height, d.width).contiguous()
-        gdtype = torch.float32 if d.map_dtype == N.F32 else torch.float16
-        present = (True, bool(d.normal.data), True, bool(d.metallic.data), bool(d.specular.data))
-        bufs = [torch.empty(tuple(maps[i].shape), dtype=gdtype, device=dev) if wanted[i] and present[i] else None for i in range(5)]
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        lib = N.lib()
-        ws_bytes = lib.pbr_mse_step_workspace_bytes(ctypes.byref(d))
-        if ws_bytes == 0:
-            raise _StepNotServed()
-        ws = torch.empty(max(1, ws_bytes // 4), dtype=torch.float32, device=dev)
-        launch(dev, lib.pbr_cook_torrance_mse_stack_step, ctypes.byref(d), tgt.data_ptr(), *[ptr(b) for b in bufs], loss.data_ptr(), ws.data_ptr())
-        STACK_LAUNCHES["mse_stack_step"] += 1
-        return loss, bufs
-
-    @staticmethod
     def forward(ctx, albedo, normal, roughness, metallic, specular, targets, kwargs):
         maps = (albedo, normal, roughness, metallic, specular)
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        loss, bufs = _MseStackStepFn._launch(maps, targets, kwargs, wanted)
-        ctx.kwargs, ctx.wanted, ctx.grads = kwargs, wanted, bufs
-        ctx.present = [t is not None for t in maps]
-        ctx.save_for_backward(*[t for t in maps if t is not None], targets)
+        bufs, _, loss = _launch_loss_step("stack", _step_plan(maps, kwargs), maps, targets, wanted)
+        _keep_step(ctx, "stack", maps, targets, kwargs, wanted, (bufs, None))
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
-        saved = ctx.saved_tensors                           # in-place edits of the maps since forward are detected, as for any op
-        grads = ctx.grads
-        ctx.grads = None                                    # handed over below: autograd may keep the very buffers
-        if grads is None:                                   # differentiated again: the first call gave its buffers away
-            it = iter(saved[:-1])
-            maps = [next(it) if p else None for p in ctx.present]
-            _, grads = _MseStackStepFn._launch(maps, saved[-1], ctx.kwargs, ctx.wanted)
+        grads, _ = _kept_step(ctx)
         _scale_step_gradients(grads, grad_loss)
         return (*grads, None, None)
 
@@ -1069,48 +1100,16 @@ class _MseStackFitFn(torch.autograd.Function):
     read-back, so a whole step captures into a graph; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
 
     @staticmethod
-    def _launch(maps, params, targets, kwargs, wanted):
-        view, light, inten = params
-        plan = plan_cook_torrance(*[None if t is None else t.detach() for t in maps], view_dir=view, light=light, light_intensity=inten, **kwargs)
-        plan.out = None                                     # the colours are never written
-        d = plan.desc
-        dev = plan.device
-        tgt = targets.detach().to(dev, torch.float32).reshape(d.batch, d.n_lights, 3, d.height, d.width).contiguous()
-        gdtype = torch.float32 if d.map_dtype == N.F32 else torch.float16
-        present = (True, bool(d.normal.data), True, bool(d.metallic.data), bool(d.specular.data))
-        bufs = [torch.empty(tuple(maps[i].shape), dtype=gdtype, device=dev) if wanted[i] and present[i] else None for i in range(5)]
-        loss = torch.empty((), dtype=torch.float32, device=dev)
-        gp = torch.empty(3 + 6 * d.n_lights, dtype=torch.float32, device=dev)
-        lib = N.lib()
-        ws_bytes = lib.pbr_mse_stack_fit_workspace_bytes(ctypes.byref(d))
-        if ws_bytes == 0:
-            raise _StepNotServed()
-        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)       # (every part of the block is a multiple of 8 bytes)
-        launch(dev, lib.pbr_cook_torrance_mse_stack_fit_step, ctypes.byref(d), tgt.data_ptr(), *[ptr(b) for b in bufs], gp.data_ptr(),
-               loss.data_ptr(), ws.data_ptr())
-        STACK_LAUNCHES["mse_stack_fit_step"] += 1
-        return loss, bufs, gp
-
-    @staticmethod
     def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs):
         maps, params = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity)
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        loss, bufs, gp = _MseStackFitFn._launch(maps, params, targets, kwargs, wanted)
-        ctx.kwargs, ctx.wanted, ctx.grads, ctx.params = kwargs, wanted, (bufs, gp), params
-        ctx.present = [t is not None for t in maps]
-        ctx.save_for_backward(*[t for t in maps if t is not None], targets)
+        bufs, gp, loss = _launch_loss_step("fit", _step_plan(maps, kwargs, params), maps, targets, wanted)
+        _keep_step(ctx, "fit", maps, targets, kwargs, wanted, (bufs, gp), params)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
-        saved = ctx.saved_tensors                           # in-place edits of the maps since forward are detected, as for any op
-        kept = ctx.grads
-        ctx.grads = None                                    # handed over below: autograd may keep the very buffers
-        if kept is None:                                    # differentiated again: the first call gave its buffers away
-            it = iter(saved[:-1])
-            maps = [next(it) if p else None for p in ctx.present]
-            _, *kept = _MseStackFitFn._launch(maps, ctx.params, saved[-1], ctx.kwargs, ctx.wanted)
-        grads, gp = kept
+        grads, gp = _kept_step(ctx)
         _scale_step_gradients(grads, grad_loss)
         k = grad_loss.detach().to(gp.device, torch.float32).reshape(1).contiguous()
         launch(gp.device, N.lib().pbr_scale_by_device_scalar, gp.data_ptr(), gp.numel(), N.F32, k.data_ptr())
@@ -1134,7 +1133,7 @@ def _stack_route(maps, params, targets, kwargs, on_device=None):
     ahead of the composition at every L measured (profiles/light_stack_fit_step.json)."""
     albedo = maps[0]
     B = albedo.shape[0] if albedo.dim() == 4 else 1
-    shared = any(t is not None and B > 1 and (t.dim() == 3 or t.shape[0] == 1) for t in maps)
+    shared = B > 1 and any(_shared_by_batch(t, B) for t in maps)
     if on_device is None:
         on_device = albedo.is_cuda
     if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets):
@@ -1167,7 +1166,7 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
     params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
     route = _stack_route(maps, params, targets, kwargs)
     if route is not None:
-        kw = {k: v for k, v in kwargs.items() if k not in ("out", "blend", "blend_flags", "out_dtype", "autotune", "rows", "height_total", "y_offset", "tile")}
+        kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED}
         try:
             if route == "fit":
                 kw = {k: v for k, v in kw.items() if k not in _PARAM_KEYS}

@@ -25,12 +25,27 @@ CACHING DEVICE_PARAMETERS ENCODED_DTYPES KeptPlan LAUNCHES Optional PADDING_MODE
     unpack_planes upload_packed version_of
 """.split()
 
+# The names functional has gained since the split (the light stacks, the height solve, the export path ...): the same command in a checkout of
+# the commit before the loss steps were put on one frame, minus PARENT_NAMES.
+GAINED_NAMES = """
+STACK_LAUNCHES _HeightFromNormalFn _MseStackFitFn _MseStackStepFn _hfn_raw _poisson_solve _scale_step_gradients _stack_lights _stack_plain
+    _stack_route cook_torrance_stack download_samples height_from_normal launch pack_image ptr rendering_loss_mse_stack
+""".split()
+
 MOVED_SETTINGS = ("PINNED_RESULT_CAP", "PLANE_SKEW_BYTES", "STAGE_MEMCPY_LIMIT", "UPLOAD_STAGE_CAP")
 
 
 def test_every_name_of_the_parent_still_resolves_on_functional():
     assert len(PARENT_NAMES) == 122 and PARENT_NAMES == sorted(set(PARENT_NAMES))
     missing = [n for n in PARENT_NAMES if n not in MOVED_SETTINGS and not hasattr(F, n)]
+    assert missing == []
+
+
+def test_every_name_gained_since_the_split_still_resolves_on_functional():
+    assert len(GAINED_NAMES) == 17 and GAINED_NAMES == sorted(set(GAINED_NAMES)) and not set(GAINED_NAMES) & set(PARENT_NAMES)
+    assert {"STACK_LAUNCHES", "_MseStackStepFn", "_MseStackFitFn", "_stack_lights", "_stack_plain", "_stack_route", "_scale_step_gradients",
+            "cook_torrance_stack", "rendering_loss_mse_stack"} <= set(GAINED_NAMES)
+    missing = [n for n in GAINED_NAMES if not hasattr(F, n)]
     assert missing == []
 
 
