@@ -84,7 +84,9 @@ def test_metallic_to_diffuse_specular_gradients(srgb, binding):
 def test_diffuse_specular_to_basecolor_metallic_gradients(srgb, binding):
     """Thresholded selects (den < 1e-6, metallic >= 0.95, two clamps): compared away from the ties, where fp32 and float64 may
     stand on different sides; every branch is exercised (dead denominators, saturated metallic, clamped basecolor)."""
-    from pypbr_amd import functional as F
+    from pypbr_amd import functional as F, torch_ops
+    if binding == "torch_op":
+        assert torch_ops.available()
     g = torch.Generator().manual_seed(3)
     H, W = 40, 56
     d, s = torch.rand(3, H, W, generator=g), torch.rand(3, H, W, generator=g)
@@ -112,7 +114,8 @@ def test_diffuse_specular_to_basecolor_metallic_gradients(srgb, binding):
             assert bool((branch & safe).any())
     for name, got, want in (("diffuse", dd.grad, d64.grad), ("specular", sd.grad, s64.grad)):
         err = (got.cpu().double() - want).abs()
-        tol = 5e-5 * (1 + want.abs())              # two chained divisions: the quotient's rounding enters squared terms
+        tol = 2e-5 * (1 + want.abs())              # the project's band: with |den| > 0.02 on the safe set the worst error is 0.14 of it (MI355X)
+        print("%s srgb=%s %s: worst error / band on the safe set %.3f" % (name, srgb, binding, float((err / tol)[safe].max())))
         assert bool((err <= tol)[safe].all()), (name, float((err - tol)[safe].max()))
 
 

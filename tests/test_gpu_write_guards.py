@@ -19,6 +19,7 @@ import torch
 
 import blend_oracle as BO
 import c_oracle as C
+import map_op_cases as MC
 import torch_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -689,6 +690,7 @@ def test_material_conversions_and_their_gradients_guarded(dt, srgb):
     code = N.F16 if dt == "f16" else N.F32
     st = _stream()
     tol = dict(rel=2e-5) if dt == "f32" else dict(rel=1e-3, f16=True)
+    pooled = [0, 0]                                               # decided elements / elements of the to_basecolor_metallic gradients, over the sweep
     for n, off in _sweep():
         g = torch.Generator().manual_seed(n * 3 + off)
         B = 2 if n % 2 else 1
@@ -732,6 +734,19 @@ def test_material_conversions_and_their_gradients_guarded(dt, srgb):
         bc_ref, mt_ref = C.specular_to_metallic(d_np.reshape(3, 1, n), s.float().numpy().reshape(3, 1, n))     # [3][P] planes
         close64(bc, torch.from_numpy(bc_ref).reshape(-1), tag + ("basecolor",), rel=1e-5, f16=dt == "f16")
         close64(mt, torch.from_numpy(mt_ref).reshape(-1), tag + ("metallic",), rel=1e-5, f16=dt == "f16")
+        # the gradients, against float64 autograd of the oracle, on the elements the map-op fixture's rule calls decided (every compared
+        # quantity 1e-3 from its threshold, the oracle's own float32 gradient within half the band, |den| >= 0.02 on live elements)
+        d64, s64 = d.double().requires_grad_(True), s.double().requires_grad_(True)
+        b64, t64 = O.diffuse_specular_to_basecolor_metallic(O.srgb_to_linear(d64) if srgb else d64, s64)
+        ((b64 * gb.double()).sum() + (t64 * gmm.double()).sum()).backward()
+        keep = MC.decided_to_basecolor_metallic(d.double(), s.double(), srgb, gb.double(), gmm.double())
+        pooled[0] += int(keep.sum())
+        pooled[1] += keep.numel()
+        assert bool(torch.isfinite(gdd.float()).all()) and bool(torch.isfinite(gss.float()).all()), tag
+        if bool(keep.any()):
+            close64(gdd.cpu()[keep], d64.grad[keep], tag + ("g diffuse",), **tol)
+            close64(gss.cpu()[keep], s64.grad[keep], tag + ("g specular",), **tol)
+    print("to_basecolor_metallic gradients %s srgb=%s: %.1f %% of %d elements decided and compared" % (dt, srgb, 100.0 * pooled[0] / pooled[1], pooled[1]))
 
 
 def test_decode_normal_and_its_gradient_guarded():
