@@ -17,8 +17,6 @@
 
 namespace pbr {
 
-typedef float bf4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ void blend_normal_one(float w, float ax, float ay, float az, float bx, float by, float bz, float &ox, float &oy, float &oz) {
     const float iw = 1.0f - w;
     const Vec3 a = {ax, ay, az}, b = {bx, by, bz};
@@ -29,7 +27,9 @@ __device__ __forceinline__ void blend_normal_one(float w, float ax, float ay, fl
 }
 
 // map1, map2: [C][P]; mask: [P]; out: [C][P].  NORMAL: F.normalize both, blend, F.normalize.  vec_ok: P % 4 == 0 and
-// 16-byte aligned planes -> 4 pixels per lane, 16-byte streaming accesses.
+// 16-byte aligned planes -> 4 pixels per lane, 16-byte streaming accesses (Span<float, 4> at unit_at, launch_util.hpp).  The two
+// widths stay written out, each plane's base formed before the lane's index: one width-generic body cost the normal blend an
+// instruction or twelve VGPRs, depending on how it indexed the planes (profiles/EXPERIMENTS.md).
 template <bool NORMAL>
 __global__ __launch_bounds__(256) void blend_kernel(const float *__restrict__ m1, const float *__restrict__ m2,
                                                     const float *__restrict__ mask, float *__restrict__ out,
@@ -37,28 +37,30 @@ __global__ __launch_bounds__(256) void blend_kernel(const float *__restrict__ m1
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (vec_ok) {
         const int64_t P4 = P / 4;
-        const bf4 *a4 = reinterpret_cast<const bf4 *>(m1), *b4 = reinterpret_cast<const bf4 *>(m2), *k4 = reinterpret_cast<const bf4 *>(mask);
-        bf4 *o4 = reinterpret_cast<bf4 *>(out);
         for (int64_t q = tid; q < P4; q += stride) {
-            const bf4 w = __builtin_nontemporal_load(k4 + q);
+            float w[4];
+            Span<float, 4>::ld_nt(unit_at<float, 4>(mask, q), 0, w);
             if (NORMAL) {
-                const bf4 ax = __builtin_nontemporal_load(a4 + q), ay = __builtin_nontemporal_load(a4 + P4 + q), az = __builtin_nontemporal_load(a4 + 2 * P4 + q);
-                const bf4 bx = __builtin_nontemporal_load(b4 + q), by = __builtin_nontemporal_load(b4 + P4 + q), bz = __builtin_nontemporal_load(b4 + 2 * P4 + q);
-                bf4 ox, oy, oz;
+                float a[3][4], b[3][4], o[3][4];
+                Span<float, 4>::ld_nt(unit_at<float, 4>(m1, q), 0, a[0]);
+                Span<float, 4>::ld_nt(unit_at<float, 4>(unit_at<float, 4>(m1, P4), q), 0, a[1]);
+                Span<float, 4>::ld_nt(unit_at<float, 4>(unit_at<float, 4>(m1, 2 * P4), q), 0, a[2]);
+                Span<float, 4>::ld_nt(unit_at<float, 4>(m2, q), 0, b[0]);
+                Span<float, 4>::ld_nt(unit_at<float, 4>(unit_at<float, 4>(m2, P4), q), 0, b[1]);
+                Span<float, 4>::ld_nt(unit_at<float, 4>(unit_at<float, 4>(m2, 2 * P4), q), 0, b[2]);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float x, y, z;
-                    blend_normal_one(w[j], ax[j], ay[j], az[j], bx[j], by[j], bz[j], x, y, z);
-                    ox[j] = x; oy[j] = y; oz[j] = z;
-                }
-                __builtin_nontemporal_store(ox, o4 + q); __builtin_nontemporal_store(oy, o4 + P4 + q); __builtin_nontemporal_store(oz, o4 + 2 * P4 + q);
+                for (int j = 0; j < 4; ++j) blend_normal_one(w[j], a[0][j], a[1][j], a[2][j], b[0][j], b[1][j], b[2][j], o[0][j], o[1][j], o[2][j]);
+                Span<float, 4>::st_nt(unit_at<float, 4>(out, q), 0, o[0]);
+                Span<float, 4>::st_nt(unit_at<float, 4>(unit_at<float, 4>(out, P4), q), 0, o[1]);
+                Span<float, 4>::st_nt(unit_at<float, 4>(unit_at<float, 4>(out, 2 * P4), q), 0, o[2]);
             } else {
                 for (int ch = 0; ch < channels; ++ch) {
-                    const bf4 a = __builtin_nontemporal_load(a4 + ch * P4 + q), b = __builtin_nontemporal_load(b4 + ch * P4 + q);
-                    bf4 o;
+                    float a[4], b[4], o[4];
+                    Span<float, 4>::ld_nt(unit_at<float, 4>(unit_at<float, 4>(m1, ch * P4), q), 0, a);
+                    Span<float, 4>::ld_nt(unit_at<float, 4>(unit_at<float, 4>(m2, ch * P4), q), 0, b);
 #pragma unroll
                     for (int j = 0; j < 4; ++j) o[j] = fmaf(w[j], a[j], (1.0f - w[j]) * b[j]);
-                    __builtin_nontemporal_store(o, o4 + ch * P4 + q);
+                    Span<float, 4>::st_nt(unit_at<float, 4>(unit_at<float, 4>(out, ch * P4), q), 0, o);
                 }
             }
         }
@@ -74,22 +76,6 @@ __global__ __launch_bounds__(256) void blend_kernel(const float *__restrict__ m1
     }
 }
 
-// V floats of one plane: V = 4 -> one 16-byte streaming access, V = 1 -> a dword.
-template <int V> struct Run;
-template <> struct Run<4> {
-    static __device__ __forceinline__ void ld(const float *p, int64_t i, float v[4]) {
-        const bf4 t = __builtin_nontemporal_load(reinterpret_cast<const bf4 *>(p + i));
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void st(float *p, int64_t i, const float v[4]) {
-        __builtin_nontemporal_store(bf4{v[0], v[1], v[2], v[3]}, reinterpret_cast<bf4 *>(p + i));
-    }
-};
-template <> struct Run<1> {
-    static __device__ __forceinline__ void ld(const float *p, int64_t i, float v[1]) { v[0] = p[i]; }
-    static __device__ __forceinline__ void st(float *p, int64_t i, const float v[1]) { p[i] = v[0]; }
-};
-
 // Gradient of blend_kernel (what autograd derives from functional.py:103-110 / :119-145): g1, g2 [C][P] (NULL = not wanted),
 // gmask [P] (NULL = not wanted; `accumulate`: added to what is there -- the mask is shared by every map of a material).
 // V pixels per lane (4: P % 4 == 0 and 16-byte aligned planes; 4096^2, 3 channels: 241 -> 207 us = 5.5 TB/s).
@@ -101,13 +87,13 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(const float *__rest
     const int64_t stride = (int64_t)gridDim.x * blockDim.x * V;
     for (int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * V; p < P; p += stride) {
         float w[V], gw[V];
-        Run<V>::ld(mask, p, w);
+        Span<float, V>::ld_nt(mask, p, w);
 #pragma unroll
         for (int j = 0; j < V; ++j) gw[j] = 0.0f;
         if (NORMAL) {
             float av[3][V], bv[3][V], gv[3][V], o1[3][V], o2[3][V];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) { Run<V>::ld(m1, c * P + p, av[c]); Run<V>::ld(m2, c * P + p, bv[c]); Run<V>::ld(gout, c * P + p, gv[c]); }
+            for (int c = 0; c < 3; ++c) { Span<float, V>::ld_nt(m1, c * P + p, av[c]); Span<float, V>::ld_nt(m2, c * P + p, bv[c]); Span<float, V>::ld_nt(gout, c * P + p, gv[c]); }
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const float iw = 1.0f - w[j];
@@ -129,31 +115,31 @@ __global__ __launch_bounds__(256) void blend_backward_kernel(const float *__rest
             }
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                if (g1) Run<V>::st(g1, c * P + p, o1[c]);
-                if (g2) Run<V>::st(g2, c * P + p, o2[c]);
+                if (g1) Span<float, V>::st_nt(g1, c * P + p, o1[c]);
+                if (g2) Span<float, V>::st_nt(g2, c * P + p, o2[c]);
             }
         } else {
             for (int ch = 0; ch < channels; ++ch) {
                 float g[V], a[V], b[V], o1[V], o2[V];
-                Run<V>::ld(gout, ch * P + p, g); Run<V>::ld(m1, ch * P + p, a); Run<V>::ld(m2, ch * P + p, b);
+                Span<float, V>::ld_nt(gout, ch * P + p, g); Span<float, V>::ld_nt(m1, ch * P + p, a); Span<float, V>::ld_nt(m2, ch * P + p, b);
 #pragma unroll
                 for (int j = 0; j < V; ++j) {
                     o1[j] = w[j] * g[j];
                     o2[j] = (1.0f - w[j]) * g[j];
                     gw[j] = fmaf(g[j], a[j] - b[j], gw[j]);
                 }
-                if (g1) Run<V>::st(g1, ch * P + p, o1);
-                if (g2) Run<V>::st(g2, ch * P + p, o2);
+                if (g1) Span<float, V>::st_nt(g1, ch * P + p, o1);
+                if (g2) Span<float, V>::st_nt(g2, ch * P + p, o2);
             }
         }
         if (gmask) {
             if (accumulate) {
                 float old[V];
-                Run<V>::ld(gmask, p, old);
+                Span<float, V>::ld_nt(gmask, p, old);
 #pragma unroll
                 for (int j = 0; j < V; ++j) gw[j] += old[j];
             }
-            Run<V>::st(gmask, p, gw);
+            Span<float, V>::st_nt(gmask, p, gw);
         }
     }
 }
@@ -203,7 +189,7 @@ int pbr_blend_maps(const void *map1, const void *map2, const void *mask, void *o
     if (is_normal && channels != 3) return PBR_ERR_CHANNELS;
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto a = static_cast<const float *>(map1), b = static_cast<const float *>(map2), m = static_cast<const float *>(mask);
-    const int vec_ok = pixels % 4 == 0 && is_aligned(map1, 16) && is_aligned(map2, 16) && is_aligned(mask, 16) && is_aligned(out, 16);
+    const int vec_ok = pixels % 4 == 0 && all_aligned(16, {map1, map2, mask, out});
     const StreamShape sh = stream_shape((size_t)(vec_ok ? pixels / 4 : pixels), is_normal ? kShapeBlendNormal : kShapeBlend);
     if (is_normal) hipLaunchKernelGGL(blend_kernel<true>, dim3(sh.grid), dim3(sh.block), sh.lds, s, a, b, m, static_cast<float *>(out), 3, pixels, vec_ok);
     else hipLaunchKernelGGL(blend_kernel<false>, dim3(sh.grid), dim3(sh.block), sh.lds, s, a, b, m, static_cast<float *>(out), (int)channels, pixels, vec_ok);
@@ -249,23 +235,18 @@ int pbr_blend_maps_backward(const void *map1, const void *map2, const void *mask
     if (!map1 || !map2 || !mask || !grad_out) return PBR_ERR_NULL_MAP;
     if (channels < 1 || pixels < 1) return PBR_ERR_SHAPE;
     if (is_normal && channels != 3) return PBR_ERR_CHANNELS;
-    const dim3 grid(stream_grid(pixels, 16));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const float *a = static_cast<const float *>(map1), *b = static_cast<const float *>(map2), *k = static_cast<const float *>(mask);
     const float *g = static_cast<const float *>(grad_out);
     float *ga = static_cast<float *>(g_map1), *gb = static_cast<float *>(g_map2), *gk = static_cast<float *>(g_mask);
-    bool vec = pixels % 4 == 0;
-    for (const void *p : {map1, map2, mask, grad_out, (const void *)g_map1, (const void *)g_map2, (const void *)g_mask})
-        if (p && !is_aligned(p, 16)) vec = false;
-    if (vec) {
-        const StreamShape sh = stream_shape((size_t)(pixels / 4), kShapeBlendBwd);
-        if (is_normal) hipLaunchKernelGGL((blend_backward_kernel<true, 4>), dim3(sh.grid), dim3(sh.block), sh.lds, s, a, b, k, g, ga, gb, gk, (int)channels, pixels, accumulate_mask);
-        else hipLaunchKernelGGL((blend_backward_kernel<false, 4>), dim3(sh.grid), dim3(sh.block), sh.lds, s, a, b, k, g, ga, gb, gk, (int)channels, pixels, accumulate_mask);
-    } else if (is_normal) {
-        hipLaunchKernelGGL((blend_backward_kernel<true, 1>), grid, dim3(256), 0, s, a, b, k, g, ga, gb, gk, (int)channels, pixels, accumulate_mask);
-    } else {
-        hipLaunchKernelGGL((blend_backward_kernel<false, 1>), grid, dim3(256), 0, s, a, b, k, g, ga, gb, gk, (int)channels, pixels, accumulate_mask);
-    }
+    const bool vec = pixels % 4 == 0 && all_aligned(16, {map1, map2, mask, grad_out, g_map1, g_map2, g_mask});
+    // (one pixel per lane keeps the grid-stride shape it was measured with)
+    const StreamShape sh = vec ? stream_shape((size_t)(pixels / 4), kShapeBlendBwd) : StreamShape{stream_grid(pixels, 16), 256, 0};
+    with_width(vec, [&](auto w) {
+        constexpr int V = decltype(w)::value;
+        if (is_normal) hipLaunchKernelGGL((blend_backward_kernel<true, V>), dim3(sh.grid), dim3(sh.block), sh.lds, s, a, b, k, g, ga, gb, gk, (int)channels, pixels, accumulate_mask);
+        else hipLaunchKernelGGL((blend_backward_kernel<false, V>), dim3(sh.grid), dim3(sh.block), sh.lds, s, a, b, k, g, ga, gb, gk, (int)channels, pixels, accumulate_mask);
+    });
     return launch_status();
 }
 

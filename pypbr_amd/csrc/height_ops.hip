@@ -18,7 +18,6 @@
 #include <hip/hip_fp16.h>
 
 #include <cstdint>
-#include <initializer_list>
 
 #include "../../include/pbr_hip.h"
 #include "stream_shape.hpp"
@@ -124,30 +123,7 @@ __device__ __forceinline__ void take_max(float &v, int32_t &i, float ov, int32_t
 
 __device__ __forceinline__ int64_t lesser(int64_t a, int64_t b) { return a < b ? a : b; }
 
-// V consecutive values of T from fp32 registers (V = 4: one 16-byte / 8-byte store; the launcher checked the alignment)
-template <typename T, int V> __device__ __forceinline__ void store_units(void *p, int64_t i, const float v[V]) {
-    if constexpr (V == 1) {
-        Elem<T>::st(p, i, v[0]);
-    } else if constexpr (sizeof(T) == 4) {
-        typedef float v4 __attribute__((ext_vector_type(4)));
-        const v4 t = {v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<v4 *>(static_cast<float *>(p) + i) = t;
-    } else {
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        const h4 t = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        *reinterpret_cast<h4 *>(static_cast<_Float16 *>(p) + i) = t;
-    }
-}
-
-template <int V> __device__ __forceinline__ void load_units(const float *p, int64_t i, float v[V]) {
-    if constexpr (V == 4) {
-        typedef float v4 __attribute__((ext_vector_type(4)));
-        const v4 t = *reinterpret_cast<const v4 *>(p + i);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        v[0] = p[i];
-    }
-}
+// (V consecutive elements at an element offset: Span<T, V>, launch_util.hpp -- plain loads and plain stores here)
 
 // stage 3: sum (fp64), min, max and the first index of each, per partial.  A lane visits its pixels in rising order and the tree
 // joins lanes by (value, index), so the index is the first one's; the tree's shape is fixed, so is the sum's rounding.
@@ -163,7 +139,7 @@ __global__ __launch_bounds__(256) void height_stats_kernel(const float *__restri
     int32_t imin = INT32_MAX, imax = INT32_MAX;
     for (int64_t i = lo + (int64_t)t * V; i < hi; i += 256 * V) {                // V == 4: n % 4 == 0, so a unit is whole
         float v[V];
-        load_units<V>(img, i, v);
+        Span<float, V>::ld(img, i, v);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             sum += (double)v[j];
@@ -240,10 +216,10 @@ __global__ __launch_bounds__(256) void height_normalize_kernel(const float *__re
     const int64_t first = (int64_t)sp * span, last = lesser(n, first + span);
     for (int64_t i = first + (int64_t)t * V; i < last; i += 256 * V) {
         float v[V];
-        load_units<V>(img, i, v);
+        Span<float, V>::ld(img, i, v);
 #pragma unroll
         for (int j = 0; j < V; ++j) v[j] = __fdiv_rn(__fsub_rn(__fsub_rn(v[j], mean), lo), range);
-        store_units<T, V>(o, i, v);
+        Span<T, V>::st(o, i, v);
     }
 }
 
@@ -258,8 +234,8 @@ __global__ __launch_bounds__(256) void height_grad_sums_kernel(const float *__re
     double sg = 0.0, sgo = 0.0;
     for (int64_t i = lo + (int64_t)t * V; i < hi; i += 256 * V) {
         float gv[V], ov[V];
-        load_units<V>(g, i, gv);
-        load_units<V>(o, i, ov);
+        Span<float, V>::ld(g, i, gv);
+        Span<float, V>::ld(o, i, ov);
 #pragma unroll
         for (int j = 0; j < V; ++j) { sg += (double)gv[j]; sgo += (double)gv[j] * (double)ov[j]; }
     }
@@ -307,7 +283,7 @@ __global__ __launch_bounds__(256) void height_normalize_backward_kernel(const fl
     const int64_t first = (int64_t)sp * span, last = lesser(n, first + span);
     for (int64_t i = first + (int64_t)t * V; i < last; i += 256 * V) {
         float v[V];
-        load_units<V>(g, i, v);
+        Span<float, V>::ld(g, i, v);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             float r = v[j] / range;
@@ -315,7 +291,7 @@ __global__ __launch_bounds__(256) void height_normalize_backward_kernel(const fl
             if (i + j == imax) r -= q;
             v[j] = r;
         }
-        store_units<float, V>(d, i, v);
+        Span<float, V>::st(d, i, v);
     }
 }
 
@@ -328,8 +304,7 @@ Tiles stencil_tiles(int32_t batch, int32_t H, int32_t W) {
 bool map_shape_ok(int32_t batch, int32_t H, int32_t W) { return batch >= 1 && H >= 1 && W >= 1 && (int64_t)H * W <= 0x7fffffff; }
 int partials(int64_t n) { return (int)((n + kChunk - 1) / kChunk); }
 bool vec4(int64_t n, std::initializer_list<const void *> ptrs, std::initializer_list<int64_t> strides) {
-    bool ok = n % 4 == 0;
-    for (const void *p : ptrs) ok = ok && is_aligned(p, 16);
+    bool ok = n % 4 == 0 && all_aligned(16, ptrs);
     for (int64_t s : strides) ok = ok && s % 4 == 0;
     return ok;
 }
@@ -348,11 +323,11 @@ int pbr_normal_divergence(const void *normal, int64_t normal_batch_stride, int64
     const Tiles t = stencil_tiles(batch, height_px, width);
     if (t.blocks > 0x7fffffff) return PBR_ERR_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define PBR_DIV(T) hipLaunchKernelGGL((normal_divergence_kernel<T>), dim3((unsigned)t.blocks), dim3(256), 0, s, normal, normal_batch_stride, \
-                                      normal_plane_stride, static_cast<float *>(div), div_batch_stride, (int)height_px, (int)width, t.x, t.y, scale, \
-                                      (int)(directx != 0))
-    if (dtype == PBR_F32) PBR_DIV(float); else PBR_DIV(__half);
-#undef PBR_DIV
+    with_dtype(dtype, [&](auto e) {
+        using T = typename decltype(e)::type;
+        hipLaunchKernelGGL((normal_divergence_kernel<T>), dim3((unsigned)t.blocks), dim3(256), 0, s, normal, normal_batch_stride, normal_plane_stride,
+                           static_cast<float *>(div), div_batch_stride, (int)height_px, (int)width, t.x, t.y, scale, (int)(directx != 0));
+    });
     return launch_status();
 }
 
@@ -403,8 +378,9 @@ int pbr_height_stats(const void *height, int64_t height_batch_stride, void *work
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto h = static_cast<const float *>(height);
     auto ws = static_cast<HeightPartial *>(workspace);
-    if (vec4(n, {height}, {height_batch_stride})) hipLaunchKernelGGL(height_stats_kernel<4>, grid, dim3(256), 0, s, h, height_batch_stride, ws, n, P);
-    else hipLaunchKernelGGL(height_stats_kernel<1>, grid, dim3(256), 0, s, h, height_batch_stride, ws, n, P);
+    with_width(vec4(n, {height}, {height_batch_stride}), [&](auto w) {
+        hipLaunchKernelGGL(height_stats_kernel<decltype(w)::value>, grid, dim3(256), 0, s, h, height_batch_stride, ws, n, P);
+    });
     return launch_status();
 }
 
@@ -418,18 +394,20 @@ int pbr_height_normalize(const void *height, int64_t height_batch_stride, const 
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
     const int64_t n = (int64_t)height_px * width;
     const int P = partials(n);
-    const bool vec = vec4(n, {height, dtype == PBR_F32 ? out : height}, {height_batch_stride, out_batch_stride}) && is_aligned(out, 8);
+    const bool vec = vec4(n, {height}, {height_batch_stride, out_batch_stride}) && is_aligned(out, quad_bytes(dtype));
     const int64_t span = 256 * (vec ? 4 : 1) * 8, spans = (n + span - 1) / span;
     if (spans * batch > 0x7fffffff) return PBR_ERR_SHAPE;
     const dim3 grid((unsigned)(spans * batch));
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto h = static_cast<const float *>(height);
     auto ws = static_cast<const HeightPartial *>(workspace);
-#define PBR_HN(T, VV) hipLaunchKernelGGL((height_normalize_kernel<T, VV>), grid, dim3(256), 0, s, h, height_batch_stride, ws, out, out_batch_stride, \
-                                         static_cast<float *>(stats), n, P, (int)spans, span)
-    if (dtype == PBR_F32) { if (vec) PBR_HN(float, 4); else PBR_HN(float, 1); }
-    else { if (vec) PBR_HN(__half, 4); else PBR_HN(__half, 1); }
-#undef PBR_HN
+    with_dtype(dtype, [&](auto t) {
+        with_width(vec, [&](auto w) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((height_normalize_kernel<T, decltype(w)::value>), grid, dim3(256), 0, s, h, height_batch_stride, ws, out, out_batch_stride,
+                               static_cast<float *>(stats), n, P, (int)spans, span);
+        });
+    });
     return launch_status();
 }
 
@@ -451,15 +429,12 @@ int pbr_height_normalize_backward(const void *grad_out, int64_t grad_batch_strid
     auto g = static_cast<const float *>(grad_out), o = static_cast<const float *>(out), st = static_cast<const float *>(stats);
     auto ws = static_cast<GradPartial *>(workspace);
     auto dh = static_cast<float *>(grad_height);
-    if (vec) {
-        hipLaunchKernelGGL(height_grad_sums_kernel<4>, sums, dim3(256), 0, s, g, grad_batch_stride, o, out_batch_stride, ws, n, P);
-        hipLaunchKernelGGL(height_normalize_backward_kernel<4>, grid, dim3(256), 0, s, g, grad_batch_stride, st, ws, dh, grad_height_batch_stride, n, P,
+    with_width(vec, [&](auto w) {
+        constexpr int V = decltype(w)::value;
+        hipLaunchKernelGGL(height_grad_sums_kernel<V>, sums, dim3(256), 0, s, g, grad_batch_stride, o, out_batch_stride, ws, n, P);
+        hipLaunchKernelGGL(height_normalize_backward_kernel<V>, grid, dim3(256), 0, s, g, grad_batch_stride, st, ws, dh, grad_height_batch_stride, n, P,
                            (int)spans, span);
-    } else {
-        hipLaunchKernelGGL(height_grad_sums_kernel<1>, sums, dim3(256), 0, s, g, grad_batch_stride, o, out_batch_stride, ws, n, P);
-        hipLaunchKernelGGL(height_normalize_backward_kernel<1>, grid, dim3(256), 0, s, g, grad_batch_stride, st, ws, dh, grad_height_batch_stride, n, P,
-                           (int)spans, span);
-    }
+    });
     return launch_status();
 }
 

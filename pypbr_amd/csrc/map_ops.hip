@@ -19,49 +19,31 @@
 
 namespace pbr {
 
-// (one element: Elem<T>, launch_util.hpp)
-// 4 elements per lane when everything is 16-byte (fp32) / 8-byte (fp16) aligned.
-template <typename T> struct Quad;
-template <> struct Quad<float> {
-    typedef float v4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ void ld(const void *p, size_t q, float v[4]) {
-        v4 t = __builtin_nontemporal_load(reinterpret_cast<const v4 *>(p) + q);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void st(void *p, size_t q, const float v[4]) {
-        v4 t = {v[0], v[1], v[2], v[3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<v4 *>(p) + q);
-    }
-};
-template <> struct Quad<__half> {
-    typedef _Float16 v4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ void ld(const void *p, size_t q, float v[4]) {
-        v4 t = __builtin_nontemporal_load(reinterpret_cast<const v4 *>(p) + q);
-        v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)t.z; v[3] = (float)t.w;
-    }
-    static __device__ __forceinline__ void st(void *p, size_t q, const float v[4]) {
-        v4 t = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<v4 *>(p) + q);
-    }
-};
+// (one element: Elem<T>; V consecutive ones at an element offset: Span<T, V>; launch_util.hpp)
+// The walk of the flat kernels: whole quads while every plane is 16-byte (fp32) / 8-byte (fp16) aligned, then the tail -- or, unaligned,
+// all of it -- one element at a time.  body(Width<V>, i) does the V elements at element offset i, so a kernel's arithmetic is written
+// once.  tid and stride are formed by the KERNEL: formed in here, the workgroup size is fetched from the dispatch packet with a
+// vector load and multiplied per lane instead of the scalar load the kernels have: +6 instructions, +4 VGPRs (profiles/EXPERIMENTS.md).
+template <typename Body>
+__device__ __forceinline__ void quads_then_tail(size_t n, int vec_ok, size_t tid, size_t stride, Body body) {
+    const size_t nq = vec_ok ? n / 4 : 0;
+    for (size_t q = tid; q < nq; q += stride) body(Width<4>{}, q * 4);
+    for (size_t i = nq * 4 + tid; i < n; i += stride) body(Width<1>{}, i);
+}
 
 // ---- colour transfer functions ---------------------------------------------------
 template <typename T, bool TO_LINEAR>
 __global__ __launch_bounds__(256) void colour_kernel(const void *src, void *dst, size_t n, int vec_ok) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nq = vec_ok ? n / 4 : 0;
-    for (size_t q = tid; q < nq; q += stride) {
-        float v[4];
-        Quad<T>::ld(src, q, v);
+    quads_then_tail(n, vec_ok, tid, stride, [&](auto w, size_t i) {
+        constexpr int V = decltype(w)::value;
+        float v[V];
+        Span<T, V>::ld_nt(src, i, v);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = TO_LINEAR ? srgb_to_linear(v[j]) : linear_to_srgb(v[j]);
-        Quad<T>::st(dst, q, v);
-    }
-    for (size_t i = nq * 4 + tid; i < n; i += stride) {
-        const float x = Elem<T>::ld(src, i);
-        Elem<T>::st(dst, i, TO_LINEAR ? srgb_to_linear(x) : linear_to_srgb(x));
-    }
+        for (int j = 0; j < V; ++j) v[j] = TO_LINEAR ? srgb_to_linear(v[j]) : linear_to_srgb(v[j]);
+        Span<T, V>::st_nt(dst, i, v);
+    });
 }
 
 // ---- metallic -> diffuse/specular (metallic.py:98-108) ---------------------------
@@ -77,9 +59,9 @@ __global__ __launch_bounds__(256) void metallic_to_specular_kernel(const void *_
             // all four loads of the lane first (outputs never alias inputs: the results are new maps), then the six stores: with
             // the loads of a channel behind the previous channel's stores a lane had one load in flight at a time
             float m[4], a[3][4];
-            Quad<T>::ld(metallic, q, m);
+            Span<T, 4>::ld_nt(unit_at<T, 4>(metallic, q), 0, m);
 #pragma unroll
-            for (int c = 0; c < 3; ++c) Quad<T>::ld(albedo, (b * 3 + c) * P4 + pq, a[c]);
+            for (int c = 0; c < 3; ++c) Span<T, 4>::ld_nt(unit_at<T, 4>(albedo, (b * 3 + c) * P4 + pq), 0, a[c]);
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const size_t o = (b * 3 + c) * P4 + pq;
@@ -90,12 +72,14 @@ __global__ __launch_bounds__(256) void metallic_to_specular_kernel(const void *_
                     d[j] = lin * om;
                     sp[j] = fmaf(lin, m[j], kDielectricF0 * om);
                 }
-                Quad<T>::st(diffuse, o, d);
-                Quad<T>::st(specular, o, sp);
+                Span<T, 4>::st_nt(unit_at<T, 4>(diffuse, o), 0, d);
+                Span<T, 4>::st_nt(unit_at<T, 4>(specular, o), 0, sp);
             }
         }
         return;
     }
+    // (the one-pixel path keeps its own order -- a channel's load behind the previous channel's stores: one body for both widths
+    // hoists its four loads too, and the fp16 kernel then takes 44 VGPRs for 42: profiles/EXPERIMENTS.md)
     const size_t total = (size_t)batch * (size_t)P;
     for (size_t i = tid; i < total; i += stride) {
         const size_t b = i / (size_t)P, p = i - b * (size_t)P;
@@ -139,22 +123,16 @@ __global__ __launch_bounds__(256) void specular_to_metallic_kernel(const void *d
                                                                    void *basecolor, void *metallic, size_t n,
                                                                    int albedo_srgb, int vec_ok) {
     const size_t stride = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nq = vec_ok ? n / 4 : 0;
-    for (size_t q = tid; q < nq; q += stride) {
-        float d[4], sp[4], bc[4], m[4];
-        Quad<T>::ld(diffuse, q, d);
-        Quad<T>::ld(specular, q, sp);
+    quads_then_tail(n, vec_ok, tid, stride, [&](auto w, size_t i) {
+        constexpr int V = decltype(w)::value;
+        float d[V], sp[V], bc[V], m[V];
+        Span<T, V>::ld_nt(diffuse, i, d);
+        Span<T, V>::ld_nt(specular, i, sp);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) specular_to_metallic_one(d[j], sp[j], albedo_srgb, bc[j], m[j]);
-        Quad<T>::st(basecolor, q, bc);
-        Quad<T>::st(metallic, q, m);
-    }
-    for (size_t i = nq * 4 + tid; i < n; i += stride) {
-        float bc, m;
-        specular_to_metallic_one(Elem<T>::ld(diffuse, i), Elem<T>::ld(specular, i), albedo_srgb, bc, m);
-        Elem<T>::st(basecolor, i, bc);
-        Elem<T>::st(metallic, i, m);
-    }
+        for (int j = 0; j < V; ++j) specular_to_metallic_one(d[j], sp[j], albedo_srgb, bc[j], m[j]);
+        Span<T, V>::st_nt(basecolor, i, bc);
+        Span<T, V>::st_nt(metallic, i, m);
+    });
 }
 
 // ---- normal decode (base.py:191-242) ---------------------------------------------
@@ -170,13 +148,13 @@ __global__ __launch_bounds__(256) void any_negative_kernel(const void *src, size
         if (__atomic_load_n(flag, __ATOMIC_RELAXED) != 0) return;   // settled by the probe or by another wave
         float v[4][4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) Quad<T>::ld(src, q + u * stride, v[u]);
+        for (int u = 0; u < 4; ++u) Span<T, 4>::ld_nt(unit_at<T, 4>(src, q + u * stride), 0, v[u]);
 #pragma unroll
         for (int u = 0; u < 4; ++u) neg |= (v[u][0] < 0.0f) | (v[u][1] < 0.0f) | (v[u][2] < 0.0f) | (v[u][3] < 0.0f);
     }
     for (; q < nq; q += stride) {
         float v[4];
-        Quad<T>::ld(src, q, v);
+        Span<T, 4>::ld_nt(unit_at<T, 4>(src, q), 0, v);
         neg |= (v[0] < 0.0f) | (v[1] < 0.0f) | (v[2] < 0.0f) | (v[3] < 0.0f);
     }
     for (size_t i = nq * 4 + tid; i < n; i += stride) neg |= Elem<T>::ld(src, i) < 0.0f;
@@ -246,13 +224,12 @@ template <typename T>
 __global__ __launch_bounds__(256) void keep_normal_kernel(const void *src, void *dst, size_t n, const int *flag, int vec_ok) {
     if (*flag == 0) return;
     const size_t stride = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nq = vec_ok ? n / 4 : 0;
-    for (size_t q = tid; q < nq; q += stride) {
-        float v[4];
-        Quad<T>::ld(src, q, v);
-        Quad<T>::st(dst, q, v);
-    }
-    for (size_t i = nq * 4 + tid; i < n; i += stride) Elem<T>::st(dst, i, Elem<T>::ld(src, i));
+    quads_then_tail(n, vec_ok, tid, stride, [&](auto w, size_t i) {
+        constexpr int V = decltype(w)::value;
+        float v[V];
+        Span<T, V>::ld_nt(src, i, v);
+        Span<T, V>::st_nt(dst, i, v);
+    });
 }
 
 // Gradient folding (autograd plumbing of the backward kernel): the backward kernel writes one gradient per OUTPUT
@@ -282,7 +259,7 @@ __global__ __launch_bounds__(256) void fold_gradient_quad_kernel(const void *__r
         for (; k + 4 <= terms; k += 4) {
             float v[4][4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) Quad<T>::ld(src, term(k + u), v[u]);
+            for (int u = 0; u < 4; ++u) Span<T, 4>::ld_nt(unit_at<T, 4>(src, term(k + u)), 0, v[u]);
 #pragma unroll
             for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -290,11 +267,11 @@ __global__ __launch_bounds__(256) void fold_gradient_quad_kernel(const void *__r
         }
         for (; k < terms; ++k) {
             float v[4];
-            Quad<T>::ld(src, term(k), v);
+            Span<T, 4>::ld_nt(unit_at<T, 4>(src, term(k)), 0, v);
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[j] += v[j];
         }
-        Quad<T>::st(dst, (size_t)i, acc);
+        Span<T, 4>::st_nt(unit_at<T, 4>(dst, (size_t)i), 0, acc);
     }
 }
 
@@ -327,23 +304,17 @@ __global__ __launch_bounds__(256) void decode_normal_backward_kernel(const float
                                                                      float *__restrict__ gin, int64_t P, const int *flag) {
     const bool keep = CH == 3 && *flag != 0;
     const size_t stride = (size_t)gridDim.x * blockDim.x * V, Ps = (size_t)P;
-    auto ld = [](const float *p, size_t i, float v[V]) {          // V = 4: one 16-byte streaming load (P % 4 == 0, aligned planes)
-        if constexpr (V == 4) Quad<float>::ld(p, i / 4, v); else v[0] = p[i];
-    };
-    auto st = [](float *p, size_t i, const float v[V]) {
-        if constexpr (V == 4) Quad<float>::st(p, i / 4, v); else p[i] = v[0];
-    };
     for (size_t p = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V; p < Ps; p += stride) {
         float g[3][V], s[3][V], o[3][V];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) ld(gout, c * Ps + p, g[c]);
+        for (int c = 0; c < 3; ++c) Span<float, V>::ld_nt(unit_at<float, V>(gout, (c * Ps + p) / V), 0, g[c]);      // V = 4: 16-byte streaming accesses (P % 4 == 0, aligned planes)
         if (keep) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) st(gin, c * Ps + p, g[c]);
+            for (int c = 0; c < 3; ++c) Span<float, V>::st_nt(unit_at<float, V>(gin, (c * Ps + p) / V), 0, g[c]);
             continue;
         }
 #pragma unroll
-        for (int c = 0; c < CH; ++c) ld(src, c * Ps + p, s[c]);
+        for (int c = 0; c < CH; ++c) Span<float, V>::ld_nt(unit_at<float, V>(src, (c * Ps + p) / V), 0, s[c]);
 #pragma unroll
         for (int k = 0; k < V; ++k) {
             const float gx = g[0][k], gy = g[1][k], gz = g[2][k];
@@ -363,7 +334,7 @@ __global__ __launch_bounds__(256) void decode_normal_backward_kernel(const float
             }
         }
 #pragma unroll
-        for (int c = 0; c < CH; ++c) st(gin, c * Ps + p, o[c]);
+        for (int c = 0; c < CH; ++c) Span<float, V>::st_nt(unit_at<float, V>(gin, (c * Ps + p) / V), 0, o[c]);
     }
 }
 
@@ -395,19 +366,15 @@ template <typename T, bool TO_LINEAR>
 __global__ __launch_bounds__(256) void colour_backward_kernel(const void *src, const void *gout, void *gin, size_t n, int vec_ok) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nq = vec_ok ? n / 4 : 0;
-    for (size_t q = tid; q < nq; q += stride) {
-        float x[4], g[4];
-        Quad<T>::ld(src, q, x);
-        Quad<T>::ld(gout, q, g);
+    quads_then_tail(n, vec_ok, tid, stride, [&](auto w, size_t i) {
+        constexpr int V = decltype(w)::value;
+        float x[V], g[V];
+        Span<T, V>::ld_nt(src, i, x);
+        Span<T, V>::ld_nt(gout, i, g);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) g[j] *= TO_LINEAR ? srgb_to_linear_slope(x[j]) : linear_to_srgb_slope(x[j]);
-        Quad<T>::st(gin, q, g);
-    }
-    for (size_t i = nq * 4 + tid; i < n; i += stride) {
-        const float x = Elem<T>::ld(src, i);
-        Elem<T>::st(gin, i, Elem<T>::ld(gout, i) * (TO_LINEAR ? srgb_to_linear_slope(x) : linear_to_srgb_slope(x)));
-    }
+        for (int j = 0; j < V; ++j) g[j] *= TO_LINEAR ? srgb_to_linear_slope(x[j]) : linear_to_srgb_slope(x[j]);
+        Span<T, V>::st_nt(gin, i, g);
+    });
 }
 
 // metallic.py:98-108 backward: diffuse = lin (1 - m), specular = 0.04 (1 - m) + lin m, lin = srgb_to_linear(albedo) | albedo.
@@ -420,23 +387,21 @@ __global__ __launch_bounds__(256) void metallic_to_specular_backward_kernel(cons
     constexpr int V = VEC ? 4 : 1;
     const size_t stride = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t PV = (size_t)P / V, total = (size_t)batch * PV;
-    auto ld = [](const void *p, size_t i, float v[V]) { if constexpr (VEC) Quad<T>::ld(p, i, v); else v[0] = Elem<T>::ld(p, i); };
-    auto st = [](void *p, size_t i, const float v[V]) { if constexpr (VEC) Quad<T>::st(p, i, v); else Elem<T>::st(p, i, v[0]); };
     for (size_t q = tid; q < total; q += stride) {
         const size_t b = q / PV, pq = q - b * PV;
         float m[V], gm[V];
-        ld(metallic, q, m);
+        Span<T, V>::ld_nt(metallic, q * V, m);
 #pragma unroll
         for (int j = 0; j < V; ++j) gm[j] = 0.0f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const size_t o = (b * 3 + c) * PV + pq;
+            const size_t o = ((b * 3 + c) * PV + pq) * V;
             float a[V], gd[V], gs[V], ga[V];
-            ld(albedo, o, a);
+            Span<T, V>::ld_nt(albedo, o, a);
 #pragma unroll
             for (int j = 0; j < V; ++j) { gd[j] = 0.0f; gs[j] = 0.0f; }
-            if (g_diffuse) ld(g_diffuse, o, gd);
-            if (g_specular) ld(g_specular, o, gs);
+            if (g_diffuse) Span<T, V>::ld_nt(g_diffuse, o, gd);
+            if (g_specular) Span<T, V>::ld_nt(g_specular, o, gs);
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const float lin = albedo_srgb ? srgb_to_linear(a[j]) : a[j];
@@ -444,9 +409,9 @@ __global__ __launch_bounds__(256) void metallic_to_specular_backward_kernel(cons
                 ga[j] = fmaf(gs[j] - gd[j], m[j], gd[j]) * slope;
                 gm[j] = fmaf(gs[j], lin - kDielectricF0, fmaf(-gd[j], lin, gm[j]));
             }
-            if (g_albedo) st(g_albedo, o, ga);
+            if (g_albedo) Span<T, V>::st_nt(g_albedo, o, ga);
         }
-        if (g_metallic) st(g_metallic, q, gm);
+        if (g_metallic) Span<T, V>::st_nt(g_metallic, q * V, gm);
     }
 }
 
@@ -483,40 +448,50 @@ __global__ __launch_bounds__(256) void specular_to_metallic_backward_kernel(cons
                                                                             const void *g_metallic, void *g_diffuse, void *g_specular,
                                                                             size_t n, int albedo_srgb, int vec_ok) {
     const size_t stride = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t nq = vec_ok ? n / 4 : 0;
-    for (size_t q = tid; q < nq; q += stride) {
-        float d[4], sp[4], gb[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gm[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gd[4], gs[4];
-        Quad<T>::ld(diffuse, q, d);
-        Quad<T>::ld(specular, q, sp);
-        if (g_basecolor) Quad<T>::ld(g_basecolor, q, gb);
-        if (g_metallic) Quad<T>::ld(g_metallic, q, gm);
+    quads_then_tail(n, vec_ok, tid, stride, [&](auto w, size_t i) {
+        constexpr int V = decltype(w)::value;
+        float d[V], sp[V], gb[V], gm[V], gd[V], gs[V];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) specular_to_metallic_backward_one(d[j], sp[j], gb[j], gm[j], albedo_srgb, gd[j], gs[j]);
-        if (g_diffuse) Quad<T>::st(g_diffuse, q, gd);
-        if (g_specular) Quad<T>::st(g_specular, q, gs);
-    }
-    for (size_t i = nq * 4 + tid; i < n; i += stride) {
-        float gd, gs;
-        specular_to_metallic_backward_one(Elem<T>::ld(diffuse, i), Elem<T>::ld(specular, i), g_basecolor ? Elem<T>::ld(g_basecolor, i) : 0.0f,
-                                          g_metallic ? Elem<T>::ld(g_metallic, i) : 0.0f, albedo_srgb, gd, gs);
-        if (g_diffuse) Elem<T>::st(g_diffuse, i, gd);
-        if (g_specular) Elem<T>::st(g_specular, i, gs);
-    }
+        for (int j = 0; j < V; ++j) { gb[j] = 0.0f; gm[j] = 0.0f; }
+        Span<T, V>::ld_nt(diffuse, i, d);
+        Span<T, V>::ld_nt(specular, i, sp);
+        if (g_basecolor) Span<T, V>::ld_nt(g_basecolor, i, gb);
+        if (g_metallic) Span<T, V>::ld_nt(g_metallic, i, gm);
+#pragma unroll
+        for (int j = 0; j < V; ++j) specular_to_metallic_backward_one(d[j], sp[j], gb[j], gm[j], albedo_srgb, gd[j], gs[j]);
+        if (g_diffuse) Span<T, V>::st_nt(g_diffuse, i, gd);
+        if (g_specular) Span<T, V>::st_nt(g_specular, i, gs);
+    });
 }
 
 
-template <typename T>
-static int fold_launch(const void *src, void *dst, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t ny, int32_t nx,
-                       int fold_batch, void *stream) {
-    const size_t items = (size_t)(fold_batch ? 1 : batch) * channels * h * w, al = 4 * sizeof(T);
-    if (w % 4 == 0 && is_aligned(src, al) && is_aligned(dst, al)) {
-        const StreamShape sh = stream_shape(items / 4, kShapeFold);
-        hipLaunchKernelGGL((fold_gradient_quad_kernel<T>), dim3(sh.grid), dim3(sh.block), sh.lds, static_cast<hipStream_t>(stream),
-                           src, dst, (int)batch, (int)channels, (int)h, (int)w, (int)ny, (int)nx, fold_batch);
-        return launch_status();
-    }
-    hipLaunchKernelGGL((fold_gradient_kernel<T>), dim3(stream_grid(items)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       src, dst, (int)batch, (int)channels, (int)h, (int)w, (int)ny, (int)nx, fold_batch);
+// Both colour transfers and both of their gradients: the entry points differ in the direction only.
+template <bool TO_LINEAR>
+static int colour_launch(const void *src, void *dst, size_t n, int dtype, void *stream) {
+    if (!src || !dst) return PBR_ERR_NULL_MAP;
+    if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
+    if (n == 0) return PBR_OK;
+    const int vec_ok = all_aligned(quad_bytes(dtype), {src, dst});
+    const StreamShape sh = stream_shape(vec_ok ? (n + 3) / 4 : n, kShapeColour);
+    with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((colour_kernel<T, TO_LINEAR>), dim3(sh.grid), dim3(sh.block), sh.lds, static_cast<hipStream_t>(stream), src, dst, n, vec_ok);
+    });
+    return launch_status();
+}
+
+template <bool TO_LINEAR>
+static int colour_backward_launch(const void *src, const void *gout, void *gin, size_t n, int dtype, void *stream) {
+    if (!src || !gout || !gin) return PBR_ERR_NULL_MAP;
+    if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
+    if (n == 0) return PBR_OK;
+    const int vec_ok = all_aligned(quad_bytes(dtype), {src, gout, gin});
+    const StreamShape sh = stream_shape(vec_ok ? (n + 3) / 4 : n, kShapeColourBwd);
+    with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((colour_backward_kernel<T, TO_LINEAR>), dim3(sh.grid), dim3(sh.block), sh.lds, static_cast<hipStream_t>(stream), src, gout, gin, n,
+                           vec_ok);
+    });
     return launch_status();
 }
 
@@ -524,31 +499,12 @@ static int fold_launch(const void *src, void *dst, int32_t batch, int32_t channe
 
 extern "C" {
 
-static int colour_launch(const void *src, void *dst, size_t n, int dtype, void *stream, bool to_linear) {
-    using namespace pbr;
-    if (!src || !dst) return PBR_ERR_NULL_MAP;
-    if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
-    if (n == 0) return PBR_OK;
-    const size_t al = dtype == PBR_F32 ? 16 : 8;
-    const int vec_ok = is_aligned(src, al) && is_aligned(dst, al);
-    const StreamShape sh = stream_shape(vec_ok ? (n + 3) / 4 : n, kShapeColour);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == PBR_F32) {
-        if (to_linear) hipLaunchKernelGGL((colour_kernel<float, true>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, dst, n, vec_ok);
-        else hipLaunchKernelGGL((colour_kernel<float, false>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, dst, n, vec_ok);
-    } else {
-        if (to_linear) hipLaunchKernelGGL((colour_kernel<__half, true>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, dst, n, vec_ok);
-        else hipLaunchKernelGGL((colour_kernel<__half, false>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, dst, n, vec_ok);
-    }
-    return launch_status();
-}
-
 int pbr_srgb_to_linear(const void *src, void *dst, size_t n, int dtype, void *stream) {
-    return colour_launch(src, dst, n, dtype, stream, true);
+    return pbr::colour_launch<true>(src, dst, n, dtype, stream);
 }
 
 int pbr_linear_to_srgb(const void *src, void *dst, size_t n, int dtype, void *stream) {
-    return colour_launch(src, dst, n, dtype, stream, false);
+    return pbr::colour_launch<false>(src, dst, n, dtype, stream);
 }
 
 int pbr_metallic_to_specular(const void *albedo, const void *metallic, void *diffuse, void *specular,
@@ -557,15 +513,14 @@ int pbr_metallic_to_specular(const void *albedo, const void *metallic, void *dif
     if (!albedo || !metallic || !diffuse || !specular) return PBR_ERR_NULL_MAP;
     if (batch < 1 || pixels < 1) return PBR_ERR_SHAPE;
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
-    const size_t al = dtype == PBR_F32 ? 16 : 8;
-    const int vec_ok = pixels % 4 == 0 && is_aligned(albedo, al) && is_aligned(metallic, al) && is_aligned(diffuse, al) && is_aligned(specular, al);
+    const int vec_ok = pixels % 4 == 0 && all_aligned(quad_bytes(dtype), {albedo, metallic, diffuse, specular});
     const size_t items = (size_t)batch * (size_t)pixels;
     const StreamShape sh = stream_shape(vec_ok ? items / 4 : items, kShapeM2S);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == PBR_F32)
-        hipLaunchKernelGGL((metallic_to_specular_kernel<float>), dim3(sh.grid), dim3(sh.block), sh.lds, s, albedo, metallic, diffuse, specular, (int)batch, pixels, albedo_is_srgb, vec_ok);
-    else
-        hipLaunchKernelGGL((metallic_to_specular_kernel<__half>), dim3(sh.grid), dim3(sh.block), sh.lds, s, albedo, metallic, diffuse, specular, (int)batch, pixels, albedo_is_srgb, vec_ok);
+    with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((metallic_to_specular_kernel<T>), dim3(sh.grid), dim3(sh.block), sh.lds, static_cast<hipStream_t>(stream), albedo, metallic, diffuse,
+                           specular, (int)batch, pixels, albedo_is_srgb, vec_ok);
+    });
     return launch_status();
 }
 
@@ -575,43 +530,22 @@ int pbr_specular_to_metallic(const void *diffuse, const void *specular, void *ba
     if (!diffuse || !specular || !basecolor || !metallic) return PBR_ERR_NULL_MAP;
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
     if (n == 0) return PBR_OK;
-    const size_t al = dtype == PBR_F32 ? 16 : 8;
-    const int vec_ok = is_aligned(diffuse, al) && is_aligned(specular, al) && is_aligned(basecolor, al) && is_aligned(metallic, al);
+    const int vec_ok = all_aligned(quad_bytes(dtype), {diffuse, specular, basecolor, metallic});
     const StreamShape sh = stream_shape(vec_ok ? (n + 3) / 4 : n, kShapeS2M);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == PBR_F32)
-        hipLaunchKernelGGL((specular_to_metallic_kernel<float>), dim3(sh.grid), dim3(sh.block), sh.lds, s, diffuse, specular, basecolor, metallic, n, albedo_is_srgb, vec_ok);
-    else
-        hipLaunchKernelGGL((specular_to_metallic_kernel<__half>), dim3(sh.grid), dim3(sh.block), sh.lds, s, diffuse, specular, basecolor, metallic, n, albedo_is_srgb, vec_ok);
-    return launch_status();
-}
-
-
-static int colour_backward_launch(const void *src, const void *gout, void *gin, size_t n, int dtype, void *stream, bool to_linear) {
-    using namespace pbr;
-    if (!src || !gout || !gin) return PBR_ERR_NULL_MAP;
-    if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
-    if (n == 0) return PBR_OK;
-    const size_t al = dtype == PBR_F32 ? 16 : 8;
-    const int vec_ok = is_aligned(src, al) && is_aligned(gout, al) && is_aligned(gin, al);
-    const StreamShape sh = stream_shape(vec_ok ? (n + 3) / 4 : n, kShapeColourBwd);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == PBR_F32) {
-        if (to_linear) hipLaunchKernelGGL((colour_backward_kernel<float, true>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, gout, gin, n, vec_ok);
-        else hipLaunchKernelGGL((colour_backward_kernel<float, false>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, gout, gin, n, vec_ok);
-    } else {
-        if (to_linear) hipLaunchKernelGGL((colour_backward_kernel<__half, true>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, gout, gin, n, vec_ok);
-        else hipLaunchKernelGGL((colour_backward_kernel<__half, false>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, gout, gin, n, vec_ok);
-    }
+    with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((specular_to_metallic_kernel<T>), dim3(sh.grid), dim3(sh.block), sh.lds, static_cast<hipStream_t>(stream), diffuse, specular,
+                           basecolor, metallic, n, albedo_is_srgb, vec_ok);
+    });
     return launch_status();
 }
 
 int pbr_srgb_to_linear_backward(const void *src, const void *grad_out, void *grad_in, size_t n, int dtype, void *stream) {
-    return colour_backward_launch(src, grad_out, grad_in, n, dtype, stream, true);
+    return pbr::colour_backward_launch<true>(src, grad_out, grad_in, n, dtype, stream);
 }
 
 int pbr_linear_to_srgb_backward(const void *src, const void *grad_out, void *grad_in, size_t n, int dtype, void *stream) {
-    return colour_backward_launch(src, grad_out, grad_in, n, dtype, stream, false);
+    return pbr::colour_backward_launch<false>(src, grad_out, grad_in, n, dtype, stream);
 }
 
 int pbr_metallic_to_specular_backward(const void *albedo, const void *metallic, const void *g_diffuse, const void *g_specular,
@@ -622,17 +556,17 @@ int pbr_metallic_to_specular_backward(const void *albedo, const void *metallic, 
     if (batch < 1 || pixels < 1) return PBR_ERR_SHAPE;
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
     if (!g_albedo && !g_metallic) return PBR_OK;
-    const size_t al = dtype == PBR_F32 ? 16 : 8;
-    auto ok = [&](const void *p) { return !p || is_aligned(p, al); };
-    const bool vec = pixels % 4 == 0 && ok(albedo) && ok(metallic) && ok(g_diffuse) && ok(g_specular) && ok(g_albedo) && ok(g_metallic);
+    const bool vec = pixels % 4 == 0 && all_aligned(quad_bytes(dtype), {albedo, metallic, g_diffuse, g_specular, g_albedo, g_metallic});
     const size_t items = (size_t)batch * (size_t)pixels;
     const StreamShape sh = stream_shape(vec ? items / 4 : items, kShapeM2SBwd);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-#define PBR_M2S_BWD(T, V) hipLaunchKernelGGL((metallic_to_specular_backward_kernel<T, V>), dim3(sh.grid), dim3(sh.block), sh.lds, s, albedo, metallic, \
-                                             g_diffuse, g_specular, g_albedo, g_metallic, (int)batch, pixels, albedo_is_srgb)
-    if (dtype == PBR_F32) { if (vec) PBR_M2S_BWD(float, true); else PBR_M2S_BWD(float, false); }
-    else { if (vec) PBR_M2S_BWD(__half, true); else PBR_M2S_BWD(__half, false); }
-#undef PBR_M2S_BWD
+    with_dtype(dtype, [&](auto t) {
+        with_width(vec, [&](auto w) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((metallic_to_specular_backward_kernel<T, decltype(w)::value == 4>), dim3(sh.grid), dim3(sh.block), sh.lds,
+                               static_cast<hipStream_t>(stream), albedo, metallic, g_diffuse, g_specular, g_albedo, g_metallic, (int)batch, pixels,
+                               albedo_is_srgb);
+        });
+    });
     return launch_status();
 }
 
@@ -642,27 +576,37 @@ int pbr_specular_to_metallic_backward(const void *diffuse, const void *specular,
     if (!diffuse || !specular) return PBR_ERR_NULL_MAP;
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
     if (n == 0 || (!g_diffuse && !g_specular)) return PBR_OK;
-    const size_t al = dtype == PBR_F32 ? 16 : 8;
-    auto ok = [&](const void *p) { return !p || is_aligned(p, al); };
-    const int vec_ok = ok(diffuse) && ok(specular) && ok(g_basecolor) && ok(g_metallic) && ok(g_diffuse) && ok(g_specular);
+    const int vec_ok = all_aligned(quad_bytes(dtype), {diffuse, specular, g_basecolor, g_metallic, g_diffuse, g_specular});
     const StreamShape sh = stream_shape(vec_ok ? (n + 3) / 4 : n, kShapeS2MBwd);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == PBR_F32)
-        hipLaunchKernelGGL((specular_to_metallic_backward_kernel<float>), dim3(sh.grid), dim3(sh.block), sh.lds, s, diffuse, specular, g_basecolor, g_metallic,
-                           g_diffuse, g_specular, n, albedo_is_srgb, vec_ok);
-    else
-        hipLaunchKernelGGL((specular_to_metallic_backward_kernel<__half>), dim3(sh.grid), dim3(sh.block), sh.lds, s, diffuse, specular, g_basecolor, g_metallic,
-                           g_diffuse, g_specular, n, albedo_is_srgb, vec_ok);
+    with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((specular_to_metallic_backward_kernel<T>), dim3(sh.grid), dim3(sh.block), sh.lds, static_cast<hipStream_t>(stream), diffuse,
+                           specular, g_basecolor, g_metallic, g_diffuse, g_specular, n, albedo_is_srgb, vec_ok);
+    });
     return launch_status();
 }
 
 int pbr_fold_gradient_typed(const void *src, void *dst, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t ny,
                             int32_t nx, int fold_batch, int dtype, void *stream) {
+    using namespace pbr;
     if (!src || !dst) return PBR_ERR_NULL_MAP;
     if (batch < 1 || channels < 1 || h < 1 || w < 1 || ny < 1 || nx < 1) return PBR_ERR_SHAPE;
-    if (dtype == PBR_F32) return pbr::fold_launch<float>(src, dst, batch, channels, h, w, ny, nx, fold_batch, stream);
-    if (dtype == PBR_F16) return pbr::fold_launch<__half>(src, dst, batch, channels, h, w, ny, nx, fold_batch, stream);
-    return PBR_ERR_DTYPE;
+    if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
+    const size_t items = (size_t)(fold_batch ? 1 : batch) * channels * h * w;
+    const bool quads = w % 4 == 0 && all_aligned(quad_bytes(dtype), {src, dst});
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (quads) {
+            const StreamShape sh = stream_shape(items / 4, kShapeFold);
+            hipLaunchKernelGGL((fold_gradient_quad_kernel<T>), dim3(sh.grid), dim3(sh.block), sh.lds, s, src, dst, (int)batch, (int)channels, (int)h, (int)w,
+                               (int)ny, (int)nx, fold_batch);
+        } else {
+            hipLaunchKernelGGL((fold_gradient_kernel<T>), dim3(stream_grid(items)), dim3(256), 0, s, src, dst, (int)batch, (int)channels, (int)h, (int)w,
+                               (int)ny, (int)nx, fold_batch);
+        }
+    });
+    return launch_status();
 }
 
 int pbr_fold_gradient(const void *src, void *dst, int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t ny,
@@ -680,42 +624,28 @@ int pbr_decode_normal(const void *src, void *dst, int32_t channels, int64_t pixe
     hipStream_t s = static_cast<hipStream_t>(stream);
     int *flag = static_cast<int *>(workspace);
     const unsigned grid = stream_grid((size_t)pixels);
-    const size_t esz = dtype == PBR_F32 ? 4 : 2, n = (size_t)pixels * 3;
+    const size_t n = (size_t)pixels * 3;
     if (channels == 2) {
         if (const int mrc = call_status(hipMemsetAsync(flag, 0, sizeof(int), s))) return mrc;
-    } else if (dtype == PBR_F32) {                                          // the probe writes the flag, 0 or 1
-        hipLaunchKernelGGL((normal_probe_kernel<float>), dim3(1), dim3(256), 0, s, src, n, flag);
-    } else {
-        hipLaunchKernelGGL((normal_probe_kernel<__half>), dim3(1), dim3(256), 0, s, src, n, flag);
     }
-    const char *s0 = static_cast<const char *>(src), *d0 = static_cast<const char *>(dst);
-    if (channels == 3 && (d0 + n * esz <= s0 || s0 + n * esz <= d0)) {      // disjoint: one pass (+ a conditional fix-up)
-        const int vec_ok = is_aligned(src, 4 * esz) && is_aligned(dst, 4 * esz);
-        const unsigned fix_grid = stream_grid(n / 16 + 1);
-        if (dtype == PBR_F32) {
-            hipLaunchKernelGGL((decode_normal_speculative_kernel<float>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
-            hipLaunchKernelGGL((keep_normal_kernel<float>), dim3(fix_grid), dim3(256), 0, s, src, dst, n, flag, vec_ok);
-        } else {
-            hipLaunchKernelGGL((decode_normal_speculative_kernel<__half>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
-            hipLaunchKernelGGL((keep_normal_kernel<__half>), dim3(fix_grid), dim3(256), 0, s, src, dst, n, flag, vec_ok);
+    with_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (channels == 2) {
+            hipLaunchKernelGGL((decode_normal_kernel<T, 2>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
+            return;
         }
-        return launch_status();
-    }
-    if (dtype == PBR_F32) {
-        if (channels == 3) {
-            hipLaunchKernelGGL((any_negative_kernel<float>), dim3(stream_grid((size_t)pixels * 3 / 16)), dim3(256), 0, s, src, (size_t)pixels * 3, flag, (int)is_aligned(src, 16));
-            hipLaunchKernelGGL((decode_normal_kernel<float, 3>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
+        hipLaunchKernelGGL((normal_probe_kernel<T>), dim3(1), dim3(256), 0, s, src, n, flag);      // the probe writes the flag, 0 or 1
+        const char *s0 = static_cast<const char *>(src), *d0 = static_cast<const char *>(dst);
+        const size_t bytes = n * sizeof(T);
+        if (d0 + bytes <= s0 || s0 + bytes <= d0) {                                                 // disjoint: one pass (+ a conditional fix-up)
+            const int vec_ok = all_aligned(quad_bytes(dtype), {src, dst});
+            hipLaunchKernelGGL((decode_normal_speculative_kernel<T>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
+            hipLaunchKernelGGL((keep_normal_kernel<T>), dim3(stream_grid(n / 16 + 1)), dim3(256), 0, s, src, dst, n, flag, vec_ok);
         } else {
-            hipLaunchKernelGGL((decode_normal_kernel<float, 2>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
+            hipLaunchKernelGGL((any_negative_kernel<T>), dim3(stream_grid(n / 16)), dim3(256), 0, s, src, n, flag, (int)all_aligned(quad_bytes(dtype), {src}));
+            hipLaunchKernelGGL((decode_normal_kernel<T, 3>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
         }
-    } else {
-        if (channels == 3) {
-            hipLaunchKernelGGL((any_negative_kernel<__half>), dim3(stream_grid((size_t)pixels * 3 / 16)), dim3(256), 0, s, src, (size_t)pixels * 3, flag, (int)is_aligned(src, 8));
-            hipLaunchKernelGGL((decode_normal_kernel<__half, 3>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
-        } else {
-            hipLaunchKernelGGL((decode_normal_kernel<__half, 2>), dim3(grid), dim3(256), 0, s, src, dst, pixels, flag);
-        }
-    }
+    });
     return launch_status();
 }
 
@@ -726,19 +656,16 @@ int pbr_decode_normal_backward(const void *src, const void *grad_out, void *grad
     if (!src || !grad_out || !grad_in || !workspace) return PBR_ERR_NULL_MAP;
     if (pixels < 1) return PBR_ERR_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const unsigned grid = stream_grid((size_t)pixels);
     auto a = static_cast<const float *>(src), g = static_cast<const float *>(grad_out);
     float *gi = static_cast<float *>(grad_in);
     const int *flag = static_cast<const int *>(workspace);
-    if (pixels % 4 == 0 && is_aligned(src, 16) && is_aligned(grad_out, 16) && is_aligned(grad_in, 16)) {
-        const unsigned vgrid = stream_grid((size_t)pixels / 4);
-        if (channels == 3) hipLaunchKernelGGL((decode_normal_backward_kernel<3, 4>), dim3(vgrid), dim3(256), 0, s, a, g, gi, pixels, flag);
-        else hipLaunchKernelGGL((decode_normal_backward_kernel<2, 4>), dim3(vgrid), dim3(256), 0, s, a, g, gi, pixels, flag);
-    } else if (channels == 3) {
-        hipLaunchKernelGGL((decode_normal_backward_kernel<3, 1>), dim3(grid), dim3(256), 0, s, a, g, gi, pixels, flag);
-    } else {
-        hipLaunchKernelGGL((decode_normal_backward_kernel<2, 1>), dim3(grid), dim3(256), 0, s, a, g, gi, pixels, flag);
-    }
+    const bool vec = pixels % 4 == 0 && all_aligned(16, {src, grad_out, grad_in});
+    const unsigned grid = stream_grid((size_t)pixels / (vec ? 4 : 1));
+    with_width(vec, [&](auto w) {
+        constexpr int V = decltype(w)::value;
+        if (channels == 3) hipLaunchKernelGGL((decode_normal_backward_kernel<3, V>), dim3(grid), dim3(256), 0, s, a, g, gi, pixels, flag);
+        else hipLaunchKernelGGL((decode_normal_backward_kernel<2, V>), dim3(grid), dim3(256), 0, s, a, g, gi, pixels, flag);
+    });
     return launch_status();
 }
 

@@ -22,35 +22,7 @@
 namespace pbr {
 namespace {
 
-// V consecutive elements at element offset i (V = 4: 16-byte fp32 / 8-byte fp16 accesses; the caller checked the alignment)
-template <typename T, int V> struct Vec;
-template <typename T> struct Vec<T, 1> {
-    static __device__ __forceinline__ void ld(const void *p, int64_t i, float v[1]) { v[0] = Elem<T>::ld(p, i); }
-    static __device__ __forceinline__ void st(void *p, int64_t i, const float v[1]) { Elem<T>::st(p, i, v[0]); }
-};
-template <> struct Vec<float, 4> {
-    typedef float v4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ void ld(const void *p, int64_t i, float v[4]) {
-        const v4 t = *reinterpret_cast<const v4 *>(static_cast<const float *>(p) + i);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    static __device__ __forceinline__ void st(void *p, int64_t i, const float v[4]) {
-        const v4 t = {v[0], v[1], v[2], v[3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<v4 *>(static_cast<float *>(p) + i));
-    }
-};
-template <> struct Vec<__half, 4> {
-    typedef _Float16 v4 __attribute__((ext_vector_type(4)));
-    static __device__ __forceinline__ void ld(const void *p, int64_t i, float v[4]) {
-        const v4 t = *reinterpret_cast<const v4 *>(static_cast<const _Float16 *>(p) + i);
-        v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)t.z; v[3] = (float)t.w;
-    }
-    static __device__ __forceinline__ void st(void *p, int64_t i, const float v[4]) {
-        const v4 t = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        __builtin_nontemporal_store(t, reinterpret_cast<v4 *>(static_cast<_Float16 *>(p) + i));
-    }
-};
-
+// (V consecutive elements at an element offset: Span<T, V>, launch_util.hpp -- plain loads, non-temporal stores)
 // One row of the height map as a wave sees it: lane l holds the V pixels of unit u (x = u V ... u V + V - 1), lane 0 also the pixel
 // left of its unit and lane 63 the pixel right of its unit (the neighbours the other lanes take from their neighbour lane).  Rows
 // outside the map, units outside the row and pixels outside the map are 0 (the reference's zero padding).
@@ -62,7 +34,7 @@ template <typename T, int V> struct HRow {
         el = 0.0f; er = 0.0f;
         if (r < 0 || r >= H) return;
         const int64_t row = (int64_t)r * W, x0 = (int64_t)u * V;
-        if (live) Vec<T, V>::ld(h, row + x0, v);
+        if (live) Span<T, V>::ld(h, row + x0, v);
         if (lane == 0 && x0 > 0 && x0 <= W) el = Elem<T>::ld(h, row + x0 - 1);
         if (lane == 63 && x0 + V < W) er = Elem<T>::ld(h, row + x0 + V);
     }
@@ -120,9 +92,9 @@ __global__ __launch_bounds__(256) void normal_from_height_kernel(const void *__r
         }
         if (live) {
             const int64_t o = (int64_t)y * W + (int64_t)u * V;
-            Vec<T, V>::st(nb, o, nx);
-            Vec<T, V>::st(nb, n_ps + o, ny);
-            Vec<T, V>::st(nb, 2 * n_ps + o, nz);
+            Span<T, V>::st_nt(nb, o, nx);
+            Span<T, V>::st_nt(nb, n_ps + o, ny);
+            Span<T, V>::st_nt(nb, 2 * n_ps + o, nz);
         }
         up = cur; cur = dn; dn = nxt;
     }
@@ -175,9 +147,9 @@ __global__ __launch_bounds__(256) void normal_from_height_backward_kernel(const 
         const bool row_in = r >= 0 && r < H;
         if (live && row_in) {
             const int64_t o = (int64_t)r * W + (int64_t)u * V;
-            Vec<float, V>::ld(g, o, gx);
-            Vec<float, V>::ld(g, g_ps + o, gy);
-            Vec<float, V>::ld(g, 2 * g_ps + o, gz);
+            Span<float, V>::ld(g, o, gx);
+            Span<float, V>::ld(g, g_ps + o, gy);
+            Span<float, V>::ld(g, 2 * g_ps + o, gz);
         }
         float left, right;
         hc.sides(lane, left, right);
@@ -196,7 +168,7 @@ __global__ __launch_bounds__(256) void normal_from_height_backward_kernel(const 
                 const float al = j == 0 ? a_left : ga1[j - 1], ar = j == V - 1 ? a_right : ga1[j + 1];
                 out[j] = fmaf(sb, gb0[j] - gb2[j], scale * (al - ar));
             }
-            if (writes) Vec<float, V>::st(gh, (int64_t)(r - 1) * W + (int64_t)u * V, out);
+            if (writes) Span<float, V>::st_nt(gh, (int64_t)(r - 1) * W + (int64_t)u * V, out);
         }
 #pragma unroll
         for (int j = 0; j < V; ++j) { gb2[j] = gb1[j]; gb1[j] = gb0[j]; ga1[j] = ga0[j]; }
@@ -214,14 +186,14 @@ __global__ __launch_bounds__(256) void normal_transform_kernel(const void *src, 
     const int64_t b = q / units, p = (q - b * units) * V;
     const int64_t so = b * s_bs + p, dO = b * d_bs + p;
     float x[V], y[V], z[V];
-    Vec<T, V>::ld(src, so, x);
-    Vec<T, V>::ld(src, so + s_ps, y);
-    Vec<T, V>::ld(src, so + 2 * s_ps, z);
+    Span<T, V>::ld(src, so, x);
+    Span<T, V>::ld(src, so + s_ps, y);
+    Span<T, V>::ld(src, so + 2 * s_ps, z);
 #pragma unroll
     for (int j = 0; j < V; ++j) normal_affine(M, x[j], y[j], z[j]);
-    Vec<T, V>::st(dst, dO, x);                                         // dst == src: every lane reads its pixels before it writes them
-    Vec<T, V>::st(dst, dO + d_ps, y);
-    Vec<T, V>::st(dst, dO + 2 * d_ps, z);
+    Span<T, V>::st_nt(dst, dO, x);                                         // dst == src: every lane reads its pixels before it writes them
+    Span<T, V>::st_nt(dst, dO + d_ps, y);
+    Span<T, V>::st_nt(dst, dO + 2 * d_ps, z);
 }
 
 // normal_affine_backward per pixel: g_v = renorm ? (g - n (n . g)) / |v|  (g / 1e-12 where the clamp held) : g;  g_xy = M^T g_v_xy, g_z = g_v_z
@@ -234,17 +206,17 @@ __global__ __launch_bounds__(256) void normal_transform_backward_kernel(const fl
     const int64_t b = q / units, p = (q - b * units) * V;
     const int64_t so = b * s_bs + p, go = b * g_bs + p, io = b * gi_bs + p;
     float x[V], y[V], z[V], gx[V], gy[V], gz[V];
-    Vec<float, V>::ld(src, so, x);
-    Vec<float, V>::ld(src, so + s_ps, y);
-    Vec<float, V>::ld(src, so + 2 * s_ps, z);
-    Vec<float, V>::ld(grad, go, gx);
-    Vec<float, V>::ld(grad, go + g_ps, gy);
-    Vec<float, V>::ld(grad, go + 2 * g_ps, gz);
+    Span<float, V>::ld(src, so, x);
+    Span<float, V>::ld(src, so + s_ps, y);
+    Span<float, V>::ld(src, so + 2 * s_ps, z);
+    Span<float, V>::ld(grad, go, gx);
+    Span<float, V>::ld(grad, go + g_ps, gy);
+    Span<float, V>::ld(grad, go + 2 * g_ps, gz);
 #pragma unroll
     for (int j = 0; j < V; ++j) normal_affine_backward(M, x[j], y[j], z[j], gx[j], gy[j], gz[j]);
-    Vec<float, V>::st(grad_in, io, gx);
-    Vec<float, V>::st(grad_in, io + gi_ps, gy);
-    Vec<float, V>::st(grad_in, io + 2 * gi_ps, gz);
+    Span<float, V>::st_nt(grad_in, io, gx);
+    Span<float, V>::st_nt(grad_in, io + gi_ps, gy);
+    Span<float, V>::st_nt(grad_in, io + 2 * gi_ps, gz);
 }
 
 // Rows per wave of the stencil walks: enough waves to fill the chip (about 16 per CU), at least 8 rows so that the two halo rows
@@ -272,8 +244,7 @@ int pbr_normal_from_height(const void *height, int64_t height_batch_stride, void
     if (!stencil_shape_ok(batch, height_px, width) || height_batch_stride < 0 || normal_batch_stride < 0 || normal_plane_stride < 0)
         return PBR_ERR_SHAPE;
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
-    const size_t esz = dtype == PBR_F32 ? 4 : 2;
-    const bool vec = width % 4 == 0 && is_aligned(height, 4 * esz) && is_aligned(normal, 4 * esz) && height_batch_stride % 4 == 0 &&
+    const bool vec = width % 4 == 0 && all_aligned(quad_bytes(dtype), {height, normal}) && height_batch_stride % 4 == 0 &&
                      normal_batch_stride % 4 == 0 && normal_plane_stride % 4 == 0;
     const int V = vec ? 4 : 1, units = width / V;
     const int64_t strips = (units + 63) / 64, groups = (strips + 3) / 4;
@@ -281,12 +252,14 @@ int pbr_normal_from_height(const void *height, int64_t height_batch_stride, void
     const int64_t blocks = groups * bands * (int64_t)batch;
     if (blocks > 0x7fffffff) return PBR_ERR_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define PBR_NFH(T, VV) hipLaunchKernelGGL((normal_from_height_kernel<T, VV>), dim3((unsigned)blocks), dim3(256), 0, s, height, height_batch_stride, \
-                                          normal, normal_batch_stride, normal_plane_stride, (int)height_px, (int)width, rows, bands, (int)groups, \
-                                          scale, (int)(directx != 0))
-    if (dtype == PBR_F32) { if (vec) PBR_NFH(float, 4); else PBR_NFH(float, 1); }
-    else { if (vec) PBR_NFH(__half, 4); else PBR_NFH(__half, 1); }
-#undef PBR_NFH
+    with_dtype(dtype, [&](auto t) {
+        with_width(vec, [&](auto w) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((normal_from_height_kernel<T, decltype(w)::value>), dim3((unsigned)blocks), dim3(256), 0, s, height, height_batch_stride,
+                               normal, normal_batch_stride, normal_plane_stride, (int)height_px, (int)width, rows, bands, (int)groups, scale,
+                               (int)(directx != 0));
+        });
+    });
     return launch_status();
 }
 
@@ -298,7 +271,7 @@ int pbr_normal_from_height_backward(const void *height, int64_t height_batch_str
     if (!stencil_shape_ok(batch, height_px, width) || height_batch_stride < 0 || grad_batch_stride < 0 || grad_plane_stride < 0 ||
         grad_height_batch_stride < 0)
         return PBR_ERR_SHAPE;
-    const bool vec = width % 4 == 0 && is_aligned(height, 16) && is_aligned(grad_normal, 16) && is_aligned(grad_height, 16) &&
+    const bool vec = width % 4 == 0 && all_aligned(16, {height, grad_normal, grad_height}) &&
                      height_batch_stride % 4 == 0 && grad_batch_stride % 4 == 0 && grad_plane_stride % 4 == 0 && grad_height_batch_stride % 4 == 0;
     const int V = vec ? 4 : 1, units = width / V;
     const int64_t strips = (units + 61) / 62, groups = (strips + 3) / 4;
@@ -308,11 +281,11 @@ int pbr_normal_from_height_backward(const void *height, int64_t height_batch_str
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto h = static_cast<const float *>(height), g = static_cast<const float *>(grad_normal);
     auto gh = static_cast<float *>(grad_height);
-#define PBR_NFH_BWD(VV) hipLaunchKernelGGL((normal_from_height_backward_kernel<VV>), dim3((unsigned)blocks), dim3(256), 0, s, h, height_batch_stride, \
-                                           g, grad_batch_stride, grad_plane_stride, gh, grad_height_batch_stride, (int)height_px, (int)width, rows, \
-                                           bands, (int)groups, scale, (int)(directx != 0))
-    if (vec) PBR_NFH_BWD(4); else PBR_NFH_BWD(1);
-#undef PBR_NFH_BWD
+    with_width(vec, [&](auto w) {
+        hipLaunchKernelGGL((normal_from_height_backward_kernel<decltype(w)::value>), dim3((unsigned)blocks), dim3(256), 0, s, h, height_batch_stride, g,
+                           grad_batch_stride, grad_plane_stride, gh, grad_height_batch_stride, (int)height_px, (int)width, rows, bands, (int)groups,
+                           scale, (int)(directx != 0));
+    });
     return launch_status();
 }
 
@@ -324,19 +297,20 @@ int pbr_normal_transform(const void *src, int64_t src_batch_stride, int64_t src_
     if (batch < 1 || pixels < 1 || src_batch_stride < 0 || src_plane_stride < 0 || dst_batch_stride < 0 || dst_plane_stride < 0)
         return PBR_ERR_SHAPE;
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
-    const size_t esz = dtype == PBR_F32 ? 4 : 2;
-    const bool vec = pixels % 4 == 0 && is_aligned(src, 4 * esz) && is_aligned(dst, 4 * esz) && src_batch_stride % 4 == 0 &&
+    const bool vec = pixels % 4 == 0 && all_aligned(quad_bytes(dtype), {src, dst}) && src_batch_stride % 4 == 0 &&
                      src_plane_stride % 4 == 0 && dst_batch_stride % 4 == 0 && dst_plane_stride % 4 == 0;
     const Affine M = make_affine(m00, m01, m10, m11, renormalize);
     const int64_t units = vec ? pixels / 4 : pixels, total = units * batch;
     const StreamShape sh = stream_shape((size_t)total, {1, 0});
     if ((int64_t)sh.grid * sh.block < total) return PBR_ERR_SHAPE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define PBR_NT(T, VV) hipLaunchKernelGGL((normal_transform_kernel<T, VV>), dim3(sh.grid), dim3(sh.block), 0, s, src, src_batch_stride, src_plane_stride, \
-                                         dst, dst_batch_stride, dst_plane_stride, units, total, M)
-    if (dtype == PBR_F32) { if (vec) PBR_NT(float, 4); else PBR_NT(float, 1); }
-    else { if (vec) PBR_NT(__half, 4); else PBR_NT(__half, 1); }
-#undef PBR_NT
+    with_dtype(dtype, [&](auto t) {
+        with_width(vec, [&](auto w) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((normal_transform_kernel<T, decltype(w)::value>), dim3(sh.grid), dim3(sh.block), 0, s, src, src_batch_stride, src_plane_stride,
+                               dst, dst_batch_stride, dst_plane_stride, units, total, M);
+        });
+    });
     return launch_status();
 }
 
@@ -349,7 +323,7 @@ int pbr_normal_transform_backward(const void *src, int64_t src_batch_stride, int
     if (batch < 1 || pixels < 1 || src_batch_stride < 0 || src_plane_stride < 0 || grad_batch_stride < 0 || grad_plane_stride < 0 ||
         grad_in_batch_stride < 0 || grad_in_plane_stride < 0)
         return PBR_ERR_SHAPE;
-    const bool vec = pixels % 4 == 0 && is_aligned(src, 16) && is_aligned(grad_out, 16) && is_aligned(grad_in, 16) && src_batch_stride % 4 == 0 &&
+    const bool vec = pixels % 4 == 0 && all_aligned(16, {src, grad_out, grad_in}) && src_batch_stride % 4 == 0 &&
                      src_plane_stride % 4 == 0 && grad_batch_stride % 4 == 0 && grad_plane_stride % 4 == 0 && grad_in_batch_stride % 4 == 0 &&
                      grad_in_plane_stride % 4 == 0;
     const Affine M = make_affine(m00, m01, m10, m11, renormalize);
@@ -359,11 +333,10 @@ int pbr_normal_transform_backward(const void *src, int64_t src_batch_stride, int
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto a = static_cast<const float *>(src), g = static_cast<const float *>(grad_out);
     auto gi = static_cast<float *>(grad_in);
-#define PBR_NT_BWD(VV) hipLaunchKernelGGL((normal_transform_backward_kernel<VV>), dim3(sh.grid), dim3(sh.block), 0, s, a, src_batch_stride, \
-                                          src_plane_stride, g, grad_batch_stride, grad_plane_stride, gi, grad_in_batch_stride, grad_in_plane_stride, \
-                                          units, total, M)
-    if (vec) PBR_NT_BWD(4); else PBR_NT_BWD(1);
-#undef PBR_NT_BWD
+    with_width(vec, [&](auto w) {
+        hipLaunchKernelGGL((normal_transform_backward_kernel<decltype(w)::value>), dim3(sh.grid), dim3(sh.block), 0, s, a, src_batch_stride, src_plane_stride,
+                           g, grad_batch_stride, grad_plane_stride, gi, grad_in_batch_stride, grad_in_plane_stride, units, total, M);
+    });
     return launch_status();
 }
 

@@ -1,6 +1,7 @@
 // stream_shape.hpp -- launch shape of the streaming kernels: stream_shape with its per-kernel rules, and stream_grid, the grid of the
 // grid-stride kernels.  Every translation unit with a launcher includes it, directly or through ct_launch.hpp, and with it
-// launch_util.hpp (hip_code, launch_status, call_status, is_aligned, resident_cus, Elem<T>).
+// launch_util.hpp (hip_code, launch_status, call_status, is_aligned, all_aligned, quad_bytes, resident_cus, with_dtype, with_width,
+// Elem<T>, Span<T, V>).
 #pragma once
 #include <cstddef>
 
