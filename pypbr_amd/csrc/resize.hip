@@ -3,14 +3,14 @@
 // Replaces MaterialBase.resize (/root/reference/pypbr/materials/base.py:490-504); the tap rule: resize_taps.hpp.  The gradient:
 // resize_backward.hip.  The kernel families and which shapes each takes: pbr_resize_form in include/pbr_hip.h.  Here: the two-tap
 // up-scale and the two generic passes; the general one-kernel form lives in resize_strip.hpp, the register-only band walk in
-// resize_down.hpp, the row walk in resize_stream.hpp.
+// resize_down.hpp, the row walk in resize_stream.hpp, the lane frame the two-tap kernel shares with the gradient's in resize_lane.hpp.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cstdint>
 
 #include "../../include/pbr_hip.h"
 #include "resize_down.hpp"
+#include "resize_lane.hpp"
 #include "resize_stream.hpp"
 #include "resize_strip.hpp"
 #include "resize_taps.hpp"
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void resize_height_kernel(const float *__restr
     }
 }
 
-// ---- up-scaling on both axes: two taps per axis, registers only (round 3) --------------------------------------------------
+// ---- up-scaling on both axes: two taps per axis, registers only ------------------------------------------------------------
 // With scale <= 1 on both axes an output pixel has at most two taps per axis (support = 1), so neither the tap tables nor the
 // LDS strip of resize_strip_kernel are needed: a lane owns FOUR consecutive output pixels of a row.  Their taps lie in at most five
 // consecutive input columns; the lane loads six from each of the row's two input rows (one 16-byte and one 8-byte load per row,
@@ -76,14 +76,12 @@ __global__ __launch_bounds__(256) void resize_height_kernel(const float *__restr
 template <int kUpRows>
 __global__ __launch_bounds__(64) void resize_up2_kernel(const float *__restrict__ src, float *__restrict__ dst, int h_in, int w_in, int h_out,
                                                         int w_out, int groups_x, int groups_y, uint32_t xcd_groups, AxisFilter fw, AxisFilter fh) {
-    const uint32_t wg = xcd_run_order(blockIdx.x, xcd_groups);
-    const uint32_t band = wg / (uint32_t)groups_x, gx = wg - band * (uint32_t)groups_x;    // band = plane * groups_y + (y / kUpRows)
-    const int plane = (int)(band / (uint32_t)groups_y), yb = (int)(band - (uint32_t)plane * (uint32_t)groups_y) * kUpRows;
+    const LanePos p = lane_position<kUpRows>(groups_x, groups_y, xcd_groups);
+    const int plane = p.plane, yb = p.r0;
     // Lanes past the row's end stay in the wave (they work on column 0 and store nothing): the rows' taps below are read ACROSS lanes,
     // and a lane that has left has no defined values (the compiler is free to form them after the exit).
-    const int x_raw = ((int)gx * 64 + (int)threadIdx.x) * 4;
-    const bool live = x_raw < w_out;
-    const int x0 = live ? x_raw : 0;
+    const bool live = p.k0 < w_out;
+    const int x0 = live ? p.k0 : 0;
     // The rows' taps are wave-uniform (every lane of the workgroup works on rows yb .. yb + kUpRows - 1) but floating-point: the scalar unit
     // cannot form them, and formed per lane they were ~30 vector instructions per row and lane (VALU busy 0.69 in a launch that should wait
     // for its stores).  Lane r forms row r's taps ONCE; the others read them through v_readlane (same arithmetic, same bits).
@@ -123,33 +121,22 @@ __global__ __launch_bounds__(64) void resize_up2_kernel(const float *__restrict_
         }
         float *q = dp + (int64_t)y * w_out;
         if (!live) continue;
-        if (whole) {
-            typedef float sf4 __attribute__((ext_vector_type(4), aligned(4)));
-            const sf4 v = {out[0], out[1], out[2], out[3]};
-            __builtin_nontemporal_store(v, reinterpret_cast<sf4 *>(q));
-        } else {
-            for (int k = 0; k < w_out - x0; ++k) q[k] = out[k];
-        }
+        store_quad(q, out, whole, w_out - x0);
     }
 }
+
 // The three weight vectors of resize_down_kernel for the whole factor S (antialiased): an axis of 16 outputs has them all -- output 0 (window clipped
 // on the left), output 5 (whole window) and output 15 (clipped on the right) -- and they do not depend on the axis' length: with n_in = S n_out the
 // tap positions relative to the window are small whole and half numbers, exact in float, whatever the output's index.  Formed with the strip kernel's statements (phase 0 of resize_strip_kernel).
 static DownTaps down_taps(int S) {
-    DownTaps t;
     const AxisFilter f = make_filter(16 * S, 16, true);
-    const int which[3] = {5, 0, 15};
-    float *const into[3] = {t.wi, t.wl, t.wr};
-    for (int s = 0; s < 3; ++s) {
-        const int i = which[s];
+    return make_down_taps([&](int i, float *w) {
         int xmin, n; float center;
         const float inv = window_norm(f, i, xmin, n, center);
-        for (int j = 0; j < 32; ++j) into[s][j] = 0.0f;
         const int shift = xmin - (S * i - S / 2);            // the window's first tap among the K = 2 S of an unclipped one
         for (int j = 0; j < n; ++j)
-            if (shift + j >= 0 && shift + j < 32) into[s][shift + j] = tap_weight(f, j, xmin, center) * inv;
-    }
-    return t;
+            if (shift + j >= 0 && shift + j < 32) w[shift + j] = tap_weight(f, j, xmin, center) * inv;
+    });
 }
 // Launch of resize_down_kernel: `small` = the side with 1 / S^2 of the elements (the down-scale's result, the up-scale's gradient).  False when the
 // shape is not the kernel's (the caller goes on to its other forms).
@@ -270,19 +257,18 @@ static int resize_forward(const void *src, void *dst, int64_t planes, int32_t h_
     float *tmp = static_cast<float *>(workspace);
     const AxisFilter fw = make_filter(w_in, w_out, antialias != 0), fh = make_filter(h_in, h_out, antialias != 0);
     if (g_resize_up2 && fw.scale <= 1.0f && fh.scale <= 1.0f && w_in >= 6) {
-        // up-scaling (or 1:1) on both axes: the two-tap register form.  3 x 4096^2 -> 6144^2 (resize_sweep.py (a probe of its round, removed with its knob: git 9ce0718:tools/), round 3).
-        // Output rows per lane.  Measured (resize_up_ab.py (a probe of its round, removed with its knob: git 9ce0718:tools/), 3 planes, us, rows 2 / 4 / 8; strip kernel for scale):
+        // up-scaling (or 1:1) on both axes: the two-tap register form.  3 x 4096^2 -> 6144^2 (resize_sweep.py).
+        // Output rows per lane.  Measured (resize_up_ab.py, 3 planes, us, rows 2 / 4 / 8; strip kernel for scale):
         //   4096^2 -> 6144^2  131.4 / 121.6 / 110.8 (157)    -> 8192^2  215.3 / 195.5 / 184.7 (270)    2048^2 -> 4096^2  59.0 / 53.6 / 53.0 (64)
         //   4096^2 -> 4608^2   79.1 /  70.0 /  73.1 (101)    -> 4096^2   63.7 /  61.2 /  66.0 (95)
         // 8 from 1.25x up (the column taps' share shrinks as the rows grow), 4 below.
         const int rows = fh.scale <= 0.8f ? 8 : 4;
-        const int64_t groups_x = (w_out + 255) / 256, groups_y = (h_out + rows - 1) / rows, n_groups = groups_x * groups_y * planes;
-        if (n_groups <= INT32_MAX) {
+        const LaneGrid grid = lane_grid(w_out, h_out, rows, planes);
+        if (grid.fits) {
             auto fn = rows == 8 ? resize_up2_kernel<8> : resize_up2_kernel<4>;
             *form = PBR_RESIZE_TWO_TAP;
             if (dry) return PBR_OK;
-            hipLaunchKernelGGL(fn, dim3((unsigned)n_groups), dim3(64), 0, s, static_cast<const float *>(src), static_cast<float *>(dst),
-                               (int)h_in, (int)w_in, (int)h_out, (int)w_out, (int)groups_x, (int)groups_y, xcd_run_groups(n_groups), fw, fh);
+            launch_lanes(fn, grid, s, static_cast<const float *>(src), static_cast<float *>(dst), h_in, w_in, h_out, w_out, fw, fh);
             return launch_status();
         }
     }
@@ -311,12 +297,12 @@ static int resize_forward(const void *src, void *dst, int64_t planes, int32_t h_
         return launch_status();
     }
     {   // strip form: tap tables + the height-reduced strip [toh][pitch] of a toh x 64 output tile in LDS, up to 36 taps per axis
-        // (round 5: 16 -> 36 taps, i.e. down-scales below 17x keep the one-kernel form)
+        // (16 -> 36 taps, i.e. down-scales below 17x keep the one-kernel form)
         const int kx = (int)(2.0f * fw.support) + 3, ky = (int)(2.0f * fh.support) + 3;      // taps per output: xsize <= 2 support + 2
         const int cols_max = (int)(kTileW * fw.scale + 2.0f * fw.support) + 4 + 3;           // + 3: window start aligned down to 16 bytes
         // Output rows per workgroup: as many as keep the workgroup's LDS within 24 KiB (6 workgroups per CU).  More rows
         // amortise the tables and re-read fewer input rows; more resident workgroups overlap the phases
-        // (resize_sweep.py (a probe of its round, removed with its knob: git 9ce0718:tools/): 2x down 32-64 rows, 3-4x down 16, up-scales 64-128).
+        // (resize_sweep.py: 2x down 32-64 rows, 3-4x down 16, up-scales 64-128).
         // 16-byte stores in the forward width pass (QUADS): 62.7 against 54.0 us with them (4096^2 -> 2048^2): never.
         StripLaunch l;
         if (kx <= 36 && ky <= 36 && strip_launch(l, planes, h_out, w_out, kx, ky, cols_max, w_in % 4 == 0 && is_aligned(src, 16), 40, 24 * 1024)) {

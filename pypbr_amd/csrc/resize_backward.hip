@@ -2,14 +2,15 @@
 //
 // The kernel families, in the order pbr_resize_bilinear_backward tries them: the band walk of resize_down.hpp with the transposed two-tap
 // weights (whole power-of-two up-scales), the two-tap transpose (other up-scales), the register gather over transposed tap tables, the
-// strip kernel of resize_strip.hpp with those tables, and the two generic passes through the workspace.
+// strip kernel of resize_strip.hpp with those tables, and the two generic passes through the workspace.  The two register kernels stand in
+// the lane frame of resize_lane.hpp; here: where their column and row weights come from, and the host's window scan (worst_span).
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cstdint>
 
 #include "../../include/pbr_hip.h"
 #include "resize_down.hpp"
+#include "resize_lane.hpp"
 #include "resize_strip.hpp"
 #include "resize_taps.hpp"
 #include "stream_shape.hpp"
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(256) void resize_backward_cols_kernel(const float *
     }
 }
 
-// ---- transposed tap tables (round 3, after the counters: the generic kernels above re-derive every candidate's
+// ---- transposed tap tables (after the counters: the generic kernels above re-derive every candidate's
 // window per element and are VALU-bound -- 132 + 221 us for a 2048^2 -> 4096^2 gradient, VALUs saturated, 0.15 of HBM).
 // A small kernel writes, per INPUT index k of an axis, the first contributing output `lo[k]`, their number `cnt[k]` and the
 // normalised weights w[j][k] (j-major: lanes that walk k read them coalesced); the kernels that read them are then pure fma streams.
@@ -160,33 +161,24 @@ __global__ __launch_bounds__(256) void resize_backward_tables_kernel(int *__rest
         rec[8 + kBandRows * j + r] = d >= 0 && d < n ? wy[(size_t)d * fh.n_in + k] : 0.0f;
     }
 }
-// ---- gradient of an up-scale: the transpose of resize_up2_kernel, registers only (round 4) ---------------------------------------
+// ---- gradient of an up-scale: the transpose of resize_up2_kernel, registers only -------------------------------------------------
 // out[y][x] = sum over two rows and two columns of wy wx in[..]; the gradient g_in[ky][kx] gathers g_out over the outputs whose
 // two-tap windows hold (ky, kx).  Windows start at first_tap(i), which is monotone in i, so the outputs that touch gradient columns
-// k0 .. k0 + 3 are the contiguous range first_tap(i) in [k0 - 1, k0 + 3]: at most 5 / scale + 1 of them.  A lane owns FOUR consecutive
-// gradient columns of R rows: it finds the start of its range once (a short search around the closed-form estimate, with the forward's
-// own arithmetic), builds the 4 x W matrix of column weights in registers (W = 8 | 12 | 16 upstream columns; zero where an output
-// does not touch a column), then walks the upstream rows that touch its R gradient rows: W / 4 16-byte loads, 4 W fma for the width
-// sum, 4 R fma into the accumulators with the row's (wave-uniform) weights.  No tables, no LDS, no barriers -- the strip kernel with
-// transposed tables (resize_strip_kernel<true>) spends most of its time in per-tile set-up and between its barriers on these shapes
-// (0.52 of HBM).  A gather by gradient element with a fixed summation order: deterministic, no atomics.  The launcher checks on the
-// host (the same float arithmetic) that W and the row bound hold for every lane; other shapes keep the table-driven passes.
+// k0 .. k0 + 3 are the contiguous range first_tap(i) in [k0 - 1, k0 + 3]: at most 5 / scale + 1 of them.  A lane (resize_lane.hpp) finds
+// the start of its range once (first_reaching), builds the 4 x W matrix of column weights in registers (W = 8 | 12 | 16 upstream columns;
+// zero where an output does not touch a column), then gathers the upstream rows that touch its R gradient rows with their (wave-uniform)
+// weights.  No tables, no LDS, no barriers -- the strip kernel with transposed tables (resize_strip_kernel<true>) spends most of its time
+// in per-tile set-up and between its barriers on these shapes (0.52 of HBM).  A gather by gradient element with a fixed summation order:
+// deterministic, no atomics.  The launcher checks on the host (the same float arithmetic) that W holds for every lane; other shapes keep
+// the table-driven passes.
 template <int W, int R>
 __global__ __launch_bounds__(64) void resize_up2_backward_kernel(const float *__restrict__ gout, float *__restrict__ gin, int h_in, int w_in, int h_out,
                                                                  int w_out, int groups_x, int groups_y, uint32_t xcd_groups, AxisFilter fw, AxisFilter fh) {
-    const uint32_t wg = xcd_run_order(blockIdx.x, xcd_groups);      // as the forward
-    const uint32_t band = wg / (uint32_t)groups_x, gx = wg - band * (uint32_t)groups_x;
-    const int plane = (int)(band / (uint32_t)groups_y), r0 = (int)(band - (uint32_t)plane * (uint32_t)groups_y) * R;
-    const int k0 = ((int)gx * 64 + (int)threadIdx.x) * 4;
+    const LanePos p = lane_position<R>(groups_x, groups_y, xcd_groups);      // as the forward
+    const int k0 = p.k0, r0 = p.r0;
     if (k0 >= w_in) return;
-    // ---- columns: the first output whose window reaches column k0 - 1 or beyond
-    int i_lo = 0;
-    if (k0 > 1) {
-        i_lo = (int)(((float)k0 - 0.5f) / fw.scale - 0.5f) - 1;
-        i_lo = i_lo < 0 ? 0 : (i_lo > w_out - 1 ? w_out - 1 : i_lo);
-        while (i_lo > 0 && first_tap(fw, i_lo - 1) >= k0 - 1) --i_lo;
-        while (i_lo < w_out - 1 && first_tap(fw, i_lo) < k0 - 1) ++i_lo;
-    }
+    // ---- columns: from the first output whose window reaches column k0 - 1 or beyond
+    const int i_lo = first_reaching(fw, k0, w_out);
     const int i_base = i_lo < w_out - W ? i_lo : w_out - W;            // W upstream columns from here, inside the row (w_out >= W: the launcher)
     float wx[4][W];
 #pragma unroll
@@ -197,95 +189,61 @@ __global__ __launch_bounds__(64) void resize_up2_backward_kernel(const float *__
         for (int c = 0; c < 4; ++c) wx[c][j] = (first == k0 + c ? wa : 0.0f) + (first + 1 == k0 + c ? wb : 0.0f);
     }
     // ---- rows: the upstream rows whose windows reach gradient rows r0 .. r0 + R - 1 (wave-uniform)
-    int y = 0;
-    if (r0 > 1) {
-        y = (int)(((float)r0 - 0.5f) / fh.scale - 0.5f) - 1;
-        y = y < 0 ? 0 : (y > h_out - 1 ? h_out - 1 : y);
-        while (y > 0 && first_tap(fh, y - 1) >= r0 - 1) --y;
-        while (y < h_out - 1 && first_tap(fh, y) < r0 - 1) ++y;
-    }
     float acc[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] = 0.0f;
-    const float *gp = gout + (int64_t)plane * h_out * w_out + i_base;
-    for (; y < h_out; ++y) {
+    for (auto &row : acc) for (float &a : row) a = 0.0f;
+    const float *gp = gout + (int64_t)p.plane * h_out * w_out + i_base;
+    for (int y = first_reaching(fh, r0, h_out); y < h_out; ++y) {
         int yf; float wy0, wy1;
         two_taps(fh, y, yf, wy0, wy1);
         if (yf > r0 + R - 1) break;
         const int y1 = min(yf + 1, h_in - 1);               // the forward's second row (weight 0 when the window holds one tap)
-        const float *row = gp + (int64_t)y * w_out;
-        float g[W];
-#pragma unroll
-        for (int q = 0; q < W / 4; ++q) {
-            const rf4 v = *reinterpret_cast<const rf4 *>(row + 4 * q);       // cached: neighbouring lanes' and rows' windows overlap
-            g[4 * q] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
-        }
-        float t[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float a = wx[c][0] * g[0];
-#pragma unroll
-            for (int j = 1; j < W; ++j) a = fmaf(wx[c][j], g[j], a);
-            t[c] = a;
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const float cy = (yf == r0 + r ? wy0 : 0.0f) + (y1 == r0 + r ? wy1 : 0.0f);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[r][c] = fmaf(cy, t[c], acc[r][c]);
-        }
+        gather_row<W, R>(gp + (int64_t)y * w_out, wx, acc, [&](int r) { return (yf == r0 + r ? wy0 : 0.0f) + (y1 == r0 + r ? wy1 : 0.0f); });
     }
-    float *dp = gin + (int64_t)plane * h_in * w_in + k0;
-    const bool whole = k0 + 4 <= w_in;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (r0 + r >= h_in) break;
-        float *q = dp + (int64_t)(r0 + r) * w_in;
-        if (whole) {
-            typedef float sf4 __attribute__((ext_vector_type(4), aligned(4)));
-            const sf4 v = {acc[r][0], acc[r][1], acc[r][2], acc[r][3]};
-            __builtin_nontemporal_store(v, reinterpret_cast<sf4 *>(q));
-        } else {
-            for (int c = 0; c < w_in - k0; ++c) q[c] = acc[r][c];
-        }
-    }
+    store_rows<R>(gin, p, h_in, w_in, acc);
 }
 
-// Host side of the kernel above: the largest number of outputs whose windows start in [k0 - 1, k0 + 3] over all lanes' k0 (multiples
-// of 4), computed with the kernel's own first_tap -- the kernel's W must cover it.
-static int up2_backward_window(const AxisFilter &f, int n_out) {
-    int worst = 0, lo = 0, hi = 0;                       // [lo, hi): outputs with first_tap in [k0 - 1, k0 + 3], both ends monotone in k0
-    for (int k0 = 0; k0 < f.n_in; k0 += 4) {
-        while (lo < n_out && first_tap(f, lo) < k0 - 1) ++lo;
+// Host side of the register kernels: the most outputs any `step` consecutive gradient indices (from a multiple of `step` on) gather from --
+// the kernel's W (or a band's rows) must cover it.  Those of the indices from k0 on are [lo, hi): neither before(i, k0) nor past(i, k0),
+// both ends monotone in k0.  The predicates use the kernels' own first_tap / tap_window: host and device agree bit for bit.
+template <typename Before, typename Past>
+static int worst_span(const AxisFilter &f, int n_out, int step, Before before, Past past) {
+    int worst = 0, lo = 0, hi = 0;
+    for (int k0 = 0; k0 < f.n_in; k0 += step) {
+        while (lo < n_out && before(lo, k0)) ++lo;
         if (hi < lo) hi = lo;
-        while (hi < n_out && first_tap(f, hi) <= k0 + 3) ++hi;
+        while (hi < n_out && !past(hi, k0)) ++hi;
         worst = hi - lo > worst ? hi - lo : worst;
     }
     return worst;
 }
-// ---- gradient of a down-scale, registers only (round 4): the two table-driven passes in one kernel without the LDS strip --------
+// resize_up2_backward_kernel: the outputs whose two-tap windows start in [k0 - 1, k0 + 3], over all lanes' k0
+static int up2_backward_window(const AxisFilter &f, int n_out) {
+    return worst_span(f, n_out, 4, [&](int i, int k0) { return first_tap(f, i) < k0 - 1; }, [&](int i, int k0) { return first_tap(f, i) > k0 + 3; });
+}
+// resize_backward_gather_kernel: the outputs whose window [xmin, xmin + size) meets [k0, k0 + rows - 1]; rows = 4: a lane's columns, kBandRows: a wave's rows
+static int band_window(const AxisFilter &f, int n_out, int rows) {
+    auto before = [&](int i, int k0) { int xmin, n; float c; tap_window(f, i, xmin, n, c); return xmin + n <= k0; };
+    return worst_span(f, n_out, rows, before, [&](int i, int k0) { return first_tap(f, i) > k0 + rows - 1; });
+}
+
+// ---- gradient of a down-scale, registers only: the two table-driven passes in one kernel without the LDS strip -------------------
 // With the transposed tap tables in global memory (resize_backward_tables_kernel: per gradient index k the first upstream index
 // lo[k] that read it, their number cnt[k] and the normalised weights w[j][k]) the gradient is a gather with short, contiguous ranges
-// on both axes.  A lane owns FOUR consecutive gradient columns of R rows.  Its columns' upstream ranges overlap and are monotone, so
-// their union is W <= 16 consecutive upstream columns: the lane builds the 4 x W matrix of column weights once (4 W table reads,
-// coalesced over the lanes), then walks the union of its rows' upstream rows: W / 4 16-byte loads, 4 W fma for the width sums, and per
-// gradient row one wave-uniform weight (scalar loads) times the four sums.  resize_strip_kernel<true> does the same work through a
-// tile of LDS with three barrier-separated phases and reaches 0.52 of HBM on 4096^2 <- 2048^2; this form has no set-up to amortise.
+// on both axes.  A lane's four columns' upstream ranges overlap and are monotone, so their union is W <= 16 consecutive upstream columns:
+// the lane builds the 4 x W matrix of column weights once (4 W table reads, coalesced over the lanes), then gathers the union of its rows'
+// upstream rows, per gradient row one wave-uniform weight (scalar loads).  resize_strip_kernel<true> does the same work through a tile of
+// LDS with three barrier-separated phases and reaches 0.52 of HBM on 4096^2 <- 2048^2; this form has no set-up to amortise.
 // Gather by gradient element, fixed order: deterministic.  The launcher checks W on the host (same float arithmetic).
 template <int W, int R, bool BAND>
 __global__ __launch_bounds__(64) void resize_backward_gather_kernel(const float *__restrict__ gout, float *__restrict__ gin, int h_in, int w_in, int h_out,
                                                                     int w_out, int groups_x, int groups_y, uint32_t xcd_groups, StripTables tb) {
-    const uint32_t wg = xcd_run_order(blockIdx.x, xcd_groups);
-    const uint32_t band = wg / (uint32_t)groups_x, gx = wg - band * (uint32_t)groups_x;
-    const int plane = (int)(band / (uint32_t)groups_y), r0 = (int)(band - (uint32_t)plane * (uint32_t)groups_y) * R;
-    const int k0 = ((int)gx * 64 + (int)threadIdx.x) * 4;
+    const LanePos p = lane_position<R>(groups_x, groups_y, xcd_groups);
+    const int k0 = p.k0, r0 = p.r0;
     if (k0 >= w_in) return;
     // ---- columns
     float wx[4][W];
     int i_base;
-    if (BAND) {                                  // the group's record (resize_backward_tables_kernel): 1 + 4 W coalesced loads, none waits for another
+    if (BAND) {                                 // the group's record (resize_backward_tables_kernel): 1 + 4 W coalesced loads, none waits for another
         const int group = k0 >> 2, groups = (w_in + 3) >> 2;
         i_base = tb.col_base[group];
 #pragma unroll
@@ -314,45 +272,14 @@ __global__ __launch_bounds__(64) void resize_backward_gather_kernel(const float 
     }
     // ---- rows (wave-uniform: scalar loads)
     float acc[R][4];
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) acc[r][c] = 0.0f;
-    const float *gp = gout + (int64_t)plane * h_out * w_out + i_base;
-    auto load_row = [&](int y, float g[W]) {
-        const float *row = gp + (int64_t)y * w_out;
-#pragma unroll
-        for (int q = 0; q < W / 4; ++q) {
-            const rf4 v = *reinterpret_cast<const rf4 *>(row + 4 * q);       // cached: neighbouring lanes' and rows' windows overlap
-            g[4 * q] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
-        }
-    };
-    auto width_sums = [&](const float g[W], float t[4]) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            float a = wx[c][0] * g[0];
-#pragma unroll
-            for (int j = 1; j < W; ++j) a = fmaf(wx[c][j], g[j], a);
-            t[c] = a;
-        }
-    };
+    for (auto &row : acc) for (float &a : row) a = 0.0f;
+    const float *gp = gout + (int64_t)p.plane * h_out * w_out + i_base;
     if (BAND) {
         // the band's record (resize_backward_tables_kernel): first upstream row, their number, eight weights per upstream row
         static_assert(!BAND || R == kBandRows, "a band is what one wave owns");
         const float *rec = tb.band + (size_t)(r0 / R) * kBandWords;
         const int y_lo = reinterpret_cast<const int *>(rec)[0], y_n = reinterpret_cast<const int *>(rec)[1];
-        for (int j = 0; j < y_n; ++j) {
-            float g[W], t[4];
-            load_row(y_lo + j, g);
-            width_sums(g, t);
-            const float *cw = rec + 8 + kBandRows * j;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const float cy = cw[r];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[r][c] = fmaf(cy, t[c], acc[r][c]);
-            }
-        }
+        for (int j = 0; j < y_n; ++j) gather_row<W, R>(gp + (int64_t)(y_lo + j) * w_out, wx, acc, [&](int r) { return rec[8 + kBandRows * j + r]; });
     } else {
         int ylo[R], yn[R], y_lo = INT32_MAX, y_hi = 0;
 #pragma unroll
@@ -361,80 +288,52 @@ __global__ __launch_bounds__(64) void resize_backward_gather_kernel(const float 
             ylo[r] = tb.lo_y[k]; yn[r] = r0 + r < h_in ? min(tb.cnt_y[k], kBwdMaxTaps) : 0;
             if (yn[r] > 0) { y_lo = min(y_lo, ylo[r]); y_hi = max(y_hi, ylo[r] + yn[r]); }
         }
-        for (int y = y_lo; y < y_hi; ++y) {
-            float g[W], t[4];
-            load_row(y, g);
-            width_sums(g, t);
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
+        for (int y = y_lo; y < y_hi; ++y)
+            gather_row<W, R>(gp + (int64_t)y * w_out, wx, acc, [&](int r) {
                 const int d = y - ylo[r];
-                const float cy = d >= 0 && d < yn[r] ? tb.w_y[(size_t)d * tb.ny + min(r0 + r, h_in - 1)] : 0.0f;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) acc[r][c] = fmaf(cy, t[c], acc[r][c]);
-            }
-        }
+                return d >= 0 && d < yn[r] ? tb.w_y[(size_t)d * tb.ny + min(r0 + r, h_in - 1)] : 0.0f;
+            });
     }
-    float *dp = gin + (int64_t)plane * h_in * w_in + k0;
-    const bool whole = k0 + 4 <= w_in;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (r0 + r >= h_in) break;
-        float *q = dp + (int64_t)(r0 + r) * w_in;
-        if (whole) {
-            typedef float sf4 __attribute__((ext_vector_type(4), aligned(4)));
-            const sf4 v = {acc[r][0], acc[r][1], acc[r][2], acc[r][3]};
-            __builtin_nontemporal_store(v, reinterpret_cast<sf4 *>(q));
-        } else {
-            for (int c = 0; c < w_in - k0; ++c) q[c] = acc[r][c];
-        }
-    }
-}
-
-// Host side: the most upstream indices any `rows` consecutive gradient indices (starting at a multiple of `rows`) gather from, from the
-// forward's own windows (an output's window [xmin, xmin + size) is monotone in the output index at both ends): the outputs whose window
-// meets [k0, k0 + rows - 1].  rows = 4: the columns of a lane of the gather kernel; rows = kBandRows: the rows of one of its waves.
-static int band_window(const AxisFilter &f, int n_out, int rows) {
-    int worst = 0, lo = 0, hi = 0;
-    for (int k0 = 0; k0 < f.n_in; k0 += rows) {
-        int xmin, n; float c;
-        while (lo < n_out) { tap_window(f, lo, xmin, n, c); if (xmin + n > k0) break; ++lo; }
-        if (hi < lo) hi = lo;
-        while (hi < n_out) { tap_window(f, hi, xmin, n, c); if (xmin > k0 + rows - 1) break; ++hi; }
-        worst = hi - lo > worst ? hi - lo : worst;
-    }
-    return worst;
+    store_rows<R>(gin, p, h_in, w_in, acc);
 }
 
 // The TRANSPOSE of an up-scale by the whole factor S has the same shape: gradient element k gathers the 2 S upstream elements S k - S/2 ... S k + 3 S/2 - 1
 // (the outputs whose two-tap windows hold input k), with one weight vector for every interior k and clipped ones for the first and the last --
 // resize_down_kernel with other numbers in its three vectors.  Weights from the forward's own two-tap rule (two_taps, with its division on the host).
 static DownTaps up_transpose_taps(int S) {
-    DownTaps t;
     const AxisFilter f = make_filter(16, 16 * S, false);     // 16 gradient elements, 16 S upstream; up-scales: antialiasing changes nothing
-    const int which[3] = {5, 0, 15};
-    float *const into[3] = {t.wi, t.wl, t.wr};
-    for (int s = 0; s < 3; ++s) {
-        const int k = which[s];
-        for (int j = 0; j < 32; ++j) into[s][j] = 0.0f;
+    return make_down_taps([&](int k, float *w) {
         for (int j = 0; j < 2 * S; ++j) {
             const int i = S * k - S / 2 + j;
             if (i < 0 || i >= 16 * S) continue;
             int first, n; float center;
             tap_window(f, i, first, n, center);
             const float a = tap_weight(f, 0, first, center), b = n > 1 ? tap_weight(f, 1, first, center) : 0.0f, inv = 1.0f / (a + b);
-            into[s][j] = (first == k ? a * inv : 0.0f) + (first + 1 == k ? b * inv : 0.0f);
+            w[j] = (first == k ? a * inv : 0.0f) + (first + 1 == k ? b * inv : 0.0f);
         }
-    }
-    return t;
+    });
 }
 
 // ---- the forms, in the order pbr_resize_bilinear_backward tries them: each decides on the host and launches, or returns false -------------
-// One call: its arguments and its workspace, carved (floats) tmp [planes][h_in][w_out] | inv_y [h_out] | inv_x [w_out] | wy [kBwdMaxTaps][h_in] |
-// wx [kBwdMaxTaps][w_in] | then ints: lo_y, cnt_y [h_in] | lo_x, cnt_x [w_in]
+// One call: its arguments and its workspace (carve_workspace)
 struct BackwardCall {
     const float *g; float *gi; int64_t planes; int h_in, w_in, h_out, w_out; AxisFilter fw, fh; hipStream_t s;
     float *tmp, *inv_y, *inv_x, *wy, *wx; int *lo_y, *cnt_y, *lo_x, *cnt_x;
 };
+// The workspace's layout, in 4-byte words from `base`: tmp [planes][h_in][w_out] | inv_y [h_out] | inv_x [w_out] | wy [kBwdMaxTaps][h_in] |
+// wx [kBwdMaxTaps][w_in] | then ints: lo_y, cnt_y [h_in] | lo_x, cnt_x [w_in] | 4 words of slack.  Sets the call's pointers (`base` = NULL: none,
+// the size query) and returns the words of the whole.
+static size_t carve_workspace(BackwardCall &c, float *base) {
+    size_t at = 0;
+    auto take = [&](auto *&p, size_t words) { p = base ? reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + at) : nullptr; at += words; };
+    take(c.tmp, (size_t)c.planes * (size_t)c.h_in * (size_t)c.w_out); take(c.inv_y, (size_t)c.h_out); take(c.inv_x, (size_t)c.w_out);
+    take(c.wy, (size_t)kBwdMaxTaps * (size_t)c.h_in); take(c.wx, (size_t)kBwdMaxTaps * (size_t)c.w_in);
+    take(c.lo_y, (size_t)c.h_in); take(c.cnt_y, (size_t)c.h_in); take(c.lo_x, (size_t)c.w_in); take(c.cnt_x, (size_t)c.w_in);
+    return at + 4;
+}
+static StripTables tables_of(const BackwardCall &c, const float *band = nullptr, const int *col_base = nullptr, const float *col_w = nullptr) {      // (the gather kernel's records: optional)
+    return {c.lo_x, c.cnt_x, c.lo_y, c.cnt_y, c.wx, c.wy, c.w_in, c.h_in, c.h_out, band, col_base, col_w};
+}
 
 // Gradient of an up-scale by 2 | 4 | 8 | 16: the band walk of resize_down.hpp over the upstream gradient, with the transposed two-tap weights.  (Powers of two only:
 // the forward's scale 1 / S is then exact and its two weights are the same for every S-th output; with 1/3, 1/5 ... the forward's fp32 tap positions drift
@@ -445,17 +344,17 @@ static bool backward_band_walk(const BackwardCall &c) {
     return (up == 2 || up == 4 || up == 8 || up == 16) && launch_down(c.g, c.gi, c.planes, c.h_in, c.w_in, up, up_transpose_taps(up), c.s);
 }
 
-// Gradient of an up-scale (up to 3x across, 4x down the rows): the register-only transpose of the two-tap forward (round 4;
-// resize_bwd_probe.py (a probe of its round, removed with its knob: git 9ce0718:tools/)).  W from the exact window count of THIS shape; rows per lane 4.
+// Gradient of an up-scale (up to 3x across, 4x down the rows): the register-only transpose of the two-tap forward (resize_bwd_probe.py).
+// W from the exact window count of THIS shape; rows per lane 4.
 static bool backward_two_tap(const BackwardCall &c) {
     if (c.fw.scale > 1.0f || c.fh.scale > 1.0f || c.fw.scale < 0.34f || c.fh.scale < 0.25f || c.w_out < 16) return false;
     const int need = up2_backward_window(c.fw, c.w_out);
     constexpr int R = 4;
-    const int64_t groups_x = (c.w_in + 255) / 256, groups_y = (c.h_in + R - 1) / R, n_groups = groups_x * groups_y * c.planes;
-    if (need > 16 || n_groups > INT32_MAX) return false;
-    auto fn = need <= 8 ? resize_up2_backward_kernel<8, R> : (need <= 12 ? resize_up2_backward_kernel<12, R> : resize_up2_backward_kernel<16, R>);
-    hipLaunchKernelGGL(fn, dim3((unsigned)n_groups), dim3(64), 0, c.s, c.g, c.gi, c.h_in, c.w_in, c.h_out, c.w_out, (int)groups_x, (int)groups_y,
-                       xcd_run_groups(n_groups), c.fw, c.fh);
+    const LaneGrid grid = lane_grid(c.w_in, c.h_in, R, c.planes);
+    if (need > 16 || !grid.fits) return false;
+    with_window(need, [&](auto w) {
+        launch_lanes(resize_up2_backward_kernel<decltype(w)::value, R>, grid, c.s, c.g, c.gi, c.h_in, c.w_in, c.h_out, c.w_out, c.fw, c.fh);
+    });
     return true;
 }
 
@@ -467,26 +366,25 @@ static void launch_tables(const BackwardCall &c, float *band, int *col_base, flo
                        c.w_out, c.fw, groups_y, band, col_base, col_w, window);
 }
 
-// Register-only gather over the tables (round 4, resize_backward_gather_kernel): 4 gradient columns x 8 rows per lane; the rows'
-// weights from the per-band matrices the tables kernel leaves in the (otherwise unused) pass-to-pass area of the workspace when they fit there (else the kernel looks the rows up).
+// Register-only gather over the tables (resize_backward_gather_kernel): 4 gradient columns x 8 rows per lane; the rows' weights from the
+// per-band matrices the tables kernel leaves in the (otherwise unused) pass-to-pass area of the workspace when they fit there (else the kernel looks the rows up).
 static bool backward_gather(const BackwardCall &c) {
     if (!tables_fit(c.fw) || !tables_fit(c.fh) || c.w_out < 16) return false;
     const int need = band_window(c.fw, c.w_out, 4);
     constexpr int R = 8;                                          // gradient rows per lane
-    const int64_t groups_x = (c.w_in + 255) / 256, groups_y = (c.h_in + R - 1) / R, n_groups = groups_x * groups_y * c.planes;
-    if (need > 16 || n_groups > INT32_MAX) return false;
-    const int window = need <= 8 ? 8 : (need <= 12 ? 12 : 16);    // the gather kernel's W
-    const size_t band_words = (size_t)((c.h_in + kBandRows - 1) / kBandRows) * kBandWords, col_groups = (size_t)(c.w_in + 3) / 4;
-    const bool banded = R == kBandRows && band_window(c.fh, c.h_out, kBandRows) <= kBandMaxRows &&
-                        band_words + col_groups * (1 + 4 * (size_t)window) <= (size_t)c.planes * c.h_in * c.w_out;
-    float *band = banded ? c.tmp : nullptr, *col_w = banded ? c.tmp + band_words + col_groups : nullptr;
-    int *col_base = banded ? reinterpret_cast<int *>(c.tmp + band_words) : nullptr;
-    launch_tables(c, band, col_base, col_w, window);
-    const StripTables tb = {c.lo_x, c.cnt_x, c.lo_y, c.cnt_y, c.wx, c.wy, c.w_in, c.h_in, c.h_out, band, col_base, col_w};
-    auto fn = banded ? (window == 8 ? resize_backward_gather_kernel<8, R, true> : (window == 12 ? resize_backward_gather_kernel<12, R, true> : resize_backward_gather_kernel<16, R, true>))
-                     : (window == 8 ? resize_backward_gather_kernel<8, R, false> : (window == 12 ? resize_backward_gather_kernel<12, R, false> : resize_backward_gather_kernel<16, R, false>));
-    hipLaunchKernelGGL(fn, dim3((unsigned)n_groups), dim3(64), 0, c.s, c.g, c.gi, c.h_in, c.w_in, c.h_out, c.w_out, (int)groups_x, (int)groups_y,
-                       xcd_run_groups(n_groups), tb);
+    const LaneGrid grid = lane_grid(c.w_in, c.h_in, R, c.planes);
+    if (need > 16 || !grid.fits) return false;
+    with_window(need, [&](auto w) {
+        constexpr int W = decltype(w)::value;                     // the gather kernel's W
+        const size_t band_words = (size_t)((c.h_in + kBandRows - 1) / kBandRows) * kBandWords, col_groups = (size_t)(c.w_in + 3) / 4;
+        const bool banded = R == kBandRows && band_window(c.fh, c.h_out, kBandRows) <= kBandMaxRows &&
+                            band_words + col_groups * (1 + 4 * (size_t)W) <= (size_t)c.planes * c.h_in * c.w_out;
+        float *band = banded ? c.tmp : nullptr, *col_w = banded ? c.tmp + band_words + col_groups : nullptr;
+        int *col_base = banded ? reinterpret_cast<int *>(c.tmp + band_words) : nullptr;
+        launch_tables(c, band, col_base, col_w, W);
+        auto fn = banded ? resize_backward_gather_kernel<W, R, true> : resize_backward_gather_kernel<W, R, false>;
+        launch_lanes(fn, grid, c.s, c.g, c.gi, c.h_in, c.w_in, c.h_out, c.w_out, tables_of(c, band, col_base, col_w));
+    });
     return true;
 }
 
@@ -496,7 +394,7 @@ static bool backward_strip(const BackwardCall &c) {
     if (!tables_fit(c.fw) || !tables_fit(c.fh)) return false;
     const int kx = (int)((2.0f * c.fw.support + 2.0f) / c.fw.scale) + 2, ky = (int)((2.0f * c.fh.support + 2.0f) / c.fh.scale) + 2;     // <= kBwdMaxTaps
     const int cols_max = (int)((float)(kTileW - 1 + 2.0f * c.fw.support) / c.fw.scale) + 8;     // upstream columns a tile of 64 reads, + alignment
-    // Rows per tile: here more rows win up to ~48 KiB of LDS (resize_bwd_probe.py (a probe of its round, removed with its knob: git 9ce0718:tools/), us at 32 / 64 / 128 rows: 2048^2 -> 4096^2
+    // Rows per tile: here more rows win up to ~48 KiB of LDS (resize_bwd_probe.py, us at 32 / 64 / 128 rows: 2048^2 -> 4096^2
     // 123 / 79 / 67, 3000^2 -> 4096^2 138 / 98 / 84, 6144^2 -> 4096^2 184 / 150 / -, 4096^2 -> 2048^2 59 / 60 / 115): the strip's
     // halo rows are re-read per tile, and a gradient tile reads few bytes for what it writes.
     // A refusal falls here, before the tables are written, and leaves the call to the generic passes -- no form stands in between, because next to nothing
@@ -509,9 +407,8 @@ static bool backward_strip(const BackwardCall &c) {
     // 16-byte stores where the gradient is at least twice its upstream (2048^2 -> 4096^2: 66.7 against 69.3 us; the other way,
     // 4096^2 -> 2048^2, 70.6 against 59.4: a quarter of the lanes then walk the LDS strip)
     const bool quads = (int64_t)c.h_in * c.w_in >= 2 * (int64_t)c.h_out * c.w_out && c.w_in % 4 == 0 && is_aligned(c.gi, 16);
-    const StripTables tb = {c.lo_x, c.cnt_x, c.lo_y, c.cnt_y, c.wx, c.wy, c.w_in, c.h_in, c.h_out, nullptr, nullptr, nullptr};
     auto strip = quads ? resize_strip_kernel<true, true> : resize_strip_kernel<true, false>;
-    hipLaunchKernelGGL(strip, dim3(l.tiles), dim3(256), l.lds, c.s, c.g, c.gi, c.h_in, c.w_in, c.w_out, l.tg, c.fw, c.fh, tb);
+    hipLaunchKernelGGL(strip, dim3(l.tiles), dim3(256), l.lds, c.s, c.g, c.gi, c.h_in, c.w_in, c.w_out, l.tg, c.fw, c.fh, tables_of(c));
     return true;
 }
 
@@ -527,12 +424,11 @@ static void backward_generic(const BackwardCall &c) {
 
 extern "C" {
 
-// (the layout: at BackwardCall)
+// (the layout: carve_workspace)
 size_t pbr_resize_backward_workspace_bytes(int64_t planes, int32_t h_in, int32_t w_in, int32_t h_out, int32_t w_out) {
     if (planes < 1 || h_in < 1 || w_in < 1 || h_out < 1 || w_out < 1) return 0;
-    const size_t words = (size_t)planes * (size_t)h_in * (size_t)w_out + (size_t)h_out + (size_t)w_out +
-                         (size_t)pbr::kBwdMaxTaps * ((size_t)h_in + (size_t)w_in) + 2 * ((size_t)h_in + (size_t)w_in) + 4;
-    return words * sizeof(float);
+    pbr::BackwardCall c = {nullptr, nullptr, planes, h_in, w_in, h_out, w_out};
+    return pbr::carve_workspace(c, nullptr) * sizeof(float);
 }
 
 int pbr_resize_bilinear_backward(const void *grad_out, void *grad_in, int64_t planes, int32_t h_in, int32_t w_in, int32_t h_out,
@@ -541,13 +437,9 @@ int pbr_resize_bilinear_backward(const void *grad_out, void *grad_in, int64_t pl
     if (!grad_out || !grad_in || !workspace) return PBR_ERR_NULL_MAP;
     if (planes < 1 || h_in < 1 || w_in < 1 || h_out < 1 || w_out < 1) return PBR_ERR_SHAPE;
     if (planes * h_in > INT32_MAX) return PBR_ERR_SHAPE;
-    float *tmp = static_cast<float *>(workspace);
-    float *inv_y = tmp + (size_t)planes * h_in * w_out, *inv_x = inv_y + h_out;
-    float *wy = inv_x + w_out, *wx = wy + (size_t)kBwdMaxTaps * h_in;
-    int *lo_y = reinterpret_cast<int *>(wx + (size_t)kBwdMaxTaps * w_in), *cnt_y = lo_y + h_in, *lo_x = cnt_y + h_in, *cnt_x = lo_x + w_in;
-    const BackwardCall c = {static_cast<const float *>(grad_out), static_cast<float *>(grad_in), planes, h_in, w_in, h_out, w_out,
-                            make_filter(w_in, w_out, antialias != 0), make_filter(h_in, h_out, antialias != 0), static_cast<hipStream_t>(stream),
-                            tmp, inv_y, inv_x, wy, wx, lo_y, cnt_y, lo_x, cnt_x};
+    BackwardCall c = {static_cast<const float *>(grad_out), static_cast<float *>(grad_in), planes, h_in, w_in, h_out, w_out,
+                      make_filter(w_in, w_out, antialias != 0), make_filter(h_in, h_out, antialias != 0), static_cast<hipStream_t>(stream)};
+    carve_workspace(c, static_cast<float *>(workspace));
     const bool tuned = g_resize_up2 != 0;      // the register-only forms of an up-scale's gradient
     const bool done = (tuned && (backward_band_walk(c) || backward_two_tap(c))) || backward_gather(c) || backward_strip(c);
     if (!done) backward_generic(c);

@@ -6,7 +6,7 @@
 // K = 2 S inputs S i - floor(S/2) ... S i - floor(S/2) + 2 S - 1 with the triangle's weights (an odd S: the last one is 0); only the FIRST and the LAST
 // output of an axis have a clipped window (the taps that fall outside are dropped; the rest are normalised by their own sum).  So there is nothing to
 // look up: the three weight vectors (interior, first, last -- the same for both axes) are formed on the host with resize_taps.hpp's
-// tap_window / tap_weight arithmetic and travel as kernel arguments, i.e. in scalar registers.
+// tap_window / tap_weight arithmetic (make_down_taps below, from the caller's rule) and travel as kernel arguments, i.e. in scalar registers.
 //
 // A lane owns C consecutive output columns of a BAND of output rows and walks down the band.  It streams the input rows that feed
 // them: C S / 4 16-byte loads per row (its own C S input columns, contiguous), the height pass as fma into the accumulators of the one or two output rows a input row
@@ -32,6 +32,13 @@ __device__ __forceinline__ void static_for(F &&f) {
 }
 
 struct DownTaps { float wi[32], wl[32], wr[32]; };       // K = 2 S normalised weights of an interior output, of output 0, of the last output; zero where the window is clipped
+// The three vectors from one rule: an axis of 16 elements has all three kinds -- element 5 (whole window), 0 (clipped on the left) and 15 (clipped on
+// the right).  fill(i, w) writes element i's weights into w[0 .. 31], zero beforehand (down_taps in resize.hip, up_transpose_taps in resize_backward.hip).
+template <typename F> inline DownTaps make_down_taps(F &&fill) {
+    DownTaps t = {};
+    fill(5, t.wi); fill(0, t.wl); fill(15, t.wr);
+    return t;
+}
 // The launch (defined once, in resize.hip; the gradient of a whole power-of-two up-scale, resize_backward.hip, runs the same kernel with the transposed
 // two-tap weights): `small` = the side with 1 / S^2 of the elements.  False when the shape is not the kernel's; `dry` = decide, launch nothing.
 bool launch_down(const float *large, float *small, int64_t planes, int h_small, int w_small, int S, const DownTaps &taps, hipStream_t s, bool dry = false);

@@ -1,5 +1,5 @@
 // resize_taps.hpp -- the tap rule of the bilinear resize and the workgroup order of its one-wave kernels: what host and device, the forward
-// (resize.hip) and the gradient (resize_backward.hip) share.
+// (resize.hip) and the gradient (resize_backward.hip) share.  The lane frame of those kernels builds on this file: resize_lane.hpp.
 //
 // MaterialBase.resize (/root/reference/pypbr/materials/base.py:490-504) calls torchvision.transforms.functional.resize on every (C,H,W)
 // float map; for float tensors that is torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=...).

@@ -161,7 +161,11 @@ def test_resize_gradient_full_size_adjoint():
 
 @pytest.mark.parametrize("shape,size,antialias", [((37, 53), (20, 31), True), ((64, 256), (32, 128), True), ((200, 260), (67, 90), True),
                                                   ((40, 64), (100, 160), False), ((130, 131), (129, 64), True), ((256, 512), (128, 256), True),
-                                                  ((40, 64), (9, 12), True), ((200, 260), (20, 26), True), ((24, 40), (60, 13), True)])
+                                                  ((40, 64), (9, 12), True), ((200, 260), (20, 26), True), ((24, 40), (60, 13), True),
+                                                  # the gather kernel's other windows, whole quads and a partial last lane each, a ragged
+                                                  # last band: <8, 8, false>, <12, 8, true>, <16, 8, true>
+                                                  ((9, 20), (3, 16), True), ((9, 17), (3, 16), True), ((9, 8), (3, 16), True), ((9, 6), (3, 16), True),
+                                                  ((9, 12), (3, 29), True), ((9, 9), (3, 23), True)])
 def test_resize_gradient_forms_agree_with_float64_autograd(shape, size, antialias):
     """pbr_resize_bilinear_backward picks its form by shape (ABI 7: the A/B knobs of round 4 are gone, profiles/EXPERIMENTS.md): the
     register gather over the transposed tap tables (banded and looked-up rows), the two-tap transpose for up-scales, the LDS strip
@@ -196,7 +200,8 @@ def test_resize_gradient_forms_agree_with_float64_autograd(shape, size, antialia
 @pytest.mark.parametrize("shape,size", [((64, 96), (128, 192)), ((37, 53), (80, 97)), ((50, 70), (50, 70)), ((33, 130), (97, 131)), ((40, 44), (57, 128)),
                                         ((9, 16), (10, 16)), ((128, 256), (300, 700)), ((5, 4), (11, 16)), ((24, 250), (31, 251)),
                                         ((2, 8), (4, 16)), ((13, 260), (52, 1040)), ((16, 8), (128, 64)), ((301, 512), (602, 1024)), ((64, 96), (256, 384)),
-                                        ((37, 12), (111, 36)), ((20, 64), (100, 320)), ((9, 40), (54, 240)), ((6, 8), (42, 56)), ((5, 16), (80, 256))])
+                                        ((37, 12), (111, 36)), ((20, 64), (100, 320)), ((9, 40), (54, 240)), ((6, 8), (42, 56)), ((5, 16), (80, 256)),
+                                        ((9, 6), (9, 17)), ((9, 8), (9, 23))])      # 16 upstream columns per lane: a partial last lane, whole quads
 def test_gradient_of_an_upscale_in_registers(shape, size):
     """pbr_resize_bilinear_backward for up-scales (round 4: resize_up2_backward_kernel, the register-only transpose of the two-tap forward):
     against float64 autograd of F.interpolate, and within rounding of the table-driven strip kernel it replaces on these shapes; exact 2x,
