@@ -12,7 +12,8 @@
 //     (8 x global_load_dwordx4 in flight per lane, 8 KiB per wave) and one 16-byte store
 //     per output plane; a wave covers 1 KiB-contiguous segments of every plane;
 //   * loads/stores carry the non-temporal hint (each byte is touched once; 4K maps are
-//     64 MiB per plane, nothing fits L2/MALL);
+//     64 MiB per plane, nothing fits L2/MALL); the result of ONE material of such planes
+//     also leaves write-through (`nt sc1`: ct_launch.hpp, result_stores_through);
 //   * view / light / intensity / grid parameters live in the kernel-argument segment and
 //     are read with scalar loads: they sit in SGPRs, which IS the wave-wide broadcast on
 //     CDNA (a cross-lane shuffle would cost VALU/LDS slots for something the scalar unit

@@ -452,8 +452,8 @@ template <int WF, int VEC, typename TM>
 __device__ __forceinline__ void store_gradients(const KArgs &a, const BArgs &b, const LanePos &p, float (&ga)[3][VEC], float (&gn)[3][VEC],
                                                 float (&gr)[VEC], float (&gm)[VEC], float (&gs)[3][VEC]) {
     auto put = [&](void *plane, int channels, int c, const float *v) {
-        if (p.sb) Ld<TM, VEC>::template store<true>(plane_at<TM>(plane, ((int64_t)p.b0 * channels + c) * a.o_cs, (uint32_t)p.pix), 0, v);
-        else Ld<TM, VEC>::template store<true>(plane, ((int64_t)p.b * channels + c) * a.o_cs + p.pix, v);
+        if (p.sb) Ld<TM, VEC>::template store<St::hinted>(plane_at<TM>(plane, ((int64_t)p.b0 * channels + c) * a.o_cs, (uint32_t)p.pix), 0, v);
+        else Ld<TM, VEC>::template store<St::hinted>(plane, ((int64_t)p.b * channels + c) * a.o_cs + p.pix, v);
     };
     if (b.g_albedo) {
 #pragma unroll

@@ -79,7 +79,7 @@ void cook_torrance_blend_kernel(const KArgs a, const KBlend b) {
     else Ld<float, VEC>::template load<true>(b.mask, p.b * b.k_bs + p.src, w);
     const bool keep_signed = b.normal_signed[p.sb ? p.b0 : p.b] != 0;
     blend_texels<WF, VEC>(t, u, w, keep_signed);
-    shade_and_store<LIGHT, WF, float, VEC, MULTI, true, MULTI>(a, p, t);
+    shade_and_store<LIGHT, WF, float, VEC, MULTI, result_store(true), MULTI>(a, p, t);
 }
 
 // The fused blend over TILED maps (round 6): the repeat-inner walk of cook_torrance_repeat_kernel with the blend in front of the decode -- both

@@ -41,8 +41,8 @@ __device__ __forceinline__ void blend_backward_sink(const KArgs &a, const LanePo
             gw[j] = fmaf(g[j], av[j] - bv[j], gw[j]);
         }
         const int64_t at = ((int64_t)mat * channels + c) * a.o_cs + p.pix;
-        if (p1) Ld<float, VEC>::template store<true>(p1, at, o1);
-        if (p2) Ld<float, VEC>::template store<true>(p2, at, o2);
+        if (p1) Ld<float, VEC>::template store<St::hinted>(p1, at, o1);
+        if (p2) Ld<float, VEC>::template store<St::hinted>(p2, at, o2);
     };
 #pragma unroll
     for (int c = 0; c < 3; ++c) lerp_back(ga[c], t.al[c], u.al[c], g1.g_albedo, g2.g_albedo, 3, c);
@@ -86,10 +86,10 @@ __device__ __forceinline__ void blend_backward_sink(const KArgs &a, const LanePo
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int64_t at = ((int64_t)mat * 3 + c) * a.o_cs + p.pix;
-        if (g1.g_normal) Ld<float, VEC>::template store<true>(g1.g_normal, at, n1[c]);
-        if (g2.g_normal) Ld<float, VEC>::template store<true>(g2.g_normal, at, n2[c]);
+        if (g1.g_normal) Ld<float, VEC>::template store<St::hinted>(g1.g_normal, at, n1[c]);
+        if (g2.g_normal) Ld<float, VEC>::template store<St::hinted>(g2.g_normal, at, n2[c]);
     }
-    if (g2.g_mask) Ld<float, VEC>::template store<true>(g2.g_mask, (int64_t)mat * a.o_cs + p.pix, gw);
+    if (g2.g_mask) Ld<float, VEC>::template store<St::hinted>(g2.g_mask, (int64_t)mat * a.o_cs + p.pix, gw);
 }
 
 template <int LIGHT, int WF, int VEC, bool MULTI>

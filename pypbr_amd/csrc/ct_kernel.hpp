@@ -74,6 +74,7 @@ struct KArgs {
     int32_t fold_log2, fold_reps;   // tiled maps: rows visited in bands of (1 << fold_log2) source rows, all fold_reps vertical repeats of a band back to back (0 = off)
     FastDiv div_reps;        // band visit / fold_reps
     int32_t xpose;           // 8-pixel lanes, fp32 result: exchange the lanes' 16-byte pieces through LDS before storing
+    int32_t st_through;      // result stores of the `ruled` kernels (St, below) write through with the hint; else the hint alone.  Speed only (ct_launch.hpp: result_stores_through)
     int32_t sbase;           // every tile lies inside one material and every lane offset the launch forms is < 2^30 elements: scalar plane addresses (plane_at);
                              // repeat kernels: offsets into the first repeat of source rows [0, map_h) -- map_h * out_W and map_h * map_w, also for thin bands
     FastDiv div_h;           // row / H
@@ -130,102 +131,6 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef f32x4 f32x4_e __attribute__((aligned(4)));
 typedef f16x4 f16x4_e __attribute__((aligned(2)));
 
-template <typename T, int VEC> struct Ld;
-template <> struct Ld<float, 4> {
-    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[4]) {
-        const f32x4_e *q = reinterpret_cast<const f32x4_e *>(static_cast<const float *>(p) + i);
-        const f32x4 t = NT ? __builtin_nontemporal_load(q) : *q;
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    }
-    template <bool NT> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[4]) {
-        const f32x4 t = {v[0], v[1], v[2], v[3]};
-        f32x4_e *q = reinterpret_cast<f32x4_e *>(static_cast<float *>(p) + i);
-        if (NT) __builtin_nontemporal_store(t, q); else *q = t;
-    }
-};
-template <> struct Ld<float, 1> {
-    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[1]) {
-        v[0] = static_cast<const float *>(p)[i];
-    }
-    template <bool NT> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[1]) {
-        static_cast<float *>(p)[i] = v[0];
-    }
-};
-template <> struct Ld<__half, 4> {
-    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[4]) {
-        const f16x4_e *q = reinterpret_cast<const f16x4_e *>(static_cast<const _Float16 *>(p) + i);
-        const f16x4 t = NT ? __builtin_nontemporal_load(q) : *q;
-        v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)t.z; v[3] = (float)t.w;
-    }
-    template <bool NT> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[4]) {
-        const f16x4 t = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-        f16x4_e *q = reinterpret_cast<f16x4_e *>(static_cast<_Float16 *>(p) + i);
-        if (NT) __builtin_nontemporal_store(t, q); else *q = t;
-    }
-};
-template <> struct Ld<__half, 1> {
-    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[1]) {
-        v[0] = (float)static_cast<const _Float16 *>(p)[i];
-    }
-    template <bool NT> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[1]) {
-        static_cast<_Float16 *>(p)[i] = (_Float16)v[0];
-    }
-};
-
-// 2 pixels per lane (one packed pair): the register-light form of the backward kernel for fp16 maps
-typedef float f32x2v __attribute__((ext_vector_type(2), aligned(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2), aligned(2)));
-template <> struct Ld<float, 2> {
-    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[2]) {
-        const f32x2v *q = reinterpret_cast<const f32x2v *>(static_cast<const float *>(p) + i);
-        const f32x2v t = NT ? __builtin_nontemporal_load(q) : *q;
-        v[0] = t.x; v[1] = t.y;
-    }
-    template <bool NT> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[2]) {
-        const f32x2v t = {v[0], v[1]};
-        f32x2v *q = reinterpret_cast<f32x2v *>(static_cast<float *>(p) + i);
-        if (NT) __builtin_nontemporal_store(t, q); else *q = t;
-    }
-};
-template <> struct Ld<__half, 2> {
-    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[2]) {
-        const f16x2 *q = reinterpret_cast<const f16x2 *>(static_cast<const _Float16 *>(p) + i);
-        const f16x2 t = NT ? __builtin_nontemporal_load(q) : *q;
-        v[0] = (float)t.x; v[1] = (float)t.y;
-    }
-    template <bool NT> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[2]) {
-        const f16x2 t = {(_Float16)v[0], (_Float16)v[1]};
-        f16x2 *q = reinterpret_cast<f16x2 *>(static_cast<_Float16 *>(p) + i);
-        if (NT) __builtin_nontemporal_store(t, q); else *q = t;
-    }
-};
-
-// 8 pixels per lane: fp16 maps read as one 16-byte load per plane; fp32 results leave as two 16-byte stores.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-template <> struct Ld<__half, 8> {
-    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[8]) {
-        const f16x8 *q = reinterpret_cast<const f16x8 *>(static_cast<const _Float16 *>(p) + i);
-        const f16x8 t = NT ? __builtin_nontemporal_load(q) : *q;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)t[j];
-    }
-    template <bool NT> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[8]) {
-        f16x8 t;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = (_Float16)v[j];
-        f16x8 *q = reinterpret_cast<f16x8 *>(static_cast<_Float16 *>(p) + i);
-        if (NT) __builtin_nontemporal_store(t, q); else *q = t;
-    }
-};
-template <> struct Ld<float, 8> {
-    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[8]) {
-        Ld<float, 4>::load<NT>(p, i, v); Ld<float, 4>::load<NT>(p, i + 4, v + 4);
-    }
-    template <bool NT> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[8]) {
-        Ld<float, 4>::store<NT>(p, i, v); Ld<float, 4>::store<NT>(p, i + 4, v + 4);
-    }
-};
-
 // Scalar plane addressing (KArgs::sbase).  The general form of an access is map + b * batch_stride + c * channel_stride +
 // lane offset with a per-lane material index b: a 64-bit multiply-add and a 64-bit add per plane in vector registers
 // (19 planes in the backward kernel: 9 % of its VALU instructions and two address registers per plane).  When the
@@ -240,6 +145,217 @@ __device__ __forceinline__ void *plane_at(const void *plane, int64_t uniform_ele
     asm("" : "+s"(base));
     return (void *)(reinterpret_cast<global_ptr>(base) + lane_elems * (uint32_t)sizeof(T));
 }
+
+// Result stores: ONE policy point for everything the forward render family writes (Ld<>::store / store_at, the 8-pixel piece exchange,
+// the repeat kernel's store_at, the batch kernel's closing stores).  The load side keeps its `bool NT`.
+//   plain           the line stays in the XCD's L2 and leaves on eviction (or at the flush behind the launch)
+//   hinted          the same with the streaming hint (`nt`): the rule for vector lanes
+//   through         device-scope write-through (`sc1`): the bytes leave in program order, the line is not kept
+//   through_hinted  both (`sc1 nt`)
+//   ruled           through_hinted or hinted, as the launcher says per launch (KArgs::st_through): one wave-uniform branch around the stores
+// Measured (profiles/EXPERIMENTS.md, "Forward kernel: result-store policy"): write-through + hint is 0.3-3 % ahead of the hint alone for
+// one 4096^2 material of the one-light fp32 kernel in the linear workgroup order, level or behind under XCD runs and for batches, level for
+// the 8-pixel and repeat-inner kernels; plain stores lose 4-23 %, write-through without the hint loses where XCD runs are the order.
+// So every family has exactly one policy (result_store below): plain for the one-pixel kernels, `ruled` for the one-light fp32 4-pixel
+// kernel, the hint alone for every other vector-lane kernel.  PBR_RESULT_STORE (0..3: one flavour for ALL vector-lane kernels) exists for
+// tools/build_alt.sh, as PBR_WAVES_PER_EU does.
+enum class St : int { plain = 0, hinted = 1, through = 2, through_hinted = 3, ruled = 4 };
+// `vector_lanes`: the kernels' NT parameter (on for 4- and 8-pixel lanes, off for the one-pixel kernels, which keep plain stores).
+constexpr St result_store(bool vector_lanes, bool one_light_f32 = false) {
+#ifdef PBR_RESULT_STORE
+    return vector_lanes ? (St)PBR_RESULT_STORE : St::plain;
+#else
+    return !vector_lanes ? St::plain : (one_light_f32 ? St::ruled : St::hinted);
+#endif
+}
+constexpr bool is_through(St p) { return p == St::through || p == St::through_hinted; }
+template <St P> using StC = std::integral_constant<St, P>;
+// fn(StC<Q>{}) with the policy Q to store under: P itself, or what the launch's flag picks for a `ruled` kernel
+template <St P, class Fn>
+__device__ __forceinline__ void with_store_policy(bool through, Fn &&fn) {
+    if constexpr (P == St::ruled) {
+        if (through) fn(StC<St::through_hinted>{}); else fn(StC<St::hinted>{});
+    } else {
+        fn(StC<P>{});
+    }
+}
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// One 16- or 8-byte vector to a per-lane 64-bit address.  The write-through flavours have no builtin in this form (the
+// buffer builtins want a wave-uniform descriptor): inline assembly, ONE global_store per vector.  The compiler neither counts
+// nor pads it, so the string carries its own wait states: `s_nop 0` in front (a stored register may come straight from v_exp:
+// linear_to_srgb_unit -- one state between a transcendental and its reader), `s_nop 1` behind (the data registers of a
+// store wider than 8 bytes are read after issue; nothing may overwrite them in the next two states).  "memory": the
+// compiler keeps its own loads and stores on their side of it; nothing in these kernels reads a result back, and the wave's
+// end waits for its outstanding stores.
+template <St P, class V>
+__device__ __forceinline__ void st_through(void *q, V t) {
+    static_assert(is_through(P) && (sizeof(V) == 16 || sizeof(V) == 8 || sizeof(V) == 4), "write-through: 16-, 8- and 4-byte vectors");
+    const global_ptr g = (global_ptr)q;
+    if constexpr (sizeof(V) == 16) {
+        const u32x4 w = __builtin_bit_cast(u32x4, t);
+        if constexpr (P == St::through) asm volatile("s_nop 0\n\tglobal_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(g), "v"(w) : "memory");
+        else asm volatile("s_nop 0\n\tglobal_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" : : "v"(g), "v"(w) : "memory");
+    } else if constexpr (sizeof(V) == 8) {
+        const u32x2 w = __builtin_bit_cast(u32x2, t);
+        if constexpr (P == St::through) asm volatile("s_nop 0\n\tglobal_store_dwordx2 %0, %1, off sc1" : : "v"(g), "v"(w) : "memory");
+        else asm volatile("s_nop 0\n\tglobal_store_dwordx2 %0, %1, off sc1 nt" : : "v"(g), "v"(w) : "memory");
+    } else {
+        const uint32_t w = __builtin_bit_cast(uint32_t, t);
+        if constexpr (P == St::through) asm volatile("s_nop 0\n\tglobal_store_dword %0, %1, off sc1" : : "v"(g), "v"(w) : "memory");
+        else asm volatile("s_nop 0\n\tglobal_store_dword %0, %1, off sc1 nt" : : "v"(g), "v"(w) : "memory");
+    }
+}
+// (one overload per vector type: the ELEMENT alignment lives in the parameter's typedef, which template deduction would drop)
+#define PBR_ST_VEC(Q, V)                                                            \
+    template <St P> __device__ __forceinline__ void st_vec(Q *q, V t) {             \
+        if constexpr (P == St::plain) *q = t;                                       \
+        else if constexpr (P == St::hinted) __builtin_nontemporal_store(t, q);      \
+        else st_through<P>(q, t);                                                   \
+    }
+typedef float f32x2v __attribute__((ext_vector_type(2), aligned(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2), aligned(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+PBR_ST_VEC(f32x4_e, f32x4)
+PBR_ST_VEC(f16x4_e, f16x4)
+PBR_ST_VEC(f32x2v, f32x2v)
+PBR_ST_VEC(f16x2, f16x2)
+PBR_ST_VEC(f16x8, f16x8)
+#undef PBR_ST_VEC
+
+// The same vector through a scalar plane address (plane_at: SGPR base + 32-bit lane offset).  Here the write-through flavours DO have
+// builtins -- raw buffer stores carry the cache-policy immediate (aux: 2 = nt, 16 = sc1) -- which the compiler counts, pads and schedules
+// like any other store: a raw descriptor (stride 0) over the 4 GiB behind the plane's uniform address, the lane's byte offset as voffset.
+// Every lane offset of an sbase launch lies below 2^30 elements (fill_args), so offset + vector stays inside the descriptor's range.
+template <St P, typename T, class V>
+__device__ __forceinline__ void st_plane(void *plane, int64_t uniform_elems, uint32_t lane_elems, V t) {
+    if constexpr (!is_through(P)) {
+        st_vec<P>(static_cast<V *>(plane_at<T>(plane, uniform_elems, lane_elems)), t);
+    } else {
+        uint64_t base = reinterpret_cast<uint64_t>(plane) + (uint64_t)uniform_elems * sizeof(T);
+        asm("" : "+s"(base));
+        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(base), 0, 0xFFFFFFFFu, 0x00020000);
+        constexpr int aux = P == St::through ? 16 : 16 | 2;
+        const uint32_t off = lane_elems * (uint32_t)sizeof(T);
+        static_assert(sizeof(V) == 16 || sizeof(V) == 8 || sizeof(V) == 4, "write-through: 16-, 8- and 4-byte vectors");
+        if constexpr (sizeof(V) == 16) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, t), rsrc, off, 0, aux);
+        else if constexpr (sizeof(V) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, t), rsrc, off, 0, aux);
+        else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, t), rsrc, off, 0, aux);
+    }
+}
+
+template <typename T, int VEC> struct Ld;
+template <> struct Ld<float, 4> {
+    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[4]) {
+        const f32x4_e *q = reinterpret_cast<const f32x4_e *>(static_cast<const float *>(p) + i);
+        const f32x4 t = NT ? __builtin_nontemporal_load(q) : *q;
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    }
+    template <St P> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[4]) {
+        st_vec<P>(reinterpret_cast<f32x4_e *>(static_cast<float *>(p) + i), f32x4{v[0], v[1], v[2], v[3]});
+    }
+    template <St P> static __device__ __forceinline__ void store_at(void *plane, int64_t uniform_elems, uint32_t lane_elems, const float v[4]) {
+        st_plane<P, float>(plane, uniform_elems, lane_elems, f32x4{v[0], v[1], v[2], v[3]});
+    }
+};
+template <> struct Ld<float, 1> {
+    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[1]) {
+        v[0] = static_cast<const float *>(p)[i];
+    }
+    template <St P> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[1]) {
+        static_cast<float *>(p)[i] = v[0];
+    }
+    template <St P> static __device__ __forceinline__ void store_at(void *plane, int64_t uniform_elems, uint32_t lane_elems, const float v[1]) {
+        store<P>(plane_at<float>(plane, uniform_elems, lane_elems), 0, v);
+    }
+};
+template <> struct Ld<__half, 4> {
+    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[4]) {
+        const f16x4_e *q = reinterpret_cast<const f16x4_e *>(static_cast<const _Float16 *>(p) + i);
+        const f16x4 t = NT ? __builtin_nontemporal_load(q) : *q;
+        v[0] = (float)t.x; v[1] = (float)t.y; v[2] = (float)t.z; v[3] = (float)t.w;
+    }
+    template <St P> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[4]) {
+        st_vec<P>(reinterpret_cast<f16x4_e *>(static_cast<_Float16 *>(p) + i), f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]});
+    }
+    template <St P> static __device__ __forceinline__ void store_at(void *plane, int64_t uniform_elems, uint32_t lane_elems, const float v[4]) {
+        st_plane<P, _Float16>(plane, uniform_elems, lane_elems, f16x4{(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]});
+    }
+};
+template <> struct Ld<__half, 1> {
+    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[1]) {
+        v[0] = (float)static_cast<const _Float16 *>(p)[i];
+    }
+    template <St P> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[1]) {
+        static_cast<_Float16 *>(p)[i] = (_Float16)v[0];
+    }
+    template <St P> static __device__ __forceinline__ void store_at(void *plane, int64_t uniform_elems, uint32_t lane_elems, const float v[1]) {
+        store<P>(plane_at<_Float16>(plane, uniform_elems, lane_elems), 0, v);
+    }
+};
+
+// 2 pixels per lane (one packed pair): the register-light form of the backward kernel for fp16 maps
+template <> struct Ld<float, 2> {
+    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[2]) {
+        const f32x2v *q = reinterpret_cast<const f32x2v *>(static_cast<const float *>(p) + i);
+        const f32x2v t = NT ? __builtin_nontemporal_load(q) : *q;
+        v[0] = t.x; v[1] = t.y;
+    }
+    template <St P> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[2]) {
+        st_vec<P>(reinterpret_cast<f32x2v *>(static_cast<float *>(p) + i), f32x2v{v[0], v[1]});
+    }
+    template <St P> static __device__ __forceinline__ void store_at(void *plane, int64_t uniform_elems, uint32_t lane_elems, const float v[2]) {
+        st_plane<P, float>(plane, uniform_elems, lane_elems, f32x2v{v[0], v[1]});
+    }
+};
+template <> struct Ld<__half, 2> {
+    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[2]) {
+        const f16x2 *q = reinterpret_cast<const f16x2 *>(static_cast<const _Float16 *>(p) + i);
+        const f16x2 t = NT ? __builtin_nontemporal_load(q) : *q;
+        v[0] = (float)t.x; v[1] = (float)t.y;
+    }
+    template <St P> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[2]) {
+        st_vec<P>(reinterpret_cast<f16x2 *>(static_cast<_Float16 *>(p) + i), f16x2{(_Float16)v[0], (_Float16)v[1]});
+    }
+    template <St P> static __device__ __forceinline__ void store_at(void *plane, int64_t uniform_elems, uint32_t lane_elems, const float v[2]) {
+        st_plane<P, _Float16>(plane, uniform_elems, lane_elems, f16x2{(_Float16)v[0], (_Float16)v[1]});
+    }
+};
+
+// 8 pixels per lane: fp16 maps read as one 16-byte load per plane; fp32 results leave as two 16-byte stores.
+template <> struct Ld<__half, 8> {
+    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[8]) {
+        const f16x8 *q = reinterpret_cast<const f16x8 *>(static_cast<const _Float16 *>(p) + i);
+        const f16x8 t = NT ? __builtin_nontemporal_load(q) : *q;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (float)t[j];
+    }
+    static __device__ __forceinline__ f16x8 pack(const float v[8]) {
+        f16x8 t;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[j] = (_Float16)v[j];
+        return t;
+    }
+    template <St P> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[8]) {
+        st_vec<P>(reinterpret_cast<f16x8 *>(static_cast<_Float16 *>(p) + i), pack(v));
+    }
+    template <St P> static __device__ __forceinline__ void store_at(void *plane, int64_t uniform_elems, uint32_t lane_elems, const float v[8]) {
+        st_plane<P, _Float16>(plane, uniform_elems, lane_elems, pack(v));
+    }
+};
+template <> struct Ld<float, 8> {
+    template <bool NT> static __device__ __forceinline__ void load(const void *p, int64_t i, float v[8]) {
+        Ld<float, 4>::load<NT>(p, i, v); Ld<float, 4>::load<NT>(p, i + 4, v + 4);
+    }
+    template <St P> static __device__ __forceinline__ void store(void *p, int64_t i, const float v[8]) {
+        Ld<float, 4>::store<P>(p, i, v); Ld<float, 4>::store<P>(p, i + 4, v + 4);
+    }
+    template <St P> static __device__ __forceinline__ void store_at(void *plane, int64_t uniform_elems, uint32_t lane_elems, const float v[8]) {
+        Ld<float, 4>::store_at<P>(plane, uniform_elems, lane_elems, v); Ld<float, 4>::store_at<P>(plane, uniform_elems, lane_elems + 4, v + 4);
+    }
+};
 
 // torch.linspace two-ended evaluation (what ATen's device kernel computes), branch-free:
 // i < n/2 ? a + step*i : b - step*(n-1-i).
@@ -540,7 +656,7 @@ __device__ __forceinline__ void decode_texels(const KArgs &a, Texels<VEC> &t) {
 // Run-time flags (sRGB decode/encode, normal present) are wave-uniform and each guards ONE hoisted
 // block over all VEC pixels, so the shading code stays one basic block and the scheduler can
 // interleave the pixel groups' transcendental latencies.
-template <int LIGHT, int WF, typename TO, int VEC, bool MULTI, bool NT, bool PACKED>
+template <int LIGHT, int WF, typename TO, int VEC, bool MULTI, St P, bool PACKED>
 __device__ __forceinline__ void shade_and_store(const KArgs &a, const LanePos &p, Texels<VEC> &t) {
     using R = typename RealOf<VEC, PACKED>::type;
     constexpr int NG = RealOf<VEC, PACKED>::N;                             // pixel groups per lane
@@ -639,22 +755,31 @@ __device__ __forceinline__ void shade_and_store(const KArgs &a, const LanePos &p
                 for (int s2 = 0; s2 < 2; ++s2) {
                     const int q = s2 * nvt + col;                             // piece index inside the row
                     const f32x4 v = xp[wave][c][(q & 1) * 72 + row0 + (q >> 1)];
-                    f32x4 *dst = p.sb ? static_cast<f32x4 *>(plane_at<float>(a.out, p.b0 * a.o_bs + c * a.o_cs, (uint32_t)p.pix - 4 * col + 4 * s2 * nvt))
-                                      : reinterpret_cast<f32x4 *>(static_cast<float *>(a.out) + base + c * a.o_cs + 4 * s2 * nvt);
-                    if (NT) __builtin_nontemporal_store(v, dst); else *dst = v;
+                    if constexpr (!is_through(P)) {                           // one store behind a selected address (16-byte aligned: pick_vec)
+                        f32x4 *dst = p.sb ? static_cast<f32x4 *>(plane_at<float>(a.out, p.b0 * a.o_bs + c * a.o_cs, (uint32_t)p.pix - 4 * col + 4 * s2 * nvt))
+                                          : reinterpret_cast<f32x4 *>(static_cast<float *>(a.out) + base + c * a.o_cs + 4 * s2 * nvt);
+                        if constexpr (P == St::hinted) __builtin_nontemporal_store(v, dst); else *dst = v;
+                    } else if (p.sb) {
+                        st_plane<P, float>(a.out, p.b0 * a.o_bs + c * a.o_cs, (uint32_t)p.pix - 4 * col + 4 * s2 * nvt, v);
+                    } else {
+                        st_vec<P>(reinterpret_cast<f32x4_e *>(static_cast<float *>(a.out) + base + c * a.o_cs + 4 * s2 * nvt), v);
+                    }
                 }
             }
             return;
         }
     }
+    with_store_policy<P>(a.st_through != 0, [&](auto policy) {
+        constexpr St Q = decltype(policy)::value;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float o[VEC];
+        for (int c = 0; c < 3; ++c) {
+            float o[VEC];
 #pragma unroll
-        for (int g = 0; g < NG; ++g) scatter(o, g, res[c][g]);
-        if (p.sb) Ld<TO, VEC>::template store<NT>(plane_at<TO>(a.out, p.b0 * a.o_bs + c * a.o_cs, (uint32_t)p.pix), 0, o);
-        else Ld<TO, VEC>::template store<NT>(a.out, p.b * a.o_bs + c * a.o_cs + p.pix, o);
-    }
+            for (int g = 0; g < NG; ++g) scatter(o, g, res[c][g]);
+            if (p.sb) Ld<TO, VEC>::template store_at<Q>(a.out, p.b0 * a.o_bs + c * a.o_cs, (uint32_t)p.pix, o);
+            else Ld<TO, VEC>::template store<Q>(a.out, p.b * a.o_bs + c * a.o_cs + p.pix, o);
+        }
+    });
 }
 
 // ------------------------------------------------------------------ kernel
@@ -684,7 +809,8 @@ void cook_torrance_kernel(const KArgs a) {
     if (!p.valid) return;
     Texels<VEC> t;
     load_texels<WF, TI, VEC, NT>(a, a.has_normal != 0, p, t);
-    shade_and_store<LIGHT, WF, TO, VEC, MULTI, NT, (MULTI || sizeof(TI) == 2 || PACK1)>(a, p, t);
+    constexpr bool one_light_f32 = VEC == 4 && !MULTI && !PACK1 && sizeof(TI) == 4 && sizeof(TO) == 4;
+    shade_and_store<LIGHT, WF, TO, VEC, MULTI, result_store(NT, one_light_f32), (MULTI || sizeof(TI) == 2 || PACK1)>(a, p, t);
 }
 
 // ------------------------------------------------------------------ batch-inner kernel (several lights)
@@ -771,8 +897,8 @@ void cook_torrance_batch_kernel(const KArgs a) {
                 if (a.out_srgb) v = linear_to_srgb_unit(v);                     // :179-180
                 scatter(o, g, v);
             }
-            if (p.sb) Ld<TO, VEC>::template store<NT>(plane_at<TO>(a.out, (p.b0 * NB + j) * a.o_bs + c * a.o_cs, (uint32_t)p.pix), 0, o);
-            else Ld<TO, VEC>::template store<NT>(a.out, pj[j].b * a.o_bs + c * a.o_cs + p.pix, o);
+            if (p.sb) Ld<TO, VEC>::template store_at<result_store(NT)>(a.out, (p.b0 * NB + j) * a.o_bs + c * a.o_cs, (uint32_t)p.pix, o);
+            else Ld<TO, VEC>::template store<result_store(NT)>(a.out, pj[j].b * a.o_bs + c * a.o_cs + p.pix, o);
         }
     }
 }
@@ -839,8 +965,8 @@ __device__ __forceinline__ void repeat_forward_body(const KArgs &a, Prepare &&pr
             float o[VEC];
 #pragma unroll
             for (int g = 0; g < NG; ++g) scatter(o, g, res[c][g]);
-            if (p.sb) Ld<TO, VEC>::template store<NTS>(plane_at<TO>(a.out, p.b0 * a.o_bs + c * a.o_cs + rep, lane_out), 0, o);
-            else Ld<TO, VEC>::template store<NTS>(a.out, p.b * a.o_bs + c * a.o_cs + rep + (int64_t)p.y * a.out_W + p.x, o);
+            if (p.sb) Ld<TO, VEC>::template store_at<result_store(NTS)>(a.out, p.b0 * a.o_bs + c * a.o_cs + rep, lane_out, o);
+            else Ld<TO, VEC>::template store<result_store(NTS)>(a.out, p.b * a.o_bs + c * a.o_cs + rep + (int64_t)p.y * a.out_W + p.x, o);
         }
     };
     auto shade = [&](const R (&xs)[NG], float ys, R (&res)[3][NG]) {

@@ -154,8 +154,7 @@ inline int pick_vec(const pbr_render_desc *d) {
 // 5.4-5.8 TB/s when they do not: rows that are not a whole number of tiles (1000^2, 3000^2: -12..14 %) and
 // 8 / 16 MiB plane strides (2048^2, 4096x1024: -2..12 %).  AUTO encodes exactly that; pbr_cook_torrance_autotune
 // measures instead of guessing.
-inline int schedule_xcd_log2(const pbr_render_desc *d, int vec) {
-    if (d->schedule >= PBR_SCHEDULE_LINEAR) return d->schedule - PBR_SCHEDULE_LINEAR;
+inline int auto_xcd_log2(const pbr_render_desc *d, int vec) {
     const int64_t esz = d->map_dtype == PBR_F32 ? 4 : 2;
     const int64_t row_bytes = (int64_t)d->width * esz, tile_bytes = 64 * (int64_t)vec * esz;
     const int64_t plane_bytes = d->albedo.channel_stride * esz;
@@ -169,6 +168,22 @@ inline int schedule_xcd_log2(const pbr_render_desc *d, int vec) {
     // and the linear one is 2 % ahead for a batch (4 x 4096^2: 451.9 vs 462.1 us), so the rule stops below that.
     if (plane_bytes % (8ll << 20) == 0 && plane_bytes < (64ll << 20)) return 6;
     return 0;
+}
+inline int schedule_xcd_log2(const pbr_render_desc *d, int vec) {
+    return d->schedule >= PBR_SCHEDULE_LINEAR ? d->schedule - PBR_SCHEDULE_LINEAR : auto_xcd_log2(d, vec);
+}
+
+// Result stores of the one-light fp32 4-pixel kernel (ct_kernel.hpp: St::ruled): write-through + hint for ONE material of 64 MiB planes or
+// more (4096^2: the headline launch) under the linear order, the hint alone otherwise.  Measured in-process against the parent build
+// (tools/store_policy_sweep.py, 11 rounds x median of 30; profiles/EXPERIMENTS.md, "Forward kernel: result-store policy"): 1 x 4096^2 in
+// the linear order -0.3 .. -3.0 % in seven runs on several boxes (never behind; beyond the parent's spread in five), converted workflow
+// -5 %; forced onto XCD runs level.  Batches do NOT take it: 64 x 1024^2 -1.0 / -1.25 / +0.8 / -1.2 / +0.6 % (the sign turns from process
+// to process on one box), 16 x 1024^2 +0.5 / +1.5 %, 8 x 2048^2 (XCD runs) +0.2 .. +0.8 % whatever the light and workflow, 4 x 4096^2
+// level.  Other result types, several lights, tiled maps, smaller single materials: not measured, the hint alone.
+inline bool result_stores_through(const pbr_render_desc *d, int vec, int xcd_log2) {
+    const int64_t plane_bytes = d->albedo.channel_stride * 4;
+    return vec == 4 && d->batch == 1 && d->n_lights == 1 && d->map_dtype == PBR_F32 && d->out_dtype == PBR_F32 && !is_tiled(d) &&
+           plane_bytes >= (64ll << 20) && xcd_log2 == 0 && auto_xcd_log2(d, vec) == 0;
 }
 
 inline void fill_args(const pbr_render_desc *d, int vec, KArgs &k, int block_log2 = 0) {
@@ -196,6 +211,7 @@ inline void fill_args(const pbr_render_desc *d, int vec, KArgs &k, int block_log
     const int64_t tiles = (int64_t)k.tiles_x * ((k.rows + by - 1) / by);
     k.n_tiles = tiles > INT32_MAX ? -1 : (int32_t)tiles;      // -1: more tiles than a 1-D grid holds, rejected by the callers
     k.xcd_log2 = schedule_xcd_log2(d, vec);
+    k.st_through = result_stores_through(d, vec, k.xcd_log2);
     k.xcd_tiles = k.n_tiles < 0 ? 0 : (k.n_tiles >> (k.xcd_log2 + 3)) << (k.xcd_log2 + 3);
     // 8-pixel lanes with an fp32 result swap 16-byte pieces between the lanes of a row before storing (ct_kernel.hpp)
     k.xpose = vec == 8 && d->out_dtype == PBR_F32;

@@ -69,7 +69,7 @@ void cook_torrance_stack_kernel(const KArgs a) {
             float o[VEC];
 #pragma unroll
             for (int g = 0; g < NG; ++g) scatter(o, g, res[c][g]);
-            Ld<float, VEC>::template store<VEC != 1>(first, ((int64_t)l * 3 + c) * a.o_cs, o);
+            Ld<float, VEC>::template store<VEC != 1 ? St::hinted : St::plain>(first, ((int64_t)l * 3 + c) * a.o_cs, o);
         }
     }
 }

@@ -8,8 +8,9 @@ D=$R/tools/bin/$NAME
 mkdir -p "$D"
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=on -fno-slp-vectorize -fno-gpu-rdc -Wno-unused-function $*"
 pids=()
-for f in cook_torrance ct_batch ct_tiled ct_backward ct_blend ct_loss map_ops resize blend; do
-    /opt/rocm/bin/hipcc $FLAGS -c "$R/pypbr_amd/csrc/$f.hip" -o "$D/$f.o" &
+for src in "$R"/pypbr_amd/csrc/*.hip; do      # every source of the library (csrc/Makefile: SRCS), so that the alternative loads on its own
+    f=$(basename "$src" .hip)
+    /opt/rocm/bin/hipcc $FLAGS -c "$src" -o "$D/$f.o" &
     pids+=($!)
 done
 for p in "${pids[@]}"; do wait "$p"; done
