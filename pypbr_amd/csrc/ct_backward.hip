@@ -1,10 +1,85 @@
 // ct_backward.hip -- launchers of the backward kernels (C ABI: pbr_cook_torrance_backward, pbr_cook_torrance_backward_params);
-// device code in ct_backward.hpp.
-#define PBR_PARAM_GRAD_KERNELS
-#include "ct_backward.hpp"
+// device code in ct_backward.hpp (the one-tile kernel) and ct_backward_stream.hpp (the streamed one); the two reduction kernels behind the
+// light / view gradients are not templates and live here.
+#include "ct_backward_stream.hpp"
 #include "ct_launch.hpp"
 
 namespace pbr {
+
+// Adds up the per-workgroup rows of the PGRAD kernels (fp64 sums, fixed order: deterministic) and applies the part of
+// the chain rule that sits in front of the kernel: view_dir and a directional light enter through F.normalize
+// (cooktorrance.py:95, :126), whose Jacobian is (I - v v^T) / max(|x|, 1e-12).  One workgroup per 3-vector:
+// vector 0 = view, 1..L = lights, L+1..2L = intensities.  out: [3 + 6 L] floats in that order.
+// Stage 1 of the row sum: kParamStageRows workgroups, each adds a contiguous block of rows.  The rows are read as one flat
+// array, lane t taking elements t, t + T, t + 2 T ... with T the largest multiple of n_param <= 256, so a lane always
+// meets the same parameter and the loads are coalesced; fp64, fixed order.  (One workgroup per 3-vector walking all
+// 131 072 rows of a 4096^2 launch by itself took 155 us -- as long as the kernel that produced them.)
+constexpr int kParamStageRows = 256;
+__global__ __launch_bounds__(256) void param_grad_stage_kernel(const float *__restrict__ partials, double *__restrict__ stage,
+                                                               int n_rows, int n_param) {
+    const int T = (256 / n_param) * n_param, per = (n_rows + kParamStageRows - 1) / kParamStageRows;
+    const int r0 = blockIdx.x * per, r1 = min(n_rows, r0 + per);
+    __shared__ double part[256];
+    double s = 0.0;
+    if ((int)threadIdx.x < T && r0 < r1) {
+        const float *p = partials + (int64_t)r0 * n_param;
+        const int64_t n = (int64_t)(r1 - r0) * n_param;
+        for (int64_t e = threadIdx.x; e < n; e += T) s += p[e];
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if ((int)threadIdx.x < n_param) {
+        double t = 0.0;
+        for (int k = threadIdx.x; k < T; k += n_param) t += part[k];
+        stage[(int64_t)blockIdx.x * n_param + threadIdx.x] = t;
+    }
+}
+
+struct ParamFinishArgs {
+    const double *stage; float *out; int32_t n_rows, n_lights, light_type;      // n_rows = kParamStageRows rows of stage sums
+    float view[3]; float lights[PBR_MAX_LIGHTS][3];
+    uint64_t dev;                     // parameters in device memory (address of the DevParams block): the raw vectors come from it
+};
+__global__ __launch_bounds__(256) void param_grad_finish_kernel(const ParamFinishArgs a) {
+    const int vec = blockIdx.x, n_param = 3 + 6 * a.n_lights;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int r = threadIdx.x; r < a.n_rows; r += 256) {
+        const double *row = a.stage + (int64_t)r * n_param + 3 * vec;
+        s[0] += row[0]; s[1] += row[1]; s[2] += row[2];
+    }
+    __shared__ double red[3][256];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) red[j][threadIdx.x] = s[j];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    double g[3] = {red[0][0], red[1][0], red[2][0]};
+    const bool normalised = vec == 0 || (vec <= a.n_lights && a.light_type == PBR_LIGHT_DIRECTIONAL);
+    if (normalised) {
+        float x[3];
+        if (a.dev) {
+            const DevParams *d = reinterpret_cast<const DevParams *>(a.dev);
+            for (int j = 0; j < 3; ++j) x[j] = vec == 0 ? d->raw_view[j] : d->raw_lights[vec - 1][j];
+        } else {
+            for (int j = 0; j < 3; ++j) x[j] = vec == 0 ? a.view[j] : a.lights[vec - 1][j];
+        }
+        const double nrm = sqrt((double)x[0] * x[0] + (double)x[1] * x[1] + (double)x[2] * x[2]);
+        if (nrm > 1e-12) {
+            const double u[3] = {x[0] / nrm, x[1] / nrm, x[2] / nrm};
+            const double ug = u[0] * g[0] + u[1] * g[1] + u[2] * g[2];
+            for (int j = 0; j < 3; ++j) g[j] = (g[j] - u[j] * ug) / nrm;
+        } else {                     // F.normalize divides by the clamp there: d(x / 1e-12)/dx
+            for (int j = 0; j < 3; ++j) g[j] *= 1e12;
+        }
+    }
+    for (int j = 0; j < 3; ++j) a.out[3 * vec + j] = (float)g[j];
+}
 
 using BwdFn = void (*)(const KArgs, const BArgs);
 
@@ -39,7 +114,7 @@ static BwdStreamFn pick_bwd_stream(const pbr_render_desc *d, bool full) {
     });
 }
 
-// Rounds of the streamed backward kernel (ct_backward.hpp: its grid is rounds x the waves the chip holds at once), or 0 when
+// Rounds of the streamed backward kernel (ct_backward_stream.hpp: its grid is rounds x the waves the chip holds at once), or 0 when
 // the launch does not qualify: fp16 maps, one light, untiled, rows a whole number of 128-pixel tiles, 4-byte aligned planes
 // with even strides (its loads and stores move two fp16 values per lane).  g_bwd_run: -1 = rule, 0 = never, N = N rounds (A/B).
 int stream_run(const pbr_render_desc *d, const void *grad_out, void *const g[5]) {

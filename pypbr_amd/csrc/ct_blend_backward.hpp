@@ -8,7 +8,7 @@
 // registers, the chain rule runs through the shading (backward_body_to, the very code of cook_torrance_backward_kernel),
 // the re-decode and the blend, and the gradients of both materials and of the mask are written (68 B/pixel).
 //
-// Sub-gradient conventions are torch's (ct_backward.hpp); the blend's arithmetic is blend_texels' (ct_blend.hpp), so forward
+// Sub-gradient conventions are torch's (ct_chain_rule.hpp); the blend's arithmetic is blend_texels' (ct_blend.hpp), so forward
 // and backward agree on every value.  fp32 maps; both materials carry all four maps.
 #pragma once
 #include "ct_backward.hpp"

@@ -16,7 +16,7 @@
 // This file is also the home of what every loss step shares on the host -- this one and the two over light stacks (ct_stack.hip): an entry
 // point is mse_gate, pick the kernel, launch_loss_step, mse_finish (declared in ct_launch.hpp).  What they share on the device is the frame
 // loss_step (ct_backward.hpp, beside the loss policies): a step kernel is that frame with its policy and its first target loads.
-#include "ct_backward.hpp"
+#include "ct_backward_stream.hpp"
 #include "ct_launch.hpp"
 
 namespace pbr {
@@ -61,7 +61,7 @@ void cook_torrance_mse_stream_kernel(const KArgs a, const BArgs b, const int til
 // partials[n] (fp32, one per workgroup of the step kernel) -> *loss = sum / count, in two stages, fp64, fixed order:
 // kMseStageGroups workgroups each add a contiguous block of the partials (coalesced: lane t takes elements t, t + 256, ...) into
 // stage[blockIdx]; then one workgroup adds the stage sums.  (One workgroup walking all 131 072 partials of a 4096^2 launch by
-// itself took longer than the step kernel: the same lesson as the light-gradient finish kernel, ct_backward.hpp.)
+// itself took longer than the step kernel: the same lesson as the light-gradient finish kernel, ct_backward.hip.)
 constexpr int kMseStageGroups = 256;
 __device__ __forceinline__ double block_sum_256(double s, double *red) {
     red[threadIdx.x] = s;

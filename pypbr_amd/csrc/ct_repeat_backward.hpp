@@ -7,11 +7,12 @@
 // Here the grid walks the SOURCE maps, like cook_torrance_repeat_kernel in the forward direction: a lane loads its texels once,
 // re-evaluates the light-independent forward terms once (colour decode and its slope, F0, normal, the PixelTerms), then visits the
 // rep_y x rep_x output positions of its texels -- upstream gradient in (12 B per output pixel), light geometry, the chain rule of
-// ct_backward.hpp (eval_light / backprop_light), the light-independent tail -- and adds each position's gradient to register
+// ct_chain_rule.hpp (eval_light / colour_adjoint / backprop_light), the light-independent tail -- and adds each position's gradient to register
 // accumulators in the order pbr_fold_gradient adds them (repeat rows outer, repeat columns inner).  Map-sized gradients are
 // written once: 12 B per output pixel + 64 B per texel instead of 76 + 32 (fold reads) + 32/n^2 per output pixel.
 //
-// Same functions per position as backward_body_to.  What differs from pbr_cook_torrance_backward + pbr_fold_gradient is the ORDER OF
+// The chain rule is ct_chain_rule.hpp's: bwd_decode, colour_adjoint / colour_adjoint_lights, backprop_light and bwd_tail; backward_body_to runs
+// the same colour adjoint and backprop_light per pixel (and the decode's and the tail's statements inline).  What differs from pbr_cook_torrance_backward + pbr_fold_gradient is the ORDER OF
 // SUMMATION, never a formula (round 6): the chain rule splits into a per-position part (light geometry, eval_light, backprop_light:
 // adjoints of kb / f0 / a2 / k / N.V / the unit normal) and a light-independent tail (bwd_tail) that is LINEAR in those adjoints with
 // coefficients that depend on the texel only.  The positions' adjoints are accumulated (backprop_light's fused multiply-adds, straight
@@ -33,82 +34,6 @@
 #include "ct_blend_backward.hpp"
 
 namespace pbr {
-
-// Forward decode of one pixel group, as the chain rule needs it again (cooktorrance.py:99-118 and the conversions it calls):
-// the statements of backward_body_to's "forward: decoded colours and their derivatives" block.
-template <class R> struct BwdTexelT {
-    R base[3], dbase[3], f0[3], df0[3], alin[3];
-    R m, om, kd_scale, rough;
-    Vec3T<R> nraw;
-    PixelTermsT<R> pt;
-};
-
-template <int WF, int VEC, class R>
-__device__ __forceinline__ void bwd_decode(const KArgs &a, const Texels<VEC> &t, int g, const Vec3 &V, BwdTexelT<R> &x) {
-    x.kd_scale = splat<R>(1.0f);
-    x.m = WF != PBR_WORKFLOW_SPECULAR ? gather<R>(t.me, g) : splat<R>(0.0f);
-    x.om = splat<R>(1.0f) - x.m;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const R al = gather<R>(t.al[c], g);
-        x.alin[c] = x.base[c] = al; x.dbase[c] = splat<R>(1.0f);
-        if (a.albedo_srgb) srgb_to_linear_and_grad(al, x.base[c], x.dbase[c]);
-        x.alin[c] = x.base[c];
-        if (WF == PBR_WORKFLOW_METALLIC) {
-            x.f0[c] = fma_(x.m, x.base[c], x.om * kDielectricF0);                  // lerp(0.04, base, m) :107
-            x.df0[c] = splat<R>(0.0f);
-        } else if (WF == PBR_WORKFLOW_SPECULAR) {
-            const R sp = gather<R>(t.sp[c], g);
-            x.f0[c] = sp; x.df0[c] = splat<R>(1.0f);
-            if (a.spec_srgb) srgb_to_linear_and_grad(sp, x.f0[c], x.df0[c]);
-        } else {   // CONVERTED: to_diffuse_specular_material (metallic.py:98-108), then the specular workflow
-            const R sp = fma_(x.alin[c], x.m, x.om * kDielectricF0);
-            x.base[c] = x.alin[c] * x.om;
-            x.f0[c] = sp; x.df0[c] = splat<R>(1.0f);
-            if (a.spec_srgb) srgb_to_linear_and_grad(sp, x.f0[c], x.df0[c]);
-        }
-    }
-    if (WF == PBR_WORKFLOW_METALLIC) x.kd_scale = x.om;
-    x.nraw = {gather<R>(t.nm[0], g), gather<R>(t.nm[1], g), gather<R>(t.nm[2], g)};
-    x.rough = gather<R>(t.ro, g);
-    pixel_terms(x.nraw, V, x.rough, x.base, x.f0, x.kd_scale, x.pt);
-}
-
-// The light-independent tail of the chain rule (backward_body_to's last block): adjoints of kb / f0 / a2 / k / N.V / the unit
-// normal -> gradients w.r.t. the stored texels of the group.
-template <int WF, class R>
-__device__ __forceinline__ void bwd_tail(const BwdTexelT<R> &x, const PixelAdjointT<R> &adj, const Vec3 &V, R (&ga)[3], R (&gn)[3], R &gr, R &gm,
-                                         R (&gs)[3]) {
-    // kb = kd_scale * base / pi ; kd_scale = 1 - m  (:169-174)
-    R g_m = splat<R>(0.0f);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        R g_base = adj.g_kb[c] * (x.kd_scale * kInvPi);
-        gs[c] = splat<R>(0.0f);
-        if (WF == PBR_WORKFLOW_METALLIC) {                               // kd_scale = 1 - m; lerp(0.04, base, m)  (:107)
-            g_m = fma_(adj.g_kb[c], x.base[c] * (-kInvPi), g_m);
-            g_base = fma_(adj.g_f0[c], x.m, g_base);
-            g_m = fma_(adj.g_f0[c], x.base[c] - kDielectricF0, g_m);
-        } else if (WF == PBR_WORKFLOW_SPECULAR) {
-            gs[c] = adj.g_f0[c] * x.df0[c];
-        } else {   // diffuse = a (1-m) ; specular = 0.04 (1-m) + a m
-            const R g_sp = adj.g_f0[c] * x.df0[c], g_diff = adj.g_kb[c] * kInvPi;
-            g_base = fma_(g_diff, x.om, g_sp * x.m);
-            g_m = fma_(g_sp, x.alin[c] - kDielectricF0, fma_(-g_diff, x.alin[c], g_m));
-        }
-        ga[c] = g_base * x.dbase[c];
-    }
-    gm = g_m;
-    gr = fma_(adj.g_k, (x.rough + 1.0f) * 0.25f, adj.g_a2 * (x.rough * 2.0f));   // k = (r+1)^2/8, a2 = r^2
-    // N.V clamp, then F.normalize: g_n = (g - n (n.g)) / |n|
-    const R gv = masked(in_unit(x.pt.ndv_raw, x.pt.ndv), adj.g_ndv);
-    const Vec3T<R> gnh = {fma_(gv, splat<R>(V.x), adj.g_n.x), fma_(gv, splat<R>(V.y), adj.g_n.y), fma_(gv, splat<R>(V.z), adj.g_n.z)};
-    const R rn = rsq(dot_plus(x.nraw, x.nraw, 1e-24f));
-    const R radial = dot(x.pt.n, gnh);
-    gn[0] = (gnh.x - x.pt.n.x * radial) * rn;
-    gn[1] = (gnh.y - x.pt.n.y * radial) * rn;
-    gn[2] = (gnh.z - x.pt.n.z * radial) * rn;
-}
 
 // The texel state only the TAIL reads (decoded colours and their slopes, metallic, roughness, the stored normal) is parked in LDS across the
 // position loop -- written once, read once (round 6).  With the tail behind the loop the gradient kernels of ONE light then need 164
@@ -146,7 +71,7 @@ struct RBArgs {
 //   LIGHT / WF: as everywhere.  TM: storage type of the maps and of their gradients.  LOSS: the rendering-loss step.
 // KArgs as fill_repeat_args leaves them (the grid of an untiled launch over the source maps; rep_y / rep_x / out_W / out_Ht /
 // y_offset / H_total describe the output) with o_cs = the MAP's plane (the gradient planes are dense [B][C][map_h * map_w]).
-//   MULTI: several lights (H12: per-light clamp, sum, clamp, encode) -- per position the two passes over the lights of backward_body_to (the
+//   MULTI: several lights (H12: per-light clamp, sum, clamp, encode) -- per position the two passes over the lights (colour_adjoint_lights: the
 //   summed colour decides the outer clamp and the encode's slope; then every light's chain rule into one adjoint); no loss policy.
 //   BLEND (round 6): the texels are the blend of TWO materials under a mask (ct_blend.hpp: blend_texels, the blended normal re-decoded), formed
 //   once per texel in front of the walk; behind it the folded gradients run on through the blend's own chain rule (blend_backward_sink) into
@@ -211,9 +136,7 @@ __device__ __forceinline__ void repeat_backward_body(const KArgs &a, const BArgs
     BwdTexelT<R> x;
     bwd_decode<WF, VEC, R>(a, t, 0, V, x);
 
-    R acc_a[3], acc_n[3], acc_s[3], acc_r = splat<R>(0.0f), acc_m = splat<R>(0.0f);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { acc_a[c] = splat<R>(0.0f); acc_n[c] = splat<R>(0.0f); acc_s[c] = splat<R>(0.0f); }
+    float oa[3][VEC], on[3][VEC], os[3][VEC] = {}, orr[VEC], om[VEC];            // the texels' gradients, summed over the repeats: bwd_tail writes them
     float sq = 0.0f;
 
     if constexpr (LIGHT == PBR_LIGHT_DIRECTIONAL && !MULTI) {
@@ -225,12 +148,13 @@ __device__ __forceinline__ void repeat_backward_body(const KArgs &a, const BArgs
         const LightGeomT<R> lg = light_geom<LIGHT, R>(lu, V, splat<R>(0.0f), 0.0f);
         LightEvalT<R> e;
         eval_light(x.pt, lg, lu.inten, e);
-        R out[3], gsum[3] = {splat<R>(0.0f), splat<R>(0.0f), splat<R>(0.0f)};
-        R enc_slope[3] = {splat<R>(1.0f), splat<R>(1.0f), splat<R>(1.0f)};
+        // The one-light colour adjoint around the sum: without a loss colour_adjoint runs on the summed upstream values; with the loss the
+        // differences out - target are what is summed, so its two steps stand apart, encode_and_slope in front of the loop, behind_encode behind it.
+        const bool srgb = a.out_srgb != 0;
+        R out[3], enc_slope[3], gsum[3] = {splat<R>(0.0f), splat<R>(0.0f), splat<R>(0.0f)};
+        if constexpr (LOSS) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {                                                                           // :179-180 (the loss compares this) and its slope
-            out[c] = e.uc[c];
-            if (a.out_srgb) { if (LOSS) linear_to_srgb_unit_and_grad(e.uc[c], out[c], enc_slope[c]); else enc_slope[c] = linear_to_srgb_grad_unit(e.uc[c]); }
+            for (int c = 0; c < 3; ++c) encode_and_slope(srgb, e.uc[c], out[c], enc_slope[c]);                  // :179-180 (the loss compares this) and its slope
         }
         // the positions' loads do not depend on one another: four positions' worth (12 loads) in flight before the first add
         constexpr int kChunk = 4;
@@ -256,19 +180,17 @@ __device__ __forceinline__ void repeat_backward_body(const KArgs &a, const BArgs
             }
         }
         R g_col[3];
+        if constexpr (LOSS) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const R gc = LOSS ? gsum[c] * rb.scale : gsum[c];
-            g_col[c] = a.out_srgb ? gc * enc_slope[c] : gc;
+            for (int c = 0; c < 3; ++c) g_col[c] = behind_encode(srgb, gsum[c] * rb.scale, enc_slope[c]);
+        } else {
+            colour_adjoint(srgb, e.uc, gsum, g_col);
         }
         PixelAdjointT<R> adj;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { adj.g_kb[c] = splat<R>(0.0f); adj.g_f0[c] = splat<R>(0.0f); }
-        adj.g_a2 = adj.g_k = adj.g_ndv = splat<R>(0.0f);
-        adj.g_n = {splat<R>(0.0f), splat<R>(0.0f), splat<R>(0.0f)};
+        adj.clear();
         LightParamAdjT<R> pa;
         backprop_light<LIGHT, false>(x.pt, lg, lu.inten, e, g_col, adj, V, pa);
-        bwd_tail<WF, R>(x, adj, V, acc_a, acc_n, acc_r, acc_m, acc_s);
+        bwd_tail<WF, VEC, R>(x, adj, V, 0, oa, on, orr, om, os);
     } else {
         // The position loop, written for the SCALAR unit as much as for the vector one (round 6).  With two waves per SIMD a wave's own
         // scalar instructions are time its vector pipe idles unless the other wave happens to issue: the loop used to spend ~130 scalar
@@ -297,13 +219,7 @@ __device__ __forceinline__ void repeat_backward_body(const KArgs &a, const BArgs
         if (kAhead && row_in_band(n_yrow)) fetch(n_rep, go);
         float ys = 0.0f;
         PixelAdjointT<R> adj;                   // summed over the positions; the tail is applied once, behind the loop
-        auto clear_adjoint = [&]() {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { adj.g_kb[c] = splat<R>(0.0f); adj.g_f0[c] = splat<R>(0.0f); }
-            adj.g_a2 = adj.g_k = adj.g_ndv = splat<R>(0.0f);
-            adj.g_n = {splat<R>(0.0f), splat<R>(0.0f), splat<R>(0.0f)};
-        };
-        clear_adjoint();
+        adj.clear();
         constexpr bool kPark = RepeatBwdShape<LOSS, MULTI>::park && !BLEND;       // (the blend form carries two materials' texels anyway: two waves)
         __shared__ float2 s_park[kPark ? kParkSlots * 64 : 1];
         if constexpr (kPark) park_texel<WF>(s_park + threadIdx.x, x, false);
@@ -336,21 +252,12 @@ __device__ __forceinline__ void repeat_backward_body(const KArgs &a, const BArgs
                         xs[0] = fma_(splat<R>(lo ? a.xstep : -a.xstep), fma_(splat<R>(lo ? 1.0f : -1.0f), lane_offsets<R>(0), splat<R>(f0)), splat<R>(lo ? a.x0 : a.x1));
                     }
                 }
-                if constexpr (MULTI) {
-                    R g_col[3], sum[3] = {splat<R>(0.0f), splat<R>(0.0f), splat<R>(0.0f)};
-                    for (int l = 0; l < a.n_lights; ++l) {          // pass 1: the summed colour decides the outer clamp / the encode's slope
-                        const LightU ll = light_of(a, l);
-                        LightEvalT<R> e;
-                        eval_light(x.pt, light_geom<LIGHT, R>(ll, V, xs[0], ys), ll.inten, e);
-    #pragma unroll
-                        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + e.uc[c];
-                    }
-    #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const R slope = SRGB ? linear_to_srgb_grad_unit(clamp01(sum[c])) : splat<R>(1.0f);
-                        g_col[c] = masked(in_unit(sum[c]), gather<R>(go[c], 0) * slope);
-                    }
-                    for (int l = 0; l < a.n_lights; ++l) {          // pass 2: every light's chain rule into the one adjoint
+                const R ref[3] = {gather<R>(go[0], 0), gather<R>(go[1], 0), gather<R>(go[2], 0)};      // upstream values; the loss step: the target's
+                R g_col[3];
+                float sqd[3] = {};                                  // the loss step: the position's squared differences
+                if constexpr (MULTI) {                              // pass 1 inside; pass 2: every light's chain rule into the one adjoint
+                    colour_adjoint_lights<LIGHT, false>(a, SRGB, x.pt, V, xs[0], ys, ref, 0.0f, g_col, sqd);
+                    for (int l = 0; l < a.n_lights; ++l) {
                         const LightU ll = light_of(a, l);
                         const LightGeomT<R> lg = light_geom<LIGHT, R>(ll, V, xs[0], ys);
                         LightEvalT<R> e;
@@ -362,24 +269,8 @@ __device__ __forceinline__ void repeat_backward_body(const KArgs &a, const BArgs
                     const LightGeomT<R> lg = light_geom<LIGHT, R>(lu, V, xs[0], ys);
                     LightEvalT<R> e;
                     eval_light(x.pt, lg, lu.inten, e);
-                    R gout_c[3], g_col[3];
-                    if constexpr (LOSS) {
-            #pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            R out = e.uc[c], slope = splat<R>(1.0f);
-                            if (SRGB) linear_to_srgb_unit_and_grad(e.uc[c], out, slope);               // :179-180 and its slope, one log2
-                            const R d = out - gather<R>(go[c], 0);
-                            if (p.valid) sq += hsum(d * d);
-                            gout_c[c] = d * rb.scale;
-                            g_col[c] = SRGB ? gout_c[c] * slope : gout_c[c];
-                        }
-                    } else {
-            #pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            gout_c[c] = gather<R>(go[c], 0);
-                            g_col[c] = SRGB ? gout_c[c] * linear_to_srgb_grad_unit(e.uc[c]) : gout_c[c];
-                        }
-                    }
+                    colour_adjoint<LOSS>(SRGB, e.uc, ref, rb.scale, g_col, sqd);
+                    if (LOSS && p.valid) { sq += sqd[0]; sq += sqd[1]; sq += sqd[2]; }      // the loss's sum counts the lanes inside the map only
                     LightParamAdjT<R> pa;
                     backprop_light<LIGHT, false>(x.pt, lg, lu.inten, e, g_col, adj, V, pa);
                 }
@@ -399,17 +290,13 @@ __device__ __forceinline__ void repeat_backward_body(const KArgs &a, const BArgs
             park_texel<WF>(s_park + threadIdx.x, x, true);
             if (WF == PBR_WORKFLOW_METALLIC) { x.om = splat<R>(1.0f) - x.m; x.kd_scale = x.om; }      // (1 - m: recomputed, the same subtraction)
         }
-        bwd_tail<WF, R>(x, adj, V, acc_a, acc_n, acc_r, acc_m, acc_s);
+        bwd_tail<WF, VEC, R>(x, adj, V, 0, oa, on, orr, om, os);
     }
     if constexpr (LOSS) {
         const float total = wave_sum(sq);
         if (threadIdx.x == 0) rb.partials[blockIdx.x] = total;
         if (!p.valid) return;
     }
-    float oa[3][VEC], on[3][VEC], os[3][VEC], orr[VEC], om[VEC];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { scatter(oa[c], 0, acc_a[c]); scatter(on[c], 0, acc_n[c]); scatter(os[c], 0, acc_s[c]); }
-    scatter(orr, 0, acc_r); scatter(om, 0, acc_m);
     if constexpr (BLEND) {
         blend_backward_sink<WF, VEC>(a, p, mat, t1, u, w, keep_signed, b, *g2, oa, on, orr, om, os);
     } else {

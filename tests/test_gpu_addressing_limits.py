@@ -378,7 +378,7 @@ def _backward_window_ref(maps, gout, y0, kw):
                          ids=["f16-streamed", "f32-one-tile"])
 def test_scalar_bases_at_their_limit_backward(dtype, normal, second):
     """Backward of one 32752 x 32768 material; the fp32 upstream gradient's lane offsets reach 2^32 - 2 MiB bytes.
-    fp16 maps: the streamed kernel, which always addresses through scalar bases (ct_backward.hpp) and is only chosen for planes below 2^30 px
+    fp16 maps: the streamed kernel, which always addresses through scalar bases (ct_backward_stream.hpp) and is only chosen for planes below 2^30 px
     (stream_run); its second form is the one-tile kernels (bwd_run = 0), whose scalar bases follow fill_args.  fp32 maps: the one-tile kernel
     (without a normal map, to keep the footprint down), second form scalar_base = 0.  Every gradient plane bit-equal to the second form; the
     first and last rows against float64 autograd (test_gpu_backward.py's criteria: fp32 2e-5 (1 + |g|), fp16 storage 1e-3 (1e-3 + |g|)).

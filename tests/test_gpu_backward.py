@@ -388,7 +388,7 @@ def test_light_view_intensity_gradients_match_the_reference_autograd(kind, lk, g
 @pytest.mark.gpu
 def test_streamed_backward_is_bit_identical_to_the_one_tile_kernels():
     """fp16 maps with one light and rows that are a whole number of 128-pixel tiles take the streamed backward kernel
-    (ct_backward.hpp: a wave walks a run of tiles, the next tile's texels travel global -> LDS while the current one is
+    (ct_backward_stream.hpp: a wave walks a run of tiles, the next tile's texels travel global -> LDS while the current one is
     differentiated).  Same backward_body as the one-tile kernel, so every gradient must agree bit for bit -- for runs
     that do not divide the tile count, batches, every workflow, both light types, a missing normal map, sRGB off, and
     only some of the gradients wanted."""

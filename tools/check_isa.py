@@ -4,7 +4,7 @@
 Two kernels of this library are correct only if the compiler emits exactly the memory instructions their hand-counted waits
 assume ("What's weak" #7):
 
-* `cook_torrance_backward_stream_kernel<LIGHT, WF, FULL>` (csrc/ct_backward.hpp): the next tile's texels travel global -> LDS by
+* `cook_torrance_backward_stream_kernel<LIGHT, WF, FULL>` (csrc/ct_backward_stream.hpp): the next tile's texels travel global -> LDS by
   DMA (`global_load_lds_dword`), the tile's values leave LDS through hand-written `ds_read`s after a hand-counted
   `s_waitcnt vmcnt(N)` -- N = the stores of one tile, because the tile's loads were issued before the previous tile's N stores
   and vmcnt retires in order.  That holds only if: the kernel has NO other vector-memory traffic (no scratch, no buffer ops, no
