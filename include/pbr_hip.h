@@ -328,6 +328,33 @@ int pbr_cook_torrance_mse_stack_step(const pbr_render_desc *desc, const void *ta
 size_t pbr_mse_stack_fit_workspace_bytes(const pbr_render_desc *desc);
 int pbr_cook_torrance_mse_stack_fit_step(const pbr_render_desc *desc, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
                                          void *g_metallic, void *g_specular, void *g_params, void *loss, void *workspace, void *stream);
+/*
+ * The perspective camera (an extension: upstream's view_dir is one direction for the whole image, i.e. an orthographic camera).  `desc` as for
+ * pbr_cook_torrance, but `desc->view_dir` is a camera POSITION C in the coordinates of a point light's position: the surface point of pixel
+ * (y, x) is P = (xs[x], -ys[y], 0) with xs = linspace(-s/2, s/2, width), ys = linspace(-s/2, s/2, height_total), s = light_size or 1.0
+ * (cooktorrance.py:130-136; the same grid for both light types), and that pixel's view vector is F.normalize(C - P).  Pixel (y, x) of the result
+ * equals pixel (y, x) of upstream's forward called with view_dir = C - P(y, x); a camera exactly on a pixel gives the zero view vector there,
+ * as F.normalize does.  fp32 or fp16 maps, all workflows, both light types, 1..PBR_MAX_LIGHTS lights summed as pbr_cook_torrance sums them,
+ * batches, row bands (y_offset / height_total), both out strides; with device_params the position is the block's un-normalised view (the
+ * `view_dir` handed to pbr_prepare_device_params), lights and intensities the block's.  Before any launch: tiled maps (map_height / map_width)
+ * PBR_ERR_UNSUPPORTED; out_dtype not PBR_F32 PBR_ERR_DTYPE; the codes of pbr_cook_torrance for everything else.  A NaN light_size fills the
+ * result with NaN for either light type (the grid is NaN).
+ */
+int pbr_cook_torrance_camera(const pbr_render_desc *desc, void *stream);
+/*
+ * Its gradient: arguments as pbr_cook_torrance_backward_params (grad_out [B][3][H][W] fp32 contiguous; every non-NULL g_* contiguous, shaped
+ * like its map, in the maps' storage type; any may be NULL), and `g_params` may be NULL too: (3 + 6 L) floats of DEVICE memory, written as
+ * [d/d camera position (3) | d/d lights (L x 3) | d/d intensities (L x 3)] w.r.t. the values in the descriptor or the device_params block.  The
+ * camera's gradient is the sum over pixels of (I - v v^T) / |C - P| g_v, the normalisation Jacobian applied per pixel before the sum;
+ * directional lights keep theirs behind it, as in pbr_cook_torrance_backward_params.  `workspace`: pbr_camera_backward_workspace_bytes(desc)
+ * bytes of device memory (one row of partial sums per workgroup, then their stage sums: added up in fp64 in a fixed order, deterministic; 0
+ * where the call does not serve the descriptor); only read or written when g_params is given.  Before any launch: the codes of
+ * pbr_cook_torrance_camera; a NULL grad_out, or a g_params without a workspace, PBR_ERR_NULL_MAP; a NaN light_size PBR_ERR_UNSUPPORTED; more
+ * workgroups than the size query promised PBR_ERR_SHAPE.
+ */
+size_t pbr_camera_backward_workspace_bytes(const pbr_render_desc *desc);
+int pbr_cook_torrance_camera_backward(const pbr_render_desc *desc, const void *grad_out, void *g_albedo, void *g_normal, void *g_roughness,
+                                      void *g_metallic, void *g_specular, void *g_params, void *workspace, void *stream);
 /* ABI 5: view / light / intensity from DEVICE memory.  `view_dir` [3], `lights` [n_lights][3], `intensities` [intensity_rows][3] with
  * intensity_rows = 1 (one intensity for every light) or n_lights: fp32 device pointers; a NULL pointer takes that parameter from the descriptor
  * (d->view_dir / d->lights / d->intensities: host values), so only what lives on the device needs to be there.  Writes `block` (pbr_device_params_bytes() bytes,

@@ -51,6 +51,7 @@ EXPORTS = (
     "pbr_pack_images",
     "pbr_cook_torrance_stack", "pbr_cook_torrance_mse_stack_step",
     "pbr_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_mse_stack_fit_step",
+    "pbr_cook_torrance_camera", "pbr_camera_backward_workspace_bytes", "pbr_cook_torrance_camera_backward",
 )
 
 
@@ -191,6 +192,12 @@ def lib():
     L.pbr_cook_torrance_mse_step.restype = ctypes.c_int
     L.pbr_cook_torrance_stack.argtypes = [ctypes.POINTER(RenderDesc), vp]
     L.pbr_cook_torrance_stack.restype = ctypes.c_int
+    L.pbr_cook_torrance_camera.argtypes = [ctypes.POINTER(RenderDesc), vp]
+    L.pbr_cook_torrance_camera.restype = ctypes.c_int
+    L.pbr_camera_backward_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
+    L.pbr_camera_backward_workspace_bytes.restype = ctypes.c_size_t
+    L.pbr_cook_torrance_camera_backward.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pbr_cook_torrance_camera_backward.restype = ctypes.c_int
     L.pbr_cook_torrance_mse_stack_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pbr_cook_torrance_mse_stack_step.restype = ctypes.c_int
     L.pbr_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]

@@ -146,6 +146,27 @@ template <class R> __device__ __forceinline__ R dotu(const Vec3T<R> &a, const Ve
     return fma_(a.z, splat<R>(b.z), fma_(a.y, splat<R>(b.y), a.x * b.x));
 }
 
+// The view vector of a pixel group is either the wave-uniform Vec3 (one direction for the whole image: the reference's orthographic
+// camera, :95) or a PixelViewT<R>: one unit vector per pixel, towards a camera at a finite position (ct_camera.hip).  A type of its own,
+// not Vec3T<R>, because Vec3T<float> IS Vec3: the one-pixel kernels could not tell the two apart.  Everything that takes a view is a
+// template over it and reads it through dotv / as_real, so the uniform instantiations compile to what they always were.
+template <class R> struct PixelViewT { R x, y, z; };
+template <class R> __device__ __forceinline__ R dotv(const Vec3T<R> &a, const Vec3 &V) { return dotu(a, V); }
+template <class R> __device__ __forceinline__ R dotv(const Vec3T<R> &a, const PixelViewT<R> &V) {
+    return fma_(a.z, V.z, fma_(a.y, V.y, a.x * V.x));
+}
+// a component of either view as R
+template <class R> __device__ __forceinline__ R as_real(float v) { return splat<R>(v); }
+template <class R> __device__ __forceinline__ R as_real(f32x2 v) { return v; }
+// Camera at C, surface point (xs, -ys, 0) (the point light's grid, :129-136): e = C - P, v = F.normalize(e).  |e|^2 carries + 1e-24 in its
+// fma chain, as |h|^2 does below: a camera sitting exactly on a pixel gives V = 0 like F.normalize's 1e-12 on the norm, not NaN.
+// `rv` = 1/|e|, the v_rsq itself: the camera position's gradient needs it again.
+template <class R> __device__ __forceinline__ PixelViewT<R> pixel_view(const Vec3 &C, R xs, float ys, R &rv) {
+    const Vec3T<R> e = {splat<R>(C.x) - xs, splat<R>(C.y + ys), splat<R>(C.z)};
+    rv = rsq(dot_plus(e, e, 1e-24f));
+    return PixelViewT<R>{e.x * rv, e.y * rv, e.z * rv};
+}
+
 // Light-dependent, material-independent terms of one pixel (:122-140, :155-159).
 template <class R> struct LightGeomT {
     Vec3T<R> d;    // point: light position - surface point, un-normalised; directional: L
@@ -169,8 +190,8 @@ template <class R> __device__ __forceinline__ R pow5(R x) { const R x2 = x * x; 
 //   fma chains (below one ulp for any distance above 4e-3 / any |h| above 4e-9): r stays <= 1e6, so a light sitting
 //   exactly on a pixel, or L = -V, give L = 0 / a zero half vector like the reference's F.normalize instead of
 //   NaN.  (They replace max(., tiny): packed fp32 has no max, and the seed is free.)
-template <class R>
-__device__ __forceinline__ LightGeomT<R> point_light_geom(const Vec3 &V, const Vec3 &Lpos, R xs, float ys) {
+template <class R, class VT>
+__device__ __forceinline__ LightGeomT<R> point_light_geom(const VT &V, const Vec3 &Lpos, R xs, float ys) {
     LightGeomT<R> g;
     const Vec3T<R> d = {splat<R>(Lpos.x) - xs, splat<R>(Lpos.y + ys), splat<R>(Lpos.z)};
     const R dd = dot_plus(d, d, 1e-12f);                            // dist^2, torch.norm :138
@@ -178,10 +199,10 @@ __device__ __forceinline__ LightGeomT<R> point_light_geom(const Vec3 &V, const V
     const R rinv = r * fma_(splat<R>(-1e-7f), r, splat<R>(1.0f));   // 1/(dist + 1e-7)  :139
     g.d = d; g.rinv = rinv; g.rdist = r;
     g.att = rcp(dd + 1e-7f);                                        // :140
-    g.h = {fma_(d.x, rinv, splat<R>(V.x)), fma_(d.y, rinv, splat<R>(V.y)), fma_(d.z, rinv, splat<R>(V.z))};   // :155
+    g.h = {fma_(d.x, rinv, as_real<R>(V.x)), fma_(d.y, rinv, as_real<R>(V.y)), fma_(d.z, rinv, as_real<R>(V.z))};   // :155
     const R rh = rsq(dot_plus(g.h, g.h, 1e-24f));
     g.rhh = rh * rh; g.rh = rh;
-    g.p5 = pow5(splat<R>(1.0f) - mul_sat_after_trans(dotu(g.h, V), rh));         // :156-158, :196  (rh: the v_rsq's own result)
+    g.p5 = pow5(splat<R>(1.0f) - mul_sat_after_trans(dotv(g.h, V), rh));         // :156-158, :196  (rh: the v_rsq's own result)
     g.om5 = splat<R>(1.0f) - g.p5;
     return g;
 }
@@ -205,12 +226,12 @@ template <class R> struct PixelTermsT {
 using PixelTerms = PixelTermsT<float>;
 
 // base: linear albedo / diffuse colour; kd_scale: (1 - metallic) or 1.
-template <class R>
-__device__ __forceinline__ void pixel_terms(const Vec3T<R> &n, const Vec3 &V, R rough, const R base[3], const R f0[3],
+template <class R, class VT>
+__device__ __forceinline__ void pixel_terms(const Vec3T<R> &n, const VT &V, R rough, const R base[3], const R f0[3],
                                             R kd_scale, PixelTermsT<R> &t) {
     const R rn = rsq(dot_plus(n, n, 1e-24f));
     t.n = {n.x * rn, n.y * rn, n.z * rn};
-    t.ndv_raw = dotu(t.n, V);
+    t.ndv_raw = dotv(t.n, V);
     t.ndv = clamp01(t.ndv_raw);
     t.ndv4 = t.ndv * 4.0f;
     t.a2 = rough * rough;

@@ -40,6 +40,9 @@ struct ParamFinishArgs {
     float view[3]; float lights[PBR_MAX_LIGHTS][3];
     uint64_t dev;                     // parameters in device memory (address of the DevParams block): the raw vectors come from it
 };
+// VIEW_IS_POSITION: vector 0 is a camera position (ct_camera.hip) -- its normalisation Jacobian depends on the pixel and was applied there,
+// before the sum: the rows hold the finished gradient, only summed here.
+template <bool VIEW_IS_POSITION>
 __global__ __launch_bounds__(256) void param_grad_finish_kernel(const ParamFinishArgs a) {
     const int vec = blockIdx.x, n_param = 3 + 6 * a.n_lights;
     double s[3] = {0.0, 0.0, 0.0};
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(256) void param_grad_finish_kernel(const ParamFinis
     }
     if (threadIdx.x != 0) return;
     double g[3] = {red[0][0], red[1][0], red[2][0]};
-    const bool normalised = vec == 0 || (vec <= a.n_lights && a.light_type == PBR_LIGHT_DIRECTIONAL);
+    const bool normalised = vec == 0 ? !VIEW_IS_POSITION : (vec <= a.n_lights && a.light_type == PBR_LIGHT_DIRECTIONAL);
     if (normalised) {
         float x[3];
         if (a.dev) {
@@ -170,8 +173,9 @@ size_t param_stage_bytes(const pbr_render_desc *d) { return (size_t)kParamStageR
 
 // The finish of the light / view gradients, for every kernel that leaves rows (pbr_cook_torrance_backward_params, the stack-fit step of
 // ct_stack.hip): `rows` = n_rows rows of 3 + 6 L partial sums with their stage block param_rows_bytes(d) further on -> g_params, through the two
-// reduction kernels (fp64, fixed order, the F.normalize Jacobians; `dev`: KArgs::dev, the parameters in device memory).
-int param_grad_finish(const pbr_render_desc *d, const float *rows, int n_rows, uint64_t dev, float *g_params, hipStream_t st) {
+// reduction kernels (fp64, fixed order, the F.normalize Jacobians; `dev`: KArgs::dev, the parameters in device memory;
+// `view_is_position`: param_grad_finish_kernel's VIEW_IS_POSITION).
+int param_grad_finish(const pbr_render_desc *d, const float *rows, int n_rows, uint64_t dev, float *g_params, hipStream_t st, bool view_is_position) {
     ParamFinishArgs f;
     std::memset(&f, 0, sizeof(f));
     const int n_param = 3 + 6 * d->n_lights;
@@ -183,7 +187,8 @@ int param_grad_finish(const pbr_render_desc *d, const float *rows, int n_rows, u
     for (int c = 0; c < 3; ++c) f.view[c] = d->view_dir[c];
     for (int i = 0; i < d->n_lights; ++i)
         for (int c = 0; c < 3; ++c) f.lights[i][c] = d->lights[i][c];
-    hipLaunchKernelGGL(param_grad_finish_kernel, dim3(1u + 2u * (unsigned)d->n_lights), dim3(256), 0, st, f);
+    hipLaunchKernelGGL(view_is_position ? param_grad_finish_kernel<true> : param_grad_finish_kernel<false>, dim3(1u + 2u * (unsigned)d->n_lights),
+                       dim3(256), 0, st, f);
     return launch_status();
 }
 

@@ -131,10 +131,10 @@ template <class R> struct PixelAdjointT {
 };
 
 // Chain rule through one light's contribution, given the adjoint of its clamped colour.
-template <int LIGHT, bool PG, class R>
+template <int LIGHT, bool PG, class R, class VT>
 __device__ __forceinline__ void backprop_light(const PixelTermsT<R> &t, const LightGeomT<R> &g, const float inten[3],
                                                const LightEvalT<R> &e, const R g_col[3], PixelAdjointT<R> &adj,
-                                               const Vec3 &V, LightParamAdjT<R> &pa) {
+                                               const VT &V, LightParamAdjT<R> &pa) {
     R g_dg = splat<R>(0.0f), g_rad = splat<R>(0.0f), g_p5 = splat<R>(0.0f);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
@@ -185,15 +185,15 @@ __device__ __forceinline__ void backprop_light(const PixelTermsT<R> &t, const Li
         // ---- light / view parameters.  h = V + L (un-normalised); c = (n.h)/|h| (:215), cos = clamp((h.V)/|h|) (:156-158),
         // p5 = (1 - cos)^5 (:196).  d(x.h / |h|)/dh = (x - (x.h / |h|^2) h) / |h|.
         const R rh = g.rh;
-        const R hv = dotu(g.h, V);
+        const R hv = dotv(g.h, V);
         const R cos_raw = hv * rh;
         const R om = splat<R>(1.0f) - clamp01(cos_raw), om2 = om * om;
         const R gcs = masked(in_unit(cos_raw), g_p5 * (om2 * om2) * -5.0f) * rh;
         const R nhr = (e.ndl_raw + t.ndv_raw) * g.rhh, hvr = hv * g.rhh;
         const R wh = fma_(gch, nhr, gcs * hvr);                              // g_h = gch n + gcs V - wh h
-        const Vec3T<R> g_h = {fma_(gch, t.n.x, fma_(gcs, splat<R>(V.x), -wh * g.h.x)),
-                              fma_(gch, t.n.y, fma_(gcs, splat<R>(V.y), -wh * g.h.y)),
-                              fma_(gch, t.n.z, fma_(gcs, splat<R>(V.z), -wh * g.h.z))};
+        const Vec3T<R> g_h = {fma_(gch, t.n.x, fma_(gcs, as_real<R>(V.x), -wh * g.h.x)),
+                              fma_(gch, t.n.y, fma_(gcs, as_real<R>(V.y), -wh * g.h.y)),
+                              fma_(gch, t.n.z, fma_(gcs, as_real<R>(V.z), -wh * g.h.z))};
         pa.g_V = {fma_(gcs, g.h.x, g_h.x), fma_(gcs, g.h.y, g_h.y), fma_(gcs, g.h.z, g_h.z)};   // + the direct V of Hv.V
         const Vec3T<R> g_Ld = {fma_(gl, t.n.x, g_h.x), fma_(gl, t.n.y, g_h.y), fma_(gl, t.n.z, g_h.z)};   // N.L and h
         if (LIGHT == PBR_LIGHT_POINT) {
@@ -217,8 +217,8 @@ template <class R> struct BwdTexelT {
     PixelTermsT<R> pt;
 };
 
-template <int WF, int VEC, class R>
-__device__ __forceinline__ void bwd_decode(const KArgs &a, const Texels<VEC> &t, int g, const Vec3 &V, BwdTexelT<R> &x) {
+template <int WF, int VEC, class R, class VT>
+__device__ __forceinline__ void bwd_decode(const KArgs &a, const Texels<VEC> &t, int g, const VT &V, BwdTexelT<R> &x) {
     x.kd_scale = splat<R>(1.0f);
     x.m = WF != PBR_WORKFLOW_SPECULAR ? gather<R>(t.me, g) : splat<R>(0.0f);
     x.om = splat<R>(1.0f) - x.m;
@@ -277,8 +277,8 @@ __device__ __forceinline__ void colour_adjoint(bool srgb, const R (&uc)[3], cons
 }
 // SEVERAL lights (H12: per-light clamp, sum, clamp, encode), the same adjoint for all of them: pass 1 over the lights -- the summed colour
 // decides the outer clamp, and the encode is taken at clamp01(sum).  Pass 2, every light's backprop_light with this g_col, is the caller's.
-template <int LIGHT, bool LOSS, class R>
-__device__ __forceinline__ void colour_adjoint_lights(const KArgs &a, bool srgb, const PixelTermsT<R> &pt, const Vec3 &V, R xs, float ys,
+template <int LIGHT, bool LOSS, class R, class VT>
+__device__ __forceinline__ void colour_adjoint_lights(const KArgs &a, bool srgb, const PixelTermsT<R> &pt, const VT &V, R xs, float ys,
                                                       const R (&ref)[3], float scale, R (&g_col)[3], float (&sqd)[3]) {
     R sum[3] = {splat<R>(0.0f), splat<R>(0.0f), splat<R>(0.0f)};
     for (int l = 0; l < a.n_lights; ++l) {
@@ -296,8 +296,8 @@ template <class R> __device__ __forceinline__ void colour_adjoint(bool srgb, con
     float none[3];
     colour_adjoint<false>(srgb, uc, up, 0.0f, g_col, none);
 }
-template <int LIGHT, class R>
-__device__ __forceinline__ void colour_adjoint_lights(const KArgs &a, bool srgb, const PixelTermsT<R> &pt, const Vec3 &V, R xs, float ys, const R (&up)[3], R (&g_col)[3]) {
+template <int LIGHT, class R, class VT>
+__device__ __forceinline__ void colour_adjoint_lights(const KArgs &a, bool srgb, const PixelTermsT<R> &pt, const VT &V, R xs, float ys, const R (&up)[3], R (&g_col)[3]) {
     float none[3];
     colour_adjoint_lights<LIGHT, false>(a, srgb, pt, V, xs, ys, up, 0.0f, g_col, none);
 }
@@ -305,8 +305,8 @@ __device__ __forceinline__ void colour_adjoint_lights(const KArgs &a, bool srgb,
 // The light-independent tail of the chain rule: adjoints of kb / f0 / a2 / k / N.V / the unit normal -> gradients w.r.t. the stored texels
 // of group g, scattered into the lane's gradient arrays (gs: the specular workflow only).  Hands back gv, the adjoint of the clamped N.V:
 // with the light / view adjoints it carries the direct share of V (gv n).
-template <int WF, int VEC, class R>
-__device__ __forceinline__ R bwd_tail(const BwdTexelT<R> &x, const PixelAdjointT<R> &adj, const Vec3 &V, int g, float (&ga)[3][VEC],
+template <int WF, int VEC, class R, class VT>
+__device__ __forceinline__ R bwd_tail(const BwdTexelT<R> &x, const PixelAdjointT<R> &adj, const VT &V, int g, float (&ga)[3][VEC],
                                       float (&gn)[3][VEC], float (&gr)[VEC], float (&gm)[VEC], float (&gs)[3][VEC]) {
     // kb = kd_scale * base / pi ; kd_scale = 1 - m  (:169-174)
     R g_m = splat<R>(0.0f);
@@ -330,7 +330,7 @@ __device__ __forceinline__ R bwd_tail(const BwdTexelT<R> &x, const PixelAdjointT
     scatter(gr, g, fma_(adj.g_k, (x.rough + 1.0f) * 0.25f, adj.g_a2 * (x.rough * 2.0f)));   // k = (r+1)^2/8, a2 = r^2
     // N.V clamp, then F.normalize: g_n = (g - n (n.g)) / |n|
     const R gv = masked(in_unit(x.pt.ndv_raw, x.pt.ndv), adj.g_ndv);
-    const Vec3T<R> gnh = {fma_(gv, splat<R>(V.x), adj.g_n.x), fma_(gv, splat<R>(V.y), adj.g_n.y), fma_(gv, splat<R>(V.z), adj.g_n.z)};
+    const Vec3T<R> gnh = {fma_(gv, as_real<R>(V.x), adj.g_n.x), fma_(gv, as_real<R>(V.y), adj.g_n.y), fma_(gv, as_real<R>(V.z), adj.g_n.z)};
     const R rn = rsq(dot_plus(x.nraw, x.nraw, 1e-24f));
     const R radial = dot(x.pt.n, gnh);
     scatter(gn[0], g, (gnh.x - x.pt.n.x * radial) * rn);

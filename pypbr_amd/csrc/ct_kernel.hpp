@@ -536,8 +536,8 @@ __device__ __forceinline__ void scatter(float *v, int g, float r) { v[g] = r; }
 __device__ __forceinline__ void scatter(float *v, int g, f32x2 r) { v[2 * g] = r.x; v[2 * g + 1] = r.y; }
 
 // Material terms of pixel group g of the lane (:99-118): base colour, F0, kD scale, normal, roughness.
-template <int WF, int VEC, class R>
-__device__ __forceinline__ void material_terms(const Texels<VEC> &t, int g, const Vec3 &V, PixelTermsT<R> &pt) {
+template <int WF, int VEC, class R, class VT>
+__device__ __forceinline__ void material_terms(const Texels<VEC> &t, int g, const VT &V, PixelTermsT<R> &pt) {
     R base[3], f0[3], kd_scale = splat<R>(1.0f);
 #pragma unroll
     for (int c = 0; c < 3; ++c) base[c] = gather<R>(t.al[c], g);
@@ -610,6 +610,21 @@ __device__ __forceinline__ LightGeomT<R> light_geom(const LightU &lu, const Vec3
     g.rinv = splat<R>(1.0f); g.rdist = splat<R>(1.0f);
     g.h = {splat<R>(lu.h[0]), splat<R>(lu.h[1]), splat<R>(lu.h[2])};
     g.rhh = splat<R>(lu.rhh); g.rh = sqrt_hw(g.rhh); g.p5 = splat<R>(lu.p5); g.om5 = splat<R>(1.0f - lu.p5); g.att = splat<R>(1.0f);
+    return g;
+}
+// Under a per-pixel view nothing of a directional light is folded on the host: h = V + L, 1/|h| and the Fresnel power are per pixel for
+// both light types, by point_light_geom's statements (d = L, rinv = rdist = att = 1: the light is already a unit direction).
+template <int LIGHT, class R>
+__device__ __forceinline__ LightGeomT<R> light_geom(const LightU &lu, const PixelViewT<R> &V, R xs, float ys) {
+    if (LIGHT == PBR_LIGHT_POINT) return point_light_geom<R>(V, Vec3{lu.l[0], lu.l[1], lu.l[2]}, xs, ys);
+    LightGeomT<R> g;
+    g.d = {splat<R>(lu.l[0]), splat<R>(lu.l[1]), splat<R>(lu.l[2])};
+    g.rinv = splat<R>(1.0f); g.rdist = splat<R>(1.0f); g.att = splat<R>(1.0f);
+    g.h = {g.d.x + V.x, g.d.y + V.y, g.d.z + V.z};                                // :155
+    const R rh = rsq(dot_plus(g.h, g.h, 1e-24f));
+    g.rhh = rh * rh; g.rh = rh;
+    g.p5 = pow5(splat<R>(1.0f) - mul_sat_after_trans(dotv(g.h, V), rh));         // :156-158, :196
+    g.om5 = splat<R>(1.0f) - g.p5;
     return g;
 }
 

@@ -1,5 +1,5 @@
 // ct_launch.hpp -- host side shared by the launchers of the render kernels (cook_torrance.hip, ct_batch.hip, ct_tiled.hip,
-// ct_backward.hip, ct_repeat_backward.hip, ct_blend.hip, ct_loss.hip, ct_stack.hip): descriptor validation, the light x workflow dispatch
+// ct_backward.hip, ct_repeat_backward.hip, ct_blend.hip, ct_loss.hip, ct_stack.hip, ct_camera.hip): descriptor validation, the light x workflow dispatch
 // (with_light_workflow), the 16-byte-path test, the workgroup-order rule and the translation of a pbr_render_desc into the
 // kernel-argument block.  Launch status, alignment test and CU count: launch_util.hpp (through stream_shape.hpp).  Tuning knobs
 // live in cook_torrance.hip (pbr_set_tuning).  Also the declarations of the host pieces several launchers call: the loss steps' gate, launch and
@@ -327,7 +327,7 @@ StreamLaunch stream_launch_shape(const pbr_render_desc *d, void *const g[5], int
 int64_t max_tiles(const pbr_render_desc *d);
 size_t param_rows_bytes(const pbr_render_desc *d);
 size_t param_stage_bytes(const pbr_render_desc *d);
-int param_grad_finish(const pbr_render_desc *d, const float *rows, int n_rows, uint64_t dev, float *g_params, hipStream_t st);
+int param_grad_finish(const pbr_render_desc *d, const float *rows, int n_rows, uint64_t dev, float *g_params, hipStream_t st, bool view_is_position = false);
 
 // The repeat-inner kernels (cook_torrance_repeat_kernel, cook_torrance_repeat_backward_kernel) serve every tiled launch whose map rows hold a
 // 4-texel lane: the whole tiled image or a row band of it (a multi-GPU shard) of ANY height -- a band thinner than a period walks the window

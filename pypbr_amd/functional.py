@@ -70,6 +70,26 @@ from ._rotate_ops import (  # noqa: F401
 TensorLike = Union[torch.Tensor, Sequence[float]]
 
 _LIGHT_TYPES = {"directional": N.LIGHT_DIRECTIONAL, "point": N.LIGHT_POINT}
+_VIEW_TYPES = ("directional", "point")
+
+
+def _view_type(kw) -> str:
+    """`view_type` of a call's keyword arguments.  "directional" (the default, upstream's behaviour): `view_dir` is one direction for the whole
+    image, an orthographic camera.  "point": `view_dir` is a camera POSITION in the point light's coordinates and every pixel looks towards it
+    (csrc/ct_camera.hip) -- whole untiled maps or row bands of them, a float32 result, no fused blend.  Pure host logic: raises before any
+    device is asked for."""
+    vt = str(kw.get("view_type", "directional")).lower()
+    if vt not in _VIEW_TYPES:
+        raise ValueError(f"Unsupported view_type: {vt}. Must be 'directional' or 'point'.")
+    if vt == "point":
+        if tile_counts(kw.get("tile", 1)) != (1, 1) or kw.get("rows") is not None:
+            raise NotImplementedError("view_type='point' renders untiled maps (tile=1): materialise the repeats first")
+        if kw.get("blend") is not None:
+            raise NotImplementedError("view_type='point' takes no fused blend: blend the materials first")
+        out = kw.get("out")
+        if kw.get("out_dtype") not in (None, torch.float32) or (isinstance(out, torch.Tensor) and out.dtype != torch.float32):
+            raise NotImplementedError("view_type='point' gives a float32 result (fp16 maps are fine)")
+    return vt
 
 
 # The caches' settings live in _caches (what they recognise as "did not change", and why all three are off by default, is said there).
@@ -272,11 +292,12 @@ class RenderPlan:
     maps repeatedly (bench.py, a rendering-loss loop) and must not pay the Python-side
     descriptor construction per step."""
 
-    def __init__(self, desc, out, keep_alive, squeeze):
+    def __init__(self, desc, out, keep_alive, squeeze, view_type="directional"):
         self.desc, self.out, self._keep, self._squeeze = desc, out, keep_alive, squeeze
         self.device = out.device
         self._second_given = keep_alive[3] is not None or keep_alive[4] is not None    # a metallic or specular map (a kept plan empties _keep)
-        self._fn = N.lib().pbr_cook_torrance
+        self.view_type = view_type                          # "point": desc.view_dir is a camera position, launched through pbr_cook_torrance_camera
+        self._fn = N.lib().pbr_cook_torrance_camera if view_type == "point" else N.lib().pbr_cook_torrance
         self._ref = ctypes.byref(desc)
         self._param_tensors = (None, None, None)            # device-resident view / lights / intensities (prepare_device_parameters)
         self._param_block, self._param_stream = None, None
@@ -391,7 +412,8 @@ def plan_cook_torrance(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
                        out: Optional[torch.Tensor] = None, schedule: int = N.SCHEDULE_AUTO,
                        autotune: bool = False, tile=1, rows: Optional[int] = None,
                        blend: Optional[Sequence[Optional[torch.Tensor]]] = None,
-                       blend_flags: Optional[torch.Tensor] = None, tuning: Optional[dict] = None) -> RenderPlan:
+                       blend_flags: Optional[torch.Tensor] = None, tuning: Optional[dict] = None,
+                       view_type: str = "directional") -> RenderPlan:
     """Validates the maps, allocates the output and fills the C-ABI descriptor; see `cook_torrance`.
     `schedule`: workgroup order (N.SCHEDULE_AUTO | N.SCHEDULE_LINEAR | N.schedule_xcd(c)), results do not depend
     on it; `autotune=True` measures the candidates on these very buffers once (blocking, a few launches) and
@@ -406,7 +428,10 @@ def plan_cook_torrance(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
     signed is decided over the WHOLE map (base.py:212); the launch works that out itself unless the maps are a row band
     of a taller untiled map -- then pass `blend_flags` (int32 [B] on the device: `RenderPlan.blend_normal_sign()` of
     every band, combined with max; distributed.cook_torrance_sharded does this).
-    `tuning={"lds_bytes": 0, ...}`: per-call schedule knobs of this plan (RenderPlan.set_tuning); speed only, never results."""
+    `tuning={"lds_bytes": 0, ...}`: per-call schedule knobs of this plan (RenderPlan.set_tuning); speed only, never results.
+    `view_type="point"`: `view_dir` is the camera's position (`_view_type`); the plan launches pbr_cook_torrance_camera, and a position that
+    lives on the device is read there at every launch, like any device-resident parameter."""
+    view_type = _view_type(dict(view_type=view_type, tile=tile, rows=rows, blend=blend, out_dtype=out_dtype, out=out))
     if not isinstance(albedo, torch.Tensor) or not albedo.is_cuda:
         raise RuntimeError("pypbr_amd.functional.cook_torrance needs maps on a ROCm device "
                            "(use material.to('cuda')); there is no CPU path")
@@ -434,7 +459,7 @@ def plan_cook_torrance(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
                             specular_is_srgb=specular_is_srgb, return_srgb=return_srgb,
                             convert_to_diffuse_specular=convert_to_diffuse_specular, y_offset=y_offset,
                             height_total=height_total, schedule=schedule, tile=(ny, nx))
-    plan = RenderPlan(desc, out, (a, n, r, m, s), squeeze and out.dim() == 4)
+    plan = RenderPlan(desc, out, (a, n, r, m, s), squeeze and out.dim() == 4, view_type)
     if tuning:
         plan.set_tuning(**tuning)
     if desc._device_parameters is not None:
@@ -471,7 +496,7 @@ def plan_cook_torrance(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
         else:
             flags = torch.empty(B, dtype=torch.int32, device=a.device)
         plan.attach_blend(bd, flags, (a2, n2, r2, second, k))
-    elif autotune:
+    elif autotune and view_type != "point":                 # (the schedules pbr_cook_torrance_autotune times are the orthographic kernels')
         plan.autotune()
     return plan
 
@@ -486,13 +511,15 @@ def cook_torrance(albedo: torch.Tensor, normal: Optional[torch.Tensor], roughnes
     view_dir, light, light_intensity (required), light_type="point", light_size=None,
     albedo_is_srgb=True, specular_is_srgb=True, return_srgb=True,
     convert_to_diffuse_specular=False, y_offset=0, height_total=None, out_dtype=None, out=None,
-    schedule=0, autotune=False, tile=1, rows=None, blend=None, blend_flags=None (see `plan_cook_torrance`).
+    schedule=0, autotune=False, tile=1, rows=None, blend=None, blend_flags=None, view_type="directional" (see `plan_cook_torrance`;
+    with view_type="point" `view_dir` is a camera position and its gradient the position's).
     Returns [3,H,W] or [B,3,H,W] (float32 unless `out_dtype`), on the same device,
     enqueued on the current stream without synchronising.  Differentiable with respect to the maps and to
     view_dir / light / light_intensity when those are tensors that require grad (backward kernels); the plain
     evaluation goes through `torch.ops.pbr_hip.cook_torrance` when that extension is built, through the ctypes
     binding of the same C ABI otherwise (and for out= / schedule= / autotune= / blend=).
     """
+    _view_type(kwargs)
     if kwargs.get("blend") is not None and torch.is_grad_enabled() and any(
             isinstance(t, torch.Tensor) and t.requires_grad
             for t in (albedo, normal, roughness, metallic, specular) + tuple(kwargs["blend"]) + tuple(kwargs.get(k) for k in _PARAM_KEYS)):
@@ -652,6 +679,8 @@ def _torch_op_can_take(albedo, kw) -> bool:
         return False
     if kw.get("out_dtype") not in (None, torch.float32, torch.float16):
         return False
+    if kw.get("view_type", "directional") != "directional":                 # the camera has no operator: the ctypes plan
+        return False
     from . import torch_ops
     return torch_ops.available()
 
@@ -670,8 +699,9 @@ def _param_tensor(v, rows):
 def _cook_torrance_via_torch_op(albedo, normal, roughness, metallic=None, specular=None, *, view_dir, light, light_intensity,
                                 light_type="point", light_size=None, albedo_is_srgb=True, specular_is_srgb=True, return_srgb=True,
                                 convert_to_diffuse_specular=False, y_offset=0, height_total=None, out_dtype=None, tile=1, rows=None,
-                                out=None, schedule=N.SCHEDULE_AUTO, autotune=False, blend=None, blend_flags=None, tuning=None):
-    # (out / schedule / autotune / blend are at their defaults here -- _torch_op_can_take -- and named so that an unknown
+                                out=None, schedule=N.SCHEDULE_AUTO, autotune=False, blend=None, blend_flags=None, tuning=None,
+                                view_type="directional"):
+    # (out / schedule / autotune / blend / view_type are at their defaults here -- _torch_op_can_take -- and named so that an unknown
     # keyword raises TypeError exactly as on the plan path; blend_flags without a blend means nothing on either path)
     lt = str(light_type).lower()
     if lt not in _LIGHT_TYPES:   # cooktorrance.py:62-65
@@ -763,11 +793,16 @@ class _CookTorranceFn(torch.autograd.Function):
             return (*grads, None, None, None, None)
         bufs = [torch.empty((B, channels[i], H, W), dtype=gdtype, device=g.device) if wanted[i] else None for i in range(5)]
         ptrs = [ptr(b) for b in bufs]
+        camera = plan.view_type == "point"                     # gp[0:3] is then the camera position's gradient (pbr_cook_torrance_camera_backward)
         if want_params:
             L = d.n_lights
             gp = torch.empty(3 + 6 * L, dtype=torch.float32, device=g.device)
-            ws = torch.empty(max(1, lib.pbr_param_grad_workspace_bytes(ctypes.byref(d)) // 4), dtype=torch.float32, device=g.device)
-            launch(g.device, lib.pbr_cook_torrance_backward_params, ctypes.byref(d), g.data_ptr(), *ptrs, gp.data_ptr(), ws.data_ptr())
+            query = lib.pbr_camera_backward_workspace_bytes if camera else lib.pbr_param_grad_workspace_bytes
+            ws = torch.empty(max(1, query(ctypes.byref(d)) // 4), dtype=torch.float32, device=g.device)
+            launch(g.device, lib.pbr_cook_torrance_camera_backward if camera else lib.pbr_cook_torrance_backward_params, ctypes.byref(d),
+                   g.data_ptr(), *ptrs, gp.data_ptr(), ws.data_ptr())
+        elif camera:
+            launch(g.device, lib.pbr_cook_torrance_camera_backward, ctypes.byref(d), g.data_ptr(), *ptrs, None, None)
         else:
             launch(g.device, lib.pbr_cook_torrance_backward, ctypes.byref(d), g.data_ptr(), *ptrs)
         grads = []
@@ -995,14 +1030,16 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
     docs/source/tutorials/06_advanced.rst:73-107 for the predicted material -- as a 0-dim tensor on the maps' device.  When a map
     requires grad and the evaluation qualifies (whole untiled maps of the batch, fp32 result, light / view parameters without
     gradients, every map with its own planes) loss and gradients come out of ONE kernel, pbr_cook_torrance_mse_step; otherwise
-    it is the differentiable evaluation followed by torch's MSE (same value to fp32 rounding, same gradients)."""
+    it is the differentiable evaluation followed by torch's MSE (same value to fp32 rounding, same gradients); so is every call with
+    view_type="point"."""
     maps = (albedo, normal, roughness, metallic, specular)
     params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
     grad_maps = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in maps)
     grad_other = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in params + (target,))
     B = albedo.shape[0] if albedo.dim() == 4 else 1
     shared = B > 1 and any(_shared_by_batch(t, B) for t in maps)
-    if grad_maps and not grad_other and _plain_kwargs(kwargs, _STEP_EXCLUDED) and not shared and albedo.is_cuda:
+    camera = _view_type(kwargs) == "point"                   # no fused camera step: the differentiable evaluation and torch's MSE
+    if grad_maps and not grad_other and _plain_kwargs(kwargs, _STEP_EXCLUDED) and not shared and albedo.is_cuda and not camera:
         # tiled maps (tile=n: MaterialBase.tile fused) take the one pass too -- the repeat-inner kernel leaves map-sized gradients -- where
         # the library serves them (one light, map rows of whole 4-texel groups); otherwise the three steps below
         kw = {k: v for k, v in kwargs.items() if k not in _STEP_EXCLUDED}
@@ -1048,12 +1085,13 @@ def cook_torrance_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], ro
     [1,3] for all lights or [L,3]; image l is exactly `cook_torrance(..., light=light[l], light_intensity=light_intensity[l])`.  Returns
     [L,3,H,W], or [B,L,3,H,W] for batched maps, float32.  ONE launch (pbr_cook_torrance_stack: maps read and decoded once, the
     light-independent terms formed once per pixel) when nothing requires grad and the maps are whole and untiled; otherwise -- gradients, `tile`,
-    `out_dtype` ... -- a torch.stack of L `cook_torrance` calls, differentiable like them.  Other keyword arguments as for `cook_torrance`."""
+    `out_dtype`, view_type="point" ... -- a torch.stack of L `cook_torrance` calls, differentiable like them.  Other keyword arguments as for
+    `cook_torrance`."""
     L, rows = _stack_lights(light, light_intensity)
     if kwargs.get("out") is not None:
         raise ValueError("cook_torrance_stack allocates its result: out= is not supported")
     maps = (albedo, normal, roughness, metallic, specular)
-    if (_stack_plain(kwargs) and isinstance(albedo, torch.Tensor) and albedo.is_cuda and albedo.dim() in (3, 4) and albedo.numel() > 0
+    if (_view_type(kwargs) != "point" and _stack_plain(kwargs) and isinstance(albedo, torch.Tensor) and albedo.is_cuda and albedo.dim() in (3, 4) and albedo.numel() > 0
             and not _needs_grad(*maps, view_dir, light, light_intensity)):
         kw = {k: v for k, v in kwargs.items() if k in ("light_type", "light_size", "albedo_is_srgb", "specular_is_srgb", "return_srgb",
                                                        "convert_to_diffuse_specular", "schedule", "tuning")}
@@ -1136,7 +1174,7 @@ def _stack_route(maps, params, targets, kwargs, on_device=None):
     shared = B > 1 and any(_shared_by_batch(t, B) for t in maps)
     if on_device is None:
         on_device = albedo.is_cuda
-    if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets):
+    if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets) or _view_type(kwargs) == "point":
         return None
     if _needs_grad(*params):
         return "fit"
@@ -1153,7 +1191,7 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
     grad, pbr_cook_torrance_mse_stack_fit_step when `view_dir`, `light` or `light_intensity` does (lights, per-shot intensities or the camera
     axis being fitted, with or without the maps: their gradients come out of the same pass; a [3] / [1,3] intensity owns the sum over the
     lights, a parameter on the CPU receives a CPU gradient).  Every other case (tiled maps, maps shared by the batch, targets that require grad,
-    no gradients wanted) is the stack followed by torch's MSE: same value to fp32 rounding, same gradients."""
+    no gradients wanted, view_type="point") is the stack followed by torch's MSE: same value to fp32 rounding, same gradients."""
     L, _ = _stack_lights(kwargs.get("light"), kwargs.get("light_intensity"))
     if not isinstance(albedo, torch.Tensor) or albedo.dim() not in (3, 4):
         raise ValueError("albedo must be [3,H,W] or [B,3,H,W]")

@@ -22,9 +22,9 @@ from .models import CookTorranceBRDF
 
 class RenderingLoss(nn.Module):
     def __init__(self, light_type='point', view_dir=torch.tensor([0.0, 0.0, 1.0]), light_dir=torch.tensor([0.1, 0.1, 1.0]),
-                 light_intensity=torch.tensor([1.0, 1.0, 1.0]), light_size=None):
+                 light_intensity=torch.tensor([1.0, 1.0, 1.0]), light_size=None, view_type='directional'):
         super().__init__()
-        self.brdf = CookTorranceBRDF(light_type=light_type)
+        self.brdf = CookTorranceBRDF(light_type=light_type, view_type=view_type)    # 'point': `view_dir` is the camera's position (models.py)
         self.view_dir = view_dir
         self.light_dir = light_dir
         self.light_intensity = light_intensity
@@ -55,7 +55,8 @@ class RenderingLoss(nn.Module):
                    and torch.device(predicted_material.device).type == "cuda" and not predicted_material._has_pending()
                    and a is not None and r is not None and "normal" in predicted_material.__dict__.get("_store", {})
                    and (m is not None or s is not None) and all(t is None or t.is_cuda for t in (a, n, r, m, s))
-                   and self.brdf.override_device is None)
+                   and self.brdf.override_device is None
+                   and (self.brdf.view_type != "point" or predicted_material.lazy_tile == (1, 1)))   # the camera renders real maps: the module materialises
         if not fusable:
             rendered_pred = self.brdf(predicted_material, self.view_dir, self.light_dir, self.light_intensity, self.light_size)
             return nn.MSELoss()(rendered_pred, rendered_gt.to(rendered_pred.device))
@@ -63,6 +64,7 @@ class RenderingLoss(nn.Module):
             s = None
         return F_.rendering_loss_mse(a, n, r, m, s, target=rendered_gt.to(a.device), view_dir=self.view_dir, light=self.light_dir,
                                      light_intensity=self.light_intensity, light_type=self.brdf.light_type, light_size=self.light_size,
+                                     view_type=self.brdf.view_type,
                                      tile=predicted_material.lazy_tile,      # a recorded tile(n): evaluated and differentiated at every repeat
                                      albedo_is_srgb=bool(predicted_material.albedo_is_srgb),
                                      specular_is_srgb=bool(getattr(predicted_material, "specular_is_srgb", True)))
@@ -80,10 +82,10 @@ class MultiLightRenderingLoss(nn.Module):
     (pbr_cook_torrance_mse_stack_fit_step); through a differentiably rendered ground truth they take the composition."""
 
     def __init__(self, light_type='point', view_dir=torch.tensor([0.0, 0.0, 1.0]), lights=torch.tensor([[0.1, 0.1, 1.0]]),
-                 light_intensities=torch.tensor([1.0, 1.0, 1.0]), light_size=None):
+                 light_intensities=torch.tensor([1.0, 1.0, 1.0]), light_size=None, view_type='directional'):
         super().__init__()
         self.n_lights, self._rows = F_._stack_lights(lights, light_intensities)          # ValueError before any device work
-        self.brdf = CookTorranceBRDF(light_type=light_type)
+        self.brdf = CookTorranceBRDF(light_type=light_type, view_type=view_type)         # 'point': `view_dir` is the camera's position
         self.view_dir = view_dir
         self.lights = lights
         self.light_intensities = light_intensities
@@ -91,7 +93,7 @@ class MultiLightRenderingLoss(nn.Module):
 
     def _kwargs(self, material):
         return dict(view_dir=self.view_dir, light=self.lights, light_intensity=self.light_intensities, light_type=self.brdf.light_type,
-                    light_size=self.light_size, tile=material.lazy_tile, albedo_is_srgb=bool(material.albedo_is_srgb),
+                    light_size=self.light_size, view_type=self.brdf.view_type, tile=material.lazy_tile, albedo_is_srgb=bool(material.albedo_is_srgb),
                     specular_is_srgb=bool(getattr(material, "specular_is_srgb", True)))
 
     def _plain_maps(self, material):
@@ -101,7 +103,8 @@ class MultiLightRenderingLoss(nn.Module):
               and torch.device(material.device).type == "cuda" and not material._has_pending()
               and a is not None and r is not None and "normal" in material.__dict__.get("_store", {})
               and (m is not None or s is not None) and all(t is None or t.is_cuda for t in (a, n, r, m, s))
-              and self.brdf.override_device is None)
+              and self.brdf.override_device is None
+              and (self.brdf.view_type != "point" or material.lazy_tile == (1, 1)))    # the camera renders real maps: the module materialises
         return (a, n, r, m, None if m is not None else s) if ok else None
 
     def _render(self, material):

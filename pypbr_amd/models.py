@@ -68,14 +68,24 @@ class CookTorranceBRDF(BRDFModel):
 
         brdf = CookTorranceBRDF(light_type="point")
         color = brdf(material, view_dir, light_dir_or_position, light_intensity, light_size)
+
+    `view_type="point"` (an extension; keyword only, so that upstream's positional `override_device` keeps its place): the second argument of
+    `forward` is the camera's POSITION, in the point light's coordinates, the way `light_dir_or_position` is a direction or a position by
+    `light_type`; every pixel looks towards it (functional.cook_torrance, view_type).  The default, "directional", is upstream's one view
+    direction for the whole image.
     """
 
-    def __init__(self, light_type: str = "point", override_device: torch.device = None):
+    def __init__(self, light_type: str = "point", override_device: torch.device = None, *, view_type: str = "directional"):
         super().__init__()
         self.light_type = light_type.lower()
         if self.light_type not in ["directional", "point"]:
             raise ValueError(
                 f"Unsupported light_type: {self.light_type}. Must be 'directional' or 'point'."
+            )
+        self.view_type = str(view_type).lower()
+        if self.view_type not in ["directional", "point"]:
+            raise ValueError(
+                f"Unsupported view_type: {self.view_type}. Must be 'directional' or 'point'."
             )
         self.override_device = override_device
 
@@ -184,7 +194,11 @@ class CookTorranceBRDF(BRDFModel):
         CPU.  `light_dir_or_position` / `light_intensity` may be (L,3) for L lights.
         """
         reuse_key = None
-        if self.PLAN_REUSE and isinstance(material, MaterialBase):
+        if self.view_type == "point" and isinstance(material, MaterialBase):
+            material.materialize_blend()                      # the camera renders real maps: a recorded blend or tile(n) is carried out first
+            if material.lazy_tile != (1, 1):
+                material.materialize_tile()
+        if self.PLAN_REUSE and self.view_type != "point" and isinstance(material, MaterialBase):      # (a kept plan is an orthographic one)
             got = self._reuse_plan(material, view_dir, light_dir_or_position, light_intensity, light_size, return_srgb)
             if isinstance(got, torch.Tensor):
                 return got
@@ -253,6 +267,8 @@ class CookTorranceBRDF(BRDFModel):
         kw = dict(view_dir=view_dir, light=light_dir_or_position, light_intensity=light_intensity, light_type=self.light_type,
                   light_size=light_size, albedo_is_srgb=bool(material.albedo_is_srgb), specular_is_srgb=specular_is_srgb,
                   return_srgb=return_srgb, tile=getattr(material, "lazy_tile", (1, 1)))
+        if self.view_type != "directional":
+            kw["view_type"] = self.view_type
         if reuse_key is not None and blend is None and albedo.numel() > 0:
             plan = F_.plan_cook_torrance(*maps, **kw)
             with torch.cuda.device(plan.device):
