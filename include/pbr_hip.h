@@ -355,6 +355,26 @@ int pbr_cook_torrance_camera(const pbr_render_desc *desc, void *stream);
 size_t pbr_camera_backward_workspace_bytes(const pbr_render_desc *desc);
 int pbr_cook_torrance_camera_backward(const pbr_render_desc *desc, const void *grad_out, void *g_albedo, void *g_normal, void *g_roughness,
                                       void *g_metallic, void *g_specular, void *g_params, void *workspace, void *stream);
+/*
+ * Light stacks under the perspective camera: pbr_cook_torrance_stack, pbr_cook_torrance_mse_stack_step and
+ * pbr_cook_torrance_mse_stack_fit_step with `desc->view_dir` a camera POSITION, as for pbr_cook_torrance_camera.  Image l of the stack is what
+ * pbr_cook_torrance_camera gives for light l alone (its own clamp, its own encode); the stack and `targets` are [B][L][3][H][W] fp32
+ * contiguous; *loss, the g_* and the workspaces are the orthographic steps'; `g_params` is [d/d camera position (3) | d/d lights (L x 3) |
+ * d/d intensities (L x 3)], the position's gradient as pbr_cook_torrance_camera_backward forms it.  fp32 or fp16 maps, all workflows, both
+ * light types, batches; with device_params the position is the block's un-normalised view, read at every launch.  One pass over the maps,
+ * deterministic.  Workspaces: pbr_mse_step_workspace_bytes(desc) for the step, pbr_camera_mse_stack_fit_workspace_bytes(desc) for the fit step
+ * (the layout and size of pbr_mse_stack_fit_workspace_bytes; 0 where the call does not serve the descriptor).
+ * Before any launch -- the stack: the codes of pbr_cook_torrance_camera (map_height / map_width set at all PBR_ERR_UNSUPPORTED, an fp16 result
+ * PBR_ERR_DTYPE), out strides PBR_ERR_UNSUPPORTED; a NaN light_size fills the whole stack with NaN.  The steps: a NULL targets / loss /
+ * workspace (fit: / g_params) PBR_ERR_NULL_MAP; out_dtype not PBR_F32 PBR_ERR_DTYPE; map_height / map_width set at all, or a NaN light_size
+ * (either light type), PBR_ERR_UNSUPPORTED; more workgroups than the size query promised PBR_ERR_SHAPE.
+ */
+int pbr_cook_torrance_camera_stack(const pbr_render_desc *desc, void *stream);
+int pbr_cook_torrance_camera_mse_stack_step(const pbr_render_desc *desc, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
+                                            void *g_metallic, void *g_specular, void *loss, void *workspace, void *stream);
+size_t pbr_camera_mse_stack_fit_workspace_bytes(const pbr_render_desc *desc);
+int pbr_cook_torrance_camera_mse_stack_fit_step(const pbr_render_desc *desc, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
+                                                void *g_metallic, void *g_specular, void *g_params, void *loss, void *workspace, void *stream);
 /* ABI 5: view / light / intensity from DEVICE memory.  `view_dir` [3], `lights` [n_lights][3], `intensities` [intensity_rows][3] with
  * intensity_rows = 1 (one intensity for every light) or n_lights: fp32 device pointers; a NULL pointer takes that parameter from the descriptor
  * (d->view_dir / d->lights / d->intensities: host values), so only what lives on the device needs to be there.  Writes `block` (pbr_device_params_bytes() bytes,

@@ -52,6 +52,8 @@ EXPORTS = (
     "pbr_cook_torrance_stack", "pbr_cook_torrance_mse_stack_step",
     "pbr_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_mse_stack_fit_step",
     "pbr_cook_torrance_camera", "pbr_camera_backward_workspace_bytes", "pbr_cook_torrance_camera_backward",
+    "pbr_cook_torrance_camera_stack", "pbr_cook_torrance_camera_mse_stack_step",
+    "pbr_camera_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_camera_mse_stack_fit_step",
 )
 
 
@@ -198,7 +200,15 @@ def lib():
     L.pbr_camera_backward_workspace_bytes.restype = ctypes.c_size_t
     L.pbr_cook_torrance_camera_backward.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pbr_cook_torrance_camera_backward.restype = ctypes.c_int
-    L.pbr_cook_torrance_mse_stack_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pbr_cook_torrance_camera_stack.argtypes = [ctypes.POINTER(RenderDesc), vp]
+    L.pbr_cook_torrance_camera_stack.restype = ctypes.c_int
+    L.pbr_cook_torrance_camera_mse_stack_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pbr_cook_torrance_camera_mse_stack_step.restype = ctypes.c_int
+    L.pbr_camera_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
+    L.pbr_camera_mse_stack_fit_workspace_bytes.restype = ctypes.c_size_t
+    L.pbr_cook_torrance_camera_mse_stack_fit_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pbr_cook_torrance_camera_mse_stack_fit_step.restype = ctypes.c_int
+    L.pbr_cook_torrance_mse_stack_step.argtypes =[ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pbr_cook_torrance_mse_stack_step.restype = ctypes.c_int
     L.pbr_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
     L.pbr_mse_stack_fit_workspace_bytes.restype = ctypes.c_size_t

@@ -10,17 +10,9 @@
 // Gradient of the camera position: sum over pixels of (I - v v^T) / |e| g_v with e = C - P, v = e / |e| and g_v the adjoint of the pixel's
 // unit view vector (every light's LightParamAdjT::g_V plus the N.V path, gv n).  The Jacobian depends on the pixel, so it is applied per
 // pixel BEFORE the sum; the rows' finish (ct_backward.hip: param_grad_finish, view_is_position) leaves vector 0 as summed.
-#include "ct_backward.hpp"
-#include "ct_launch.hpp"
+#include "ct_camera.hpp"      // camera_of, camera_gate, nan_grid, camera_args: shared with the light-stack forms (ct_camera_stack.hip)
 
 namespace pbr {
-
-// The camera position of a launch: the kernel arguments' V (which the launchers fill with the position AS GIVEN, not normalised), or the
-// device block's raw_view when the parameters live in device memory.  Wave-uniform.
-__device__ __forceinline__ Vec3 camera_of(const KArgs &a) {
-    if (a.dev) { const DevParamsPtr d = dev_params(a.dev); return Vec3{d->raw_view[0], d->raw_view[1], d->raw_view[2]}; }
-    return Vec3{a.V[0], a.V[1], a.V[2]};
-}
 
 // ------------------------------------------------------------------ forward
 //   LIGHT / WF / TI / VEC as cook_torrance_kernel; the result is fp32.  VEC = 4 for widths that 4 divides, else 1.
@@ -201,23 +193,6 @@ void cook_torrance_camera_backward_kernel(const KArgs a, const BArgs b) {
 }
 
 // ------------------------------------------------------------------ launchers
-// What both entry points ask before any launch: a valid descriptor, untiled maps (there is no tiled or blended camera form), an fp32 result.
-static int camera_gate(const pbr_render_desc *d) {
-    const int rc = validate(d);
-    if (rc != PBR_OK) return rc;
-    if (d->map_height || d->map_width) return PBR_ERR_UNSUPPORTED;
-    if (d->out_dtype != PBR_F32) return PBR_ERR_DTYPE;
-    return PBR_OK;
-}
-// A NaN light_size makes the grid, hence every view vector, NaN whatever the light type (ct_launch.hpp: nan_light_size is the point light's).
-static bool nan_grid(const pbr_render_desc *d) { return d->light_size != d->light_size; }
-
-// fill_args, with the view as the kernels read it here: the position as given (fill_args normalises it for the orthographic kernels)
-static void camera_args(const pbr_render_desc *d, int vec, KArgs &k, int block_log2) {
-    fill_args(d, vec, k, block_log2);
-    for (int c = 0; c < 3; ++c) k.V[c] = d->view_dir[c];
-}
-
 template <int L, int W>
 static KernelFn pick_camera_variant(bool half_maps, int vec, bool several) {
     if (vec == 1) return half_maps ? cook_torrance_camera_kernel<L, W, __half, 1, true> : cook_torrance_camera_kernel<L, W, float, 1, true>;

@@ -875,16 +875,22 @@ def _step_plan(maps, kwargs, params=None):
     return plan
 
 
-# kind -> (entry point, workspace query); the stack kinds take [B,L,3,H,W] targets, "fit" also leaves the 3 + 6 L parameter gradients
+# kind -> (entry point, workspace query); the stack kinds take [B,L,3,H,W] targets, the fit kinds also leave the 3 + 6 L parameter gradients;
+# the camera kinds are the stack kinds of a plan with view_type="point" (the descriptor's view_dir is the camera's position)
 _STEP_KINDS = {"step": ("pbr_cook_torrance_mse_step", "pbr_mse_step_workspace_bytes"),
                "stack": ("pbr_cook_torrance_mse_stack_step", "pbr_mse_step_workspace_bytes"),
-               "fit": ("pbr_cook_torrance_mse_stack_fit_step", "pbr_mse_stack_fit_workspace_bytes")}
+               "fit": ("pbr_cook_torrance_mse_stack_fit_step", "pbr_mse_stack_fit_workspace_bytes"),
+               "camera_stack": ("pbr_cook_torrance_camera_mse_stack_step", "pbr_mse_step_workspace_bytes"),
+               "camera_fit": ("pbr_cook_torrance_camera_mse_stack_fit_step", "pbr_camera_mse_stack_fit_workspace_bytes")}
+_FIT_KINDS = ("fit", "camera_fit")
 
 
 def _launch_loss_step(kind, plan, maps, targets, wanted):
     """ONE launch of a loss step -> (gradient buffers | None per map, parameter gradients [3 + 6 L] | None, loss).  Raises _StepNotServed
     before anything is launched when the library does not serve the descriptor as one pass (e.g. tiled maps with several lights)."""
     entry, query = _STEP_KINDS[kind]
+    if kind.startswith("camera") != (plan.view_type == "point"):
+        raise ValueError("loss step %r does not take a plan with view_type=%r" % (kind, plan.view_type))
     d = plan.desc
     dev = plan.device                                       # the maps' device: targets handed over on the CPU, or on another GPU, are brought here
     lights = () if kind == "step" else (d.n_lights,)
@@ -895,7 +901,7 @@ def _launch_loss_step(kind, plan, maps, targets, wanted):
     # it -- autograd takes ownership of such a gradient instead of cloning it (a 4096^2 fp16 albedo: 73 us per step)
     bufs = [torch.empty(tuple(maps[i].shape), dtype=gdtype, device=dev) if wanted[i] and present[i] else None for i in range(5)]
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    gp = torch.empty(3 + 6 * d.n_lights, dtype=torch.float32, device=dev) if kind == "fit" else None
+    gp = torch.empty(3 + 6 * d.n_lights, dtype=torch.float32, device=dev) if kind in _FIT_KINDS else None
     lib = N.lib()
     ws_bytes = getattr(lib, query)(ctypes.byref(d))
     if ws_bytes == 0:
@@ -1030,15 +1036,28 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
     docs/source/tutorials/06_advanced.rst:73-107 for the predicted material -- as a 0-dim tensor on the maps' device.  When a map
     requires grad and the evaluation qualifies (whole untiled maps of the batch, fp32 result, light / view parameters without
     gradients, every map with its own planes) loss and gradients come out of ONE kernel, pbr_cook_torrance_mse_step; otherwise
-    it is the differentiable evaluation followed by torch's MSE (same value to fp32 rounding, same gradients); so is every call with
-    view_type="point"."""
+    it is the differentiable evaluation followed by torch's MSE (same value to fp32 rounding, same gradients).  With view_type="point"
+    (`view_dir` is the camera's position) and ONE light the call is the light stack of one image -- the same quantity: one image, its own
+    clamp and encode, the mean over 3 B H W values -- and takes its one pass under `rendering_loss_mse_stack`'s conditions:
+    pbr_cook_torrance_camera_mse_stack_step, or pbr_cook_torrance_camera_mse_stack_fit_step when `view_dir`, `light` or `light_intensity`
+    requires grad; several lights summed into one image under the camera stay the composition."""
     maps = (albedo, normal, roughness, metallic, specular)
     params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
     grad_maps = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in maps)
     grad_other = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in params + (target,))
     B = albedo.shape[0] if albedo.dim() == 4 else 1
     shared = B > 1 and any(_shared_by_batch(t, B) for t in maps)
-    camera = _view_type(kwargs) == "point"                   # no fused camera step: the differentiable evaluation and torch's MSE
+    camera = _view_type(kwargs) == "point"
+    if camera and torch.is_grad_enabled() and isinstance(target, torch.Tensor) and tuple(target.shape) == tuple(albedo.shape[:-3]) + (3,) + tuple(albedo.shape[-2:]):
+        # one light: the L = 1 stack step (or fit step); several lights summed into one image have no fused camera form
+        try:
+            one_light = _stack_lights(params[1], params[2]) == (1, 1)
+        except (ValueError, TypeError, AttributeError, RuntimeError):
+            one_light = False                                # whatever is wrong with the lights is the evaluation's to say
+        route = _camera_stack_route(maps, params, target, kwargs) if one_light else None
+        loss = _camera_loss_step(route, maps, params, target, kwargs) if route is not None else None
+        if loss is not None:
+            return loss
     if grad_maps and not grad_other and _plain_kwargs(kwargs, _STEP_EXCLUDED) and not shared and albedo.is_cuda and not camera:
         # tiled maps (tile=n: MaterialBase.tile fused) take the one pass too -- the repeat-inner kernel leaves map-sized gradients -- where
         # the library serves them (one light, map rows of whole 4-texel groups); otherwise the three steps below
@@ -1054,7 +1073,8 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
 # ------------------------------------------------------------------ light stacks: L images, one per light, out of one pass over the maps
 # An extension over the reference (csrc/ct_stack.hip): a capture for SVBRDF fitting is a stack of photographs from ONE camera position with the
 # light moved between the shots; image l of the stack is what `cook_torrance` gives for light l alone, and the loss is the MSE over all of them.
-STACK_LAUNCHES = {"cook_torrance_stack": 0, "mse_stack_step": 0, "mse_stack_fit_step": 0}       # calls of the stack entry points (the tests count launches)
+STACK_LAUNCHES = {"cook_torrance_stack": 0, "mse_stack_step": 0, "mse_stack_fit_step": 0,       # calls of the stack entry points (the tests count launches)
+                  "camera_stack": 0, "camera_mse_stack_step": 0, "camera_mse_stack_fit_step": 0}     # ... and of their forms under the perspective camera
 
 
 def _stack_lights(light, light_intensity) -> Tuple[int, int]:
@@ -1085,24 +1105,25 @@ def cook_torrance_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], ro
     [1,3] for all lights or [L,3]; image l is exactly `cook_torrance(..., light=light[l], light_intensity=light_intensity[l])`.  Returns
     [L,3,H,W], or [B,L,3,H,W] for batched maps, float32.  ONE launch (pbr_cook_torrance_stack: maps read and decoded once, the
     light-independent terms formed once per pixel) when nothing requires grad and the maps are whole and untiled; otherwise -- gradients, `tile`,
-    `out_dtype`, view_type="point" ... -- a torch.stack of L `cook_torrance` calls, differentiable like them.  Other keyword arguments as for
-    `cook_torrance`."""
+    `out_dtype` ... -- a torch.stack of L `cook_torrance` calls, differentiable like them.  With view_type="point" (`view_dir` is the camera's
+    position) the one launch is pbr_cook_torrance_camera_stack, under the same conditions.  Other keyword arguments as for `cook_torrance`."""
     L, rows = _stack_lights(light, light_intensity)
     if kwargs.get("out") is not None:
         raise ValueError("cook_torrance_stack allocates its result: out= is not supported")
     maps = (albedo, normal, roughness, metallic, specular)
-    if (_view_type(kwargs) != "point" and _stack_plain(kwargs) and isinstance(albedo, torch.Tensor) and albedo.is_cuda and albedo.dim() in (3, 4) and albedo.numel() > 0
+    camera = _view_type(kwargs) == "point"
+    if (_stack_plain(kwargs) and isinstance(albedo, torch.Tensor) and albedo.is_cuda and albedo.dim() in (3, 4) and albedo.numel() > 0
             and not _needs_grad(*maps, view_dir, light, light_intensity)):
         kw = {k: v for k, v in kwargs.items() if k in ("light_type", "light_size", "albedo_is_srgb", "specular_is_srgb", "return_srgb",
-                                                       "convert_to_diffuse_specular", "schedule", "tuning")}
+                                                       "convert_to_diffuse_specular", "schedule", "tuning", "view_type")}
         B = 1 if albedo.dim() == 3 else albedo.shape[0]
         stack = torch.empty((B, L, 3) + tuple(albedo.shape[-2:]), dtype=torch.float32, device=albedo.device)
         # the plan describes ONE image per material; as `out` it gets the head of the stack's block -- contiguous, so the descriptor carries the
         # block's address and no strides -- and the stack's entry point spaces the materials 3 L planes apart itself
         plan = plan_cook_torrance(albedo, normal, roughness, metallic, specular, view_dir=view_dir, light=light, light_intensity=light_intensity,
                                   out=stack.view(B * L, 3, *stack.shape[-2:])[:B], **kw)
-        launch(plan.device, N.lib().pbr_cook_torrance_stack, ctypes.byref(plan.desc))
-        STACK_LAUNCHES["cook_torrance_stack"] += 1
+        launch(plan.device, N.lib().pbr_cook_torrance_camera_stack if camera else N.lib().pbr_cook_torrance_stack, ctypes.byref(plan.desc))
+        STACK_LAUNCHES["camera_stack" if camera else "cook_torrance_stack"] += 1
         return stack[0] if albedo.dim() == 3 else stack
     lt = (light if isinstance(light, torch.Tensor) else torch.as_tensor(light, dtype=torch.float32)).reshape(-1, 3)
     it = (light_intensity if isinstance(light_intensity, torch.Tensor) else torch.as_tensor(light_intensity, dtype=torch.float32)).reshape(-1, 3)
@@ -1147,21 +1168,66 @@ class _MseStackFitFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss):
-        grads, gp = _kept_step(ctx)
-        _scale_step_gradients(grads, grad_loss)
-        k = grad_loss.detach().to(gp.device, torch.float32).reshape(1).contiguous()
-        launch(gp.device, N.lib().pbr_scale_by_device_scalar, gp.data_ptr(), gp.numel(), N.F32, k.data_ptr())
-        L = (gp.numel() - 3) // 6
-        need = [ctx.needs_input_grad[5 + i] for i in range(3)]
-        host = gp.cpu() if any(n and not p.is_cuda for n, p in zip(need, ctx.params)) else None      # ONE copy for every parameter held on the CPU
+        return _fit_step_backward(ctx, grad_loss)
 
-        def part(i, first, rows):
-            if not need[i]:
-                return None
-            g = (gp if ctx.params[i].is_cuda else host)[first:first + 3 * rows]
-            return _param_grad(g if i == 0 else g.reshape(rows, 3), ctx.params[i], L if i == 2 else 1)
-        pgrads = [part(0, 0, 1), part(1, 3, L), part(2, 3 + 3 * L, L)]
-        return (*grads, *pgrads, None, None)
+
+def _fit_step_backward(ctx, grad_loss):
+    """What a fit step's backward returns (_MseStackFitFn, _CameraStackFitFn): the kept map gradients and the block [view | lights L x 3 |
+    intensities L x 3], both scaled by the upstream gradient on the device, the block sliced and shaped like the parameters.  Element 0:3 is
+    handed back as the entry point left it: the view direction's gradient behind its F.normalize Jacobian, or the camera position's own."""
+    grads, gp = _kept_step(ctx)
+    _scale_step_gradients(grads, grad_loss)
+    k = grad_loss.detach().to(gp.device, torch.float32).reshape(1).contiguous()
+    launch(gp.device, N.lib().pbr_scale_by_device_scalar, gp.data_ptr(), gp.numel(), N.F32, k.data_ptr())
+    L = (gp.numel() - 3) // 6
+    need = [ctx.needs_input_grad[5 + i] for i in range(3)]
+    host = gp.cpu() if any(n and not p.is_cuda for n, p in zip(need, ctx.params)) else None      # ONE copy for every parameter held on the CPU
+
+    def part(i, first, rows):
+        if not need[i]:
+            return None
+        g = (gp if ctx.params[i].is_cuda else host)[first:first + 3 * rows]
+        return _param_grad(g if i == 0 else g.reshape(rows, 3), ctx.params[i], L if i == 2 else 1)
+    pgrads = [part(0, 0, 1), part(1, 3, L), part(2, 3 + 3 * L, L)]
+    return (*grads, *pgrads, None, None)
+
+
+class _CameraStackStepFn(torch.autograd.Function):
+    """_MseStackStepFn under the perspective camera (view_type="point" in `kwargs`: `view_dir` is the camera's position): ONE kernel,
+    pbr_cook_torrance_camera_mse_stack_step, gives the loss over the L images and the map gradients summed over the lights."""
+
+    @staticmethod
+    def forward(ctx, albedo, normal, roughness, metallic, specular, targets, kwargs):
+        maps = (albedo, normal, roughness, metallic, specular)
+        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
+        bufs, _, loss = _launch_loss_step("camera_stack", _step_plan(maps, kwargs), maps, targets, wanted)
+        _keep_step(ctx, "camera_stack", maps, targets, kwargs, wanted, (bufs, None))
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        grads, _ = _kept_step(ctx)
+        _scale_step_gradients(grads, grad_loss)
+        return (*grads, None, None)
+
+
+class _CameraStackFitFn(torch.autograd.Function):
+    """_MseStackFitFn under the perspective camera: ONE kernel (pbr_cook_torrance_camera_mse_stack_fit_step) gives the loss, the map gradients
+    and the (3 + 6 L) gradients of the camera's position, the lights and the intensities.  The position's gradient is handed back as the
+    kernel summed it (the per-pixel normalisation is differentiated in the kernel; there is no F.normalize of the position).  Parameters on the
+    device are read there at every launch; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
+
+    @staticmethod
+    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs):
+        maps, params = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity)
+        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
+        bufs, gp, loss = _launch_loss_step("camera_fit", _step_plan(maps, kwargs, params), maps, targets, wanted)
+        _keep_step(ctx, "camera_fit", maps, targets, kwargs, wanted, (bufs, gp), params)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        return _fit_step_backward(ctx, grad_loss)
 
 
 def _stack_route(maps, params, targets, kwargs, on_device=None):
@@ -1181,6 +1247,38 @@ def _stack_route(maps, params, targets, kwargs, on_device=None):
     return "step" if _needs_grad(*maps) else None
 
 
+def _camera_stack_route(maps, params, targets, kwargs, on_device=None):
+    """_stack_route for view_type="point" (`view_dir` is the camera's position): "fit" (_CameraStackFitFn: the position, a light or an
+    intensity requires grad, with or without the maps), "step" (_CameraStackStepFn: only maps do) or None (the composition: the stack of
+    camera renders and torch's MSE).  The same conditions -- plain arguments, untiled maps, every map with its own planes, targets that need
+    no grad, maps on a ROCm device (`on_device`: None = ask the albedo) -- and the view type itself.  No rule by L: both steps were ahead of the
+    composition at every L measured, the single photograph included (profiles/camera_stack_probe.json)."""
+    if _view_type(kwargs) != "point":
+        return None
+    albedo = maps[0]
+    B = albedo.shape[0] if albedo.dim() == 4 else 1
+    shared = B > 1 and any(_shared_by_batch(t, B) for t in maps)
+    if on_device is None:
+        on_device = albedo.is_cuda
+    if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets):
+        return None
+    if _needs_grad(*params):
+        return "fit"
+    return "step" if _needs_grad(*maps) else None
+
+
+def _camera_loss_step(route, maps, params, targets, kwargs):
+    """The fused camera step `_camera_stack_route` chose, or None when the library does not serve the descriptor as one pass."""
+    kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED}
+    try:
+        if route == "fit":
+            kw = {k: v for k, v in kw.items() if k not in _PARAM_KEYS}
+            return _CameraStackFitFn.apply(*maps, *params, targets, kw)
+        return _CameraStackStepFn.apply(*maps, targets, kw)
+    except _StepNotServed:
+        return None
+
+
 def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], roughness: torch.Tensor,
                              metallic: Optional[torch.Tensor] = None, specular: Optional[torch.Tensor] = None, *,
                              targets: torch.Tensor, **kwargs) -> torch.Tensor:
@@ -1190,8 +1288,10 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
     arguments, every map with its own planes, on a ROCm device -- and untiled maps: pbr_cook_torrance_mse_stack_step when only maps require
     grad, pbr_cook_torrance_mse_stack_fit_step when `view_dir`, `light` or `light_intensity` does (lights, per-shot intensities or the camera
     axis being fitted, with or without the maps: their gradients come out of the same pass; a [3] / [1,3] intensity owns the sum over the
-    lights, a parameter on the CPU receives a CPU gradient).  Every other case (tiled maps, maps shared by the batch, targets that require grad,
-    no gradients wanted, view_type="point") is the stack followed by torch's MSE: same value to fp32 rounding, same gradients."""
+    lights, a parameter on the CPU receives a CPU gradient).  With view_type="point" (`view_dir` is the camera's position) the two passes are
+    pbr_cook_torrance_camera_mse_stack_step and pbr_cook_torrance_camera_mse_stack_fit_step under the same conditions, and the view's
+    gradient is the position's.  Every other case (tiled maps, maps shared by the batch, targets that require grad, no gradients wanted) is
+    the stack followed by torch's MSE: same value to fp32 rounding, same gradients."""
     L, _ = _stack_lights(kwargs.get("light"), kwargs.get("light_intensity"))
     if not isinstance(albedo, torch.Tensor) or albedo.dim() not in (3, 4):
         raise ValueError("albedo must be [3,H,W] or [B,3,H,W]")
@@ -1202,6 +1302,11 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
         raise ValueError("targets must be the stack %s, got %s" % (want, tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets)))
     maps = (albedo, normal, roughness, metallic, specular)
     params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
+    if _view_type(kwargs) == "point":
+        route = _camera_stack_route(maps, params, targets, kwargs)
+        loss = _camera_loss_step(route, maps, params, targets, kwargs) if route is not None else None
+        if loss is not None:
+            return loss
     route = _stack_route(maps, params, targets, kwargs)
     if route is not None:
         kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED}

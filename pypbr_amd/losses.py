@@ -79,7 +79,10 @@ class MultiLightRenderingLoss(nn.Module):
     the one-pass form (functional.rendering_loss_mse_stack -> pbr_cook_torrance_mse_stack_step), follows RenderingLoss's rules.
     With photographs as `ground_truth`, `lights`, `light_intensities` or `view_dir` that require grad -- plain tensors, or nn.Parameters,
     which nn.Module registers on assignment so that `loss.parameters()` yields them -- are fitted in the same pass
-    (pbr_cook_torrance_mse_stack_fit_step); through a differentiably rendered ground truth they take the composition."""
+    (pbr_cook_torrance_mse_stack_fit_step); through a differentiably rendered ground truth they take the composition.  With
+    view_type='point' (`view_dir` is the camera's position) the one launch and the two passes are the camera's own
+    (pbr_cook_torrance_camera_stack, pbr_cook_torrance_camera_mse_stack_step, pbr_cook_torrance_camera_mse_stack_fit_step), under the same
+    rules; the gradient `view_dir` receives is the position's."""
 
     def __init__(self, light_type='point', view_dir=torch.tensor([0.0, 0.0, 1.0]), lights=torch.tensor([[0.1, 0.1, 1.0]]),
                  light_intensities=torch.tensor([1.0, 1.0, 1.0]), light_size=None, view_type='directional'):
