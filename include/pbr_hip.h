@@ -375,6 +375,28 @@ int pbr_cook_torrance_camera_mse_stack_step(const pbr_render_desc *desc, const v
 size_t pbr_camera_mse_stack_fit_workspace_bytes(const pbr_render_desc *desc);
 int pbr_cook_torrance_camera_mse_stack_fit_step(const pbr_render_desc *desc, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
                                                 void *g_metallic, void *g_specular, void *g_params, void *loss, void *workspace, void *stream);
+/*
+ * Light stacks with one camera position PER SHOT (a handheld capture: the camera moves with the flash): the three camera-stack calls with the
+ * L positions handed over beside the descriptor -- `desc->view_dir` and the device_params block's view are not read.  Image l of the stack is
+ * what pbr_cook_torrance_camera gives for position l and light l alone: its own view vectors F.normalize(C_l - P(y, x)), its own clamp, its own
+ * encode.  Exactly one of `cameras_host` / `cameras_device` is non-NULL: `cameras_host` is float[L][3] in host memory, read now (the values
+ * travel in the kernel arguments); `cameras_device` is float[L][3] fp32 in DEVICE memory, read by the kernel when it runs -- no read-back,
+ * nothing baked in, so a captured graph sees the positions' current values at every replay.  Lights and intensities: the descriptor or its
+ * device_params block, as everywhere.  Stack, `targets`, *loss, the g_* and the step's workspace are the camera stack's; `g_params` is 9 L
+ * floats of DEVICE memory, [d/d cameras (L x 3) | d/d lights (L x 3) | d/d intensities (L x 3)]: each position's gradient the sum over pixels
+ * of (I - v v^T) / |C_l - P| g_v, applied per pixel before the sum; directional lights behind their F.normalize Jacobian.  The fit step's
+ * workspace is pbr_view_mse_stack_fit_workspace_bytes(desc): the camera fit layout with rows of 9 L floats (0 where the call does not serve
+ * the descriptor).  64 + 12 L bytes per pixel like the other stacks; one pass over the maps, deterministic.
+ * Before any launch: the codes of the camera-stack calls, and both or neither of the two camera pointers PBR_ERR_NULL_MAP.
+ */
+int pbr_cook_torrance_view_stack(const pbr_render_desc *desc, const float *cameras_host, const void *cameras_device, void *stream);
+int pbr_cook_torrance_view_mse_stack_step(const pbr_render_desc *desc, const float *cameras_host, const void *cameras_device, const void *targets,
+                                          void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic, void *g_specular, void *loss,
+                                          void *workspace, void *stream);
+size_t pbr_view_mse_stack_fit_workspace_bytes(const pbr_render_desc *desc);
+int pbr_cook_torrance_view_mse_stack_fit_step(const pbr_render_desc *desc, const float *cameras_host, const void *cameras_device, const void *targets,
+                                              void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic, void *g_specular,
+                                              void *g_params, void *loss, void *workspace, void *stream);
 /* ABI 5: view / light / intensity from DEVICE memory.  `view_dir` [3], `lights` [n_lights][3], `intensities` [intensity_rows][3] with
  * intensity_rows = 1 (one intensity for every light) or n_lights: fp32 device pointers; a NULL pointer takes that parameter from the descriptor
  * (d->view_dir / d->lights / d->intensities: host values), so only what lives on the device needs to be there.  Writes `block` (pbr_device_params_bytes() bytes,

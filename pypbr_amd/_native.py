@@ -54,6 +54,8 @@ EXPORTS = (
     "pbr_cook_torrance_camera", "pbr_camera_backward_workspace_bytes", "pbr_cook_torrance_camera_backward",
     "pbr_cook_torrance_camera_stack", "pbr_cook_torrance_camera_mse_stack_step",
     "pbr_camera_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_camera_mse_stack_fit_step",
+    "pbr_cook_torrance_view_stack", "pbr_cook_torrance_view_mse_stack_step",
+    "pbr_view_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_view_mse_stack_fit_step",
 )
 
 
@@ -208,6 +210,16 @@ def lib():
     L.pbr_camera_mse_stack_fit_workspace_bytes.restype = ctypes.c_size_t
     L.pbr_cook_torrance_camera_mse_stack_fit_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pbr_cook_torrance_camera_mse_stack_fit_step.restype = ctypes.c_int
+    # one camera position per shot: (desc, cameras_host float[L][3] | NULL, cameras_device | NULL, ...) -- exactly one of the two
+    fp = ctypes.POINTER(ctypes.c_float)
+    L.pbr_cook_torrance_view_stack.argtypes = [ctypes.POINTER(RenderDesc), fp, vp, vp]
+    L.pbr_cook_torrance_view_stack.restype = ctypes.c_int
+    L.pbr_cook_torrance_view_mse_stack_step.argtypes = [ctypes.POINTER(RenderDesc), fp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pbr_cook_torrance_view_mse_stack_step.restype = ctypes.c_int
+    L.pbr_view_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
+    L.pbr_view_mse_stack_fit_workspace_bytes.restype = ctypes.c_size_t
+    L.pbr_cook_torrance_view_mse_stack_fit_step.argtypes = [ctypes.POINTER(RenderDesc), fp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pbr_cook_torrance_view_mse_stack_fit_step.restype = ctypes.c_int
     L.pbr_cook_torrance_mse_stack_step.argtypes =[ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pbr_cook_torrance_mse_stack_step.restype = ctypes.c_int
     L.pbr_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]

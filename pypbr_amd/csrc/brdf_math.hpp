@@ -248,6 +248,18 @@ __device__ __forceinline__ void pixel_terms(const Vec3T<R> &n, const VT &V, R ro
     for (int c = 0; c < 3; ++c) { t.kb[c] = base[c] * s; t.f0[c] = f0[c]; }
 }
 
+// The six terms of a PixelTermsT that depend on the view, formed again for another view of the same pixel (ct_view_stack.hip: one camera
+// per shot of a stack): pixel_terms' own statements for those fields, so a pixel under view V holds the bits pixel_terms(..., V, ...) gives.
+template <class R, class VT>
+__device__ __forceinline__ void view_terms(PixelTermsT<R> &t, const VT &V) {
+    t.ndv_raw = dotv(t.n, V);
+    t.ndv = clamp01(t.ndv_raw);
+    t.ndv4 = t.ndv * 4.0f;
+    t.dv = fma_(t.ndv, t.omk, t.kk);
+    t.a2ndv = t.a2 * t.ndv;
+    t.a2ndv_pi = (t.a2 * kInvPi) * t.ndv;
+}
+
 // GGX denominator (:213-217), cancellation-free: a2 + (1-a2) sin^2(N,H) when N.H > 0, else 1, with
 // sin^2 = |h - (N.h) N|^2 / |h|^2 (N unit).  Rounding errors of N.h and of |N| move the projection ALONG N, i.e.
 // orthogonally to it, so they enter sin^2 only to second order; 9 ops against 12 for the cross product.

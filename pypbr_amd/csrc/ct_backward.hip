@@ -192,6 +192,72 @@ int param_grad_finish(const pbr_render_desc *d, const float *rows, int n_rows, u
     return launch_status();
 }
 
+// ------------------------------------------------------------------ rows of any length (ct_view_stack.hip: 9 L floats, one camera per shot)
+// param_grad_finish's sibling: a row is n_vec 3-vectors, of which vectors [first_light, first_light + L) are the lights' -- directional ones
+// pass through F.normalize's Jacobian as above -- and every other vector is only summed (camera positions: their Jacobian depends on the pixel
+// and was applied before the sum; intensities).  Stage 1 is param_grad_stage_kernel itself: it takes the row length as an argument.
+struct RowsFinishArgs {
+    const double *stage; float *out; int32_t n_rows, n_vec, first_light, n_lights, light_type;
+    float lights[PBR_MAX_LIGHTS][3];
+    uint64_t dev;
+};
+__global__ __launch_bounds__(256) void param_rows_finish_kernel(const RowsFinishArgs a) {
+    const int vec = blockIdx.x, n_param = 3 * a.n_vec;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int r = threadIdx.x; r < a.n_rows; r += 256) {
+        const double *row = a.stage + (int64_t)r * n_param + 3 * vec;
+        s[0] += row[0]; s[1] += row[1]; s[2] += row[2];
+    }
+    __shared__ double red[3][256];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) red[j][threadIdx.x] = s[j];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    double g[3] = {red[0][0], red[1][0], red[2][0]};
+    const int light = vec - a.first_light;
+    if (light >= 0 && light < a.n_lights && a.light_type == PBR_LIGHT_DIRECTIONAL) {
+        float x[3];
+        for (int j = 0; j < 3; ++j) x[j] = a.dev ? reinterpret_cast<const DevParams *>(a.dev)->raw_lights[light][j] : a.lights[light][j];
+        const double nrm = sqrt((double)x[0] * x[0] + (double)x[1] * x[1] + (double)x[2] * x[2]);
+        if (nrm > 1e-12) {
+            const double u[3] = {x[0] / nrm, x[1] / nrm, x[2] / nrm};
+            const double ug = u[0] * g[0] + u[1] * g[1] + u[2] * g[2];
+            for (int j = 0; j < 3; ++j) g[j] = (g[j] - u[j] * ug) / nrm;
+        } else {
+            for (int j = 0; j < 3; ++j) g[j] *= 1e12;
+        }
+    }
+    for (int j = 0; j < 3; ++j) a.out[3 * vec + j] = (float)g[j];
+}
+
+size_t param_rows_bytes_of(const pbr_render_desc *d, int n_param) {
+    const size_t rows = (size_t)max_tiles(d) * (size_t)n_param * sizeof(float);
+    return (rows + 7) & ~(size_t)7;
+}
+size_t param_stage_bytes_of(int n_param) { return (size_t)kParamStageRows * (size_t)n_param * sizeof(double); }
+
+int param_rows_finish(const pbr_render_desc *d, const float *rows, int n_rows, int n_vec, int first_light, uint64_t dev, float *out, hipStream_t st) {
+    RowsFinishArgs f;
+    std::memset(&f, 0, sizeof(f));
+    const int n_param = 3 * n_vec;
+    double *stage = reinterpret_cast<double *>(reinterpret_cast<char *>(const_cast<float *>(rows)) + param_rows_bytes_of(d, n_param));
+    hipLaunchKernelGGL(param_grad_stage_kernel, dim3(kParamStageRows), dim3(256), 0, st, rows, stage, n_rows, n_param);
+    f.stage = stage; f.out = out;
+    f.n_rows = kParamStageRows; f.n_vec = n_vec; f.first_light = first_light; f.n_lights = d->n_lights; f.light_type = d->light_type;
+    f.dev = dev;
+    for (int i = 0; i < d->n_lights; ++i)
+        for (int c = 0; c < 3; ++c) f.lights[i][c] = d->lights[i][c];
+    hipLaunchKernelGGL(param_rows_finish_kernel, dim3((unsigned)n_vec), dim3(256), 0, st, f);
+    return launch_status();
+}
+
 static int launch_backward(const pbr_render_desc *d, const void *grad_out, void *g_albedo, void *g_normal, void *g_roughness,
                            void *g_metallic, void *g_specular, void *g_params, void *workspace, void *stream) {
     const int rc = validate(d);

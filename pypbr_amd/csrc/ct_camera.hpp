@@ -25,6 +25,15 @@ static int camera_gate(const pbr_render_desc *d) {
 // A NaN light_size makes the grid, hence every view vector, NaN whatever the light type (ct_launch.hpp: nan_light_size is the point light's).
 static bool nan_grid(const pbr_render_desc *d) { return d->light_size != d->light_size; }
 
+// What the camera's loss steps (ct_camera_stack.hip, ct_view_stack.hip) ask before any launch: the loss steps' gate (valid descriptor, the caller's pointers, an fp32 result, untiled maps) and
+// what the camera adds to it -- no map size at all (camera_gate), no NaN grid whatever the light type.
+static int camera_step_gate(const pbr_render_desc *d, bool pointers_given) {
+    int rc = mse_gate(d, pointers_given, false);
+    if (rc == PBR_OK) rc = camera_gate(d);
+    if (rc != PBR_OK) return rc;
+    return nan_grid(d) ? PBR_ERR_UNSUPPORTED : PBR_OK;
+}
+
 // fill_args, with the view as the kernels read it here: the position as given (fill_args normalises it for the orthographic kernels)
 static void camera_args(const pbr_render_desc *d, int vec, KArgs &k, int block_log2) {
     fill_args(d, vec, k, block_log2);

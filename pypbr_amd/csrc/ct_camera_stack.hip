@@ -168,15 +168,6 @@ static LossStepFn pick_camera_stack_step(bool half_maps, int vec) {
     return vec == 2 ? cook_torrance_camera_mse_stack_step_kernel<L, W, 2, float, PGRAD> : cook_torrance_camera_mse_stack_step_kernel<L, W, 1, float, PGRAD>;
 }
 
-// What the two steps ask before any launch: the loss steps' gate (valid descriptor, the caller's pointers, an fp32 result, untiled maps) and
-// what the camera adds to it -- no map size at all (camera_gate), no NaN grid whatever the light type.
-static int camera_step_gate(const pbr_render_desc *d, bool pointers_given) {
-    int rc = mse_gate(d, pointers_given, false);
-    if (rc == PBR_OK) rc = camera_gate(d);
-    if (rc != PBR_OK) return rc;
-    return nan_grid(d) ? PBR_ERR_UNSUPPORTED : PBR_OK;
-}
-
 // launch_loss_step (ct_loss.hip) with the camera's kernel arguments: that launcher fills them itself (fill_args normalises the view), and
 // here the view must stay the position as given (camera_args).  Everything else is its statements: one-wave workgroups of `vec` pixels per
 // lane, contiguous target and gradient planes, scale = 2 / count, never more workgroups than the rows' size query promised.

@@ -328,6 +328,11 @@ int64_t max_tiles(const pbr_render_desc *d);
 size_t param_rows_bytes(const pbr_render_desc *d);
 size_t param_stage_bytes(const pbr_render_desc *d);
 int param_grad_finish(const pbr_render_desc *d, const float *rows, int n_rows, uint64_t dev, float *g_params, hipStream_t st, bool view_is_position = false);
+// ... and for rows of another length (ct_view_stack.hip: n_vec = 3 L 3-vectors, the lights' at first_light = L): the bytes of max_tiles rows of
+// n_param floats and of their stage sums, and rows -> out; vectors outside [first_light, first_light + L) are only summed
+size_t param_rows_bytes_of(const pbr_render_desc *d, int n_param);
+size_t param_stage_bytes_of(int n_param);
+int param_rows_finish(const pbr_render_desc *d, const float *rows, int n_rows, int n_vec, int first_light, uint64_t dev, float *out, hipStream_t st);
 
 // The repeat-inner kernels (cook_torrance_repeat_kernel, cook_torrance_repeat_backward_kernel) serve every tiled launch whose map rows hold a
 // 4-texel lane: the whole tiled image or a row band of it (a multi-GPU shard) of ANY height -- a band thinner than a period walks the window

@@ -881,15 +881,35 @@ _STEP_KINDS = {"step": ("pbr_cook_torrance_mse_step", "pbr_mse_step_workspace_by
                "stack": ("pbr_cook_torrance_mse_stack_step", "pbr_mse_step_workspace_bytes"),
                "fit": ("pbr_cook_torrance_mse_stack_fit_step", "pbr_mse_stack_fit_workspace_bytes"),
                "camera_stack": ("pbr_cook_torrance_camera_mse_stack_step", "pbr_mse_step_workspace_bytes"),
-               "camera_fit": ("pbr_cook_torrance_camera_mse_stack_fit_step", "pbr_camera_mse_stack_fit_workspace_bytes")}
-_FIT_KINDS = ("fit", "camera_fit")
+               "camera_fit": ("pbr_cook_torrance_camera_mse_stack_fit_step", "pbr_camera_mse_stack_fit_workspace_bytes"),
+               "view_stack": ("pbr_cook_torrance_view_mse_stack_step", "pbr_mse_step_workspace_bytes"),
+               "view_fit": ("pbr_cook_torrance_view_mse_stack_fit_step", "pbr_view_mse_stack_fit_workspace_bytes")}
+_FIT_KINDS = ("fit", "camera_fit", "view_fit")
+_VIEW_KINDS = ("view_stack", "view_fit")          # one camera position per shot: the positions travel beside the plan, and a fit row is 9 L floats
+_POINT_KINDS = ("camera_stack", "camera_fit") + _VIEW_KINDS
 
 
-def _launch_loss_step(kind, plan, maps, targets, wanted):
+def _camera_rows(view_dir, L, device):
+    """The L camera positions of a view-stack launch as the entry points take them: (host float[3 L], None) -- read now, at every call -- or
+    (None, contiguous float32 [L,3] tensor on `device`) for positions that live on a ROCm device: the kernel reads them when it runs, nothing
+    is copied to the host."""
+    if isinstance(view_dir, torch.Tensor) and view_dir.is_cuda and DEVICE_PARAMETERS:
+        c = view_dir.detach().to(device, torch.float32).reshape(L, 3).contiguous()
+        if c.data_ptr() != view_dir.data_ptr():
+            _warn_parameter_copy(view_dir, device)
+        return None, c
+    rows = _host_vec3(view_dir, rows=-1)
+    if len(rows) != L:
+        raise ValueError("view_dir holds %d positions for %d shots" % (len(rows), L))
+    return (ctypes.c_float * (3 * L))(*[x for r in rows for x in r]), None
+
+
+def _launch_loss_step(kind, plan, maps, targets, wanted, cameras=None):
     """ONE launch of a loss step -> (gradient buffers | None per map, parameter gradients [3 + 6 L] | None, loss).  Raises _StepNotServed
-    before anything is launched when the library does not serve the descriptor as one pass (e.g. tiled maps with several lights)."""
+    before anything is launched when the library does not serve the descriptor as one pass (e.g. tiled maps with several lights).
+    `cameras`: the view kinds' [L,3] positions (the plan's own view is not read); their parameter gradients are [9 L]."""
     entry, query = _STEP_KINDS[kind]
-    if kind.startswith("camera") != (plan.view_type == "point"):
+    if (kind in _POINT_KINDS) != (plan.view_type == "point"):
         raise ValueError("loss step %r does not take a plan with view_type=%r" % (kind, plan.view_type))
     d = plan.desc
     dev = plan.device                                       # the maps' device: targets handed over on the CPU, or on another GPU, are brought here
@@ -901,17 +921,34 @@ def _launch_loss_step(kind, plan, maps, targets, wanted):
     # it -- autograd takes ownership of such a gradient instead of cloning it (a 4096^2 fp16 albedo: 73 us per step)
     bufs = [torch.empty(tuple(maps[i].shape), dtype=gdtype, device=dev) if wanted[i] and present[i] else None for i in range(5)]
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    gp = torch.empty(3 + 6 * d.n_lights, dtype=torch.float32, device=dev) if kind in _FIT_KINDS else None
+    gp = torch.empty((9 if kind in _VIEW_KINDS else 6) * d.n_lights + (0 if kind in _VIEW_KINDS else 3), dtype=torch.float32,
+                     device=dev) if kind in _FIT_KINDS else None
+    where = ()
+    if kind in _VIEW_KINDS:
+        cam_host, cam_dev = _camera_rows(cameras, d.n_lights, dev)
+        where = (cam_host, ptr(cam_dev))
     lib = N.lib()
     ws_bytes = getattr(lib, query)(ctypes.byref(d))
     if ws_bytes == 0:
         raise _StepNotServed()
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev)      # at least the bytes asked for, 8-byte aligned
-    launch(dev, getattr(lib, entry), ctypes.byref(d), tgt.data_ptr(), *[ptr(b) for b in bufs], *([] if gp is None else [gp.data_ptr()]),
+    launch(dev, getattr(lib, entry), ctypes.byref(d), *where, tgt.data_ptr(), *[ptr(b) for b in bufs], *([] if gp is None else [gp.data_ptr()]),
            loss.data_ptr(), ws.data_ptr())
     if kind != "step":
         STACK_LAUNCHES[entry[len("pbr_cook_torrance_"):]] += 1
     return bufs, gp, loss
+
+
+_NO_VIEW = (0.0, 0.0, 1.0)      # the view of a view-stack plan: never read (the positions come beside the descriptor)
+
+
+def _plan_and_launch(kind, maps, kwargs, params, targets, wanted):
+    """_step_plan and _launch_loss_step for any kind.  The view kinds plan with a placeholder view and hand `params[0]`, the [L,3] positions,
+    to the launch."""
+    if kind in _VIEW_KINDS:
+        plan = _step_plan(maps, kwargs, (_NO_VIEW, params[1], params[2]))
+        return _launch_loss_step(kind, plan, maps, targets, wanted, cameras=params[0])
+    return _launch_loss_step(kind, _step_plan(maps, kwargs, params), maps, targets, wanted)
 
 
 def _keep_step(ctx, kind, maps, targets, kwargs, wanted, kept, params=None):
@@ -931,7 +968,7 @@ def _kept_step(ctx):
     if kept is None:
         it = iter(saved[:-1])
         maps = [next(it) if p else None for p in ctx.present]
-        kept = _launch_loss_step(ctx.kind, _step_plan(maps, ctx.kwargs, ctx.params), maps, saved[-1], ctx.wanted)[:2]
+        kept = _plan_and_launch(ctx.kind, maps, ctx.kwargs, ctx.params, saved[-1], ctx.wanted)[:2]
     return kept
 
 
@@ -1074,7 +1111,8 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
 # An extension over the reference (csrc/ct_stack.hip): a capture for SVBRDF fitting is a stack of photographs from ONE camera position with the
 # light moved between the shots; image l of the stack is what `cook_torrance` gives for light l alone, and the loss is the MSE over all of them.
 STACK_LAUNCHES = {"cook_torrance_stack": 0, "mse_stack_step": 0, "mse_stack_fit_step": 0,       # calls of the stack entry points (the tests count launches)
-                  "camera_stack": 0, "camera_mse_stack_step": 0, "camera_mse_stack_fit_step": 0}     # ... and of their forms under the perspective camera
+                  "camera_stack": 0, "camera_mse_stack_step": 0, "camera_mse_stack_fit_step": 0,     # ... and of their forms under the perspective camera
+                  "view_stack": 0, "view_mse_stack_step": 0, "view_mse_stack_fit_step": 0}            # ... with one camera position per shot
 
 
 def _stack_lights(light, light_intensity) -> Tuple[int, int]:
@@ -1093,6 +1131,22 @@ def _stack_lights(light, light_intensity) -> Tuple[int, int]:
     return L, R
 
 
+def _stack_views(view_dir, L: int) -> int:
+    """Rows of a stack's `view_dir`, by element count, from shapes alone: 1 (3 values: one view for all shots) or L (3 L values: one per shot;
+    for L = 1, [1,3] and [3] are the same thing).  Raises ValueError for anything else."""
+    n = view_dir.numel() if isinstance(view_dir, torch.Tensor) else torch.as_tensor(view_dir, dtype=torch.float32).numel()
+    if n == 3:
+        return 1
+    if n == 3 * L:
+        return L
+    raise ValueError("view_dir must be [3] (one view for all %d shots) or [L,3] = [%d,3] (one per shot), got %d values" % (L, L, n))
+
+
+def _view_rows(view_dir):
+    """`view_dir` [L,3] as something row l can be taken of (the composition hands row l to call l; a tensor keeps its graph)."""
+    return (view_dir if isinstance(view_dir, torch.Tensor) else torch.as_tensor(view_dir, dtype=torch.float32)).reshape(-1, 3)
+
+
 def _stack_plain(kw) -> bool:
     """The keyword arguments of a call that pbr_cook_torrance_stack / pbr_cook_torrance_mse_stack_step serve: whole untiled maps, a fresh fp32 result."""
     return _plain_kwargs(kw, _STACK_EXCLUDED)
@@ -1106,29 +1160,39 @@ def cook_torrance_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], ro
     [L,3,H,W], or [B,L,3,H,W] for batched maps, float32.  ONE launch (pbr_cook_torrance_stack: maps read and decoded once, the
     light-independent terms formed once per pixel) when nothing requires grad and the maps are whole and untiled; otherwise -- gradients, `tile`,
     `out_dtype` ... -- a torch.stack of L `cook_torrance` calls, differentiable like them.  With view_type="point" (`view_dir` is the camera's
-    position) the one launch is pbr_cook_torrance_camera_stack, under the same conditions.  Other keyword arguments as for `cook_torrance`."""
+    position) the one launch is pbr_cook_torrance_camera_stack, under the same conditions.  `view_dir` may also be [L,3], one view per shot
+    (the rule is by element count: 3 values are one view for all shots): with view_type="point" one camera position per shot -- a handheld
+    capture, camera and flash moving together -- and image l is `cook_torrance(view_dir=view_dir[l], light=light[l], ...)`, from ONE launch of
+    pbr_cook_torrance_view_stack under the same conditions; with view_type="directional" one orthographic direction per shot, which has no
+    kernel of its own and is always the torch.stack of L calls.  Other keyword arguments as for `cook_torrance`."""
     L, rows = _stack_lights(light, light_intensity)
+    per_shot = _stack_views(view_dir, L) > 1
     if kwargs.get("out") is not None:
         raise ValueError("cook_torrance_stack allocates its result: out= is not supported")
     maps = (albedo, normal, roughness, metallic, specular)
     camera = _view_type(kwargs) == "point"
     if (_stack_plain(kwargs) and isinstance(albedo, torch.Tensor) and albedo.is_cuda and albedo.dim() in (3, 4) and albedo.numel() > 0
-            and not _needs_grad(*maps, view_dir, light, light_intensity)):
+            and not _needs_grad(*maps, view_dir, light, light_intensity) and (camera or not per_shot)):
         kw = {k: v for k, v in kwargs.items() if k in ("light_type", "light_size", "albedo_is_srgb", "specular_is_srgb", "return_srgb",
                                                        "convert_to_diffuse_specular", "schedule", "tuning", "view_type")}
         B = 1 if albedo.dim() == 3 else albedo.shape[0]
         stack = torch.empty((B, L, 3) + tuple(albedo.shape[-2:]), dtype=torch.float32, device=albedo.device)
         # the plan describes ONE image per material; as `out` it gets the head of the stack's block -- contiguous, so the descriptor carries the
         # block's address and no strides -- and the stack's entry point spaces the materials 3 L planes apart itself
-        plan = plan_cook_torrance(albedo, normal, roughness, metallic, specular, view_dir=view_dir, light=light, light_intensity=light_intensity,
-                                  out=stack.view(B * L, 3, *stack.shape[-2:])[:B], **kw)
-        launch(plan.device, N.lib().pbr_cook_torrance_camera_stack if camera else N.lib().pbr_cook_torrance_stack, ctypes.byref(plan.desc))
-        STACK_LAUNCHES["camera_stack" if camera else "cook_torrance_stack"] += 1
+        plan = plan_cook_torrance(albedo, normal, roughness, metallic, specular, view_dir=_NO_VIEW if per_shot else view_dir, light=light,
+                                  light_intensity=light_intensity, out=stack.view(B * L, 3, *stack.shape[-2:])[:B], **kw)
+        if per_shot:
+            cam_host, cam_dev = _camera_rows(view_dir, L, plan.device)
+            launch(plan.device, N.lib().pbr_cook_torrance_view_stack, ctypes.byref(plan.desc), cam_host, ptr(cam_dev))
+        else:
+            launch(plan.device, N.lib().pbr_cook_torrance_camera_stack if camera else N.lib().pbr_cook_torrance_stack, ctypes.byref(plan.desc))
+        STACK_LAUNCHES["view_stack" if per_shot else "camera_stack" if camera else "cook_torrance_stack"] += 1
         return stack[0] if albedo.dim() == 3 else stack
     lt = (light if isinstance(light, torch.Tensor) else torch.as_tensor(light, dtype=torch.float32)).reshape(-1, 3)
     it = (light_intensity if isinstance(light_intensity, torch.Tensor) else torch.as_tensor(light_intensity, dtype=torch.float32)).reshape(-1, 3)
-    images = [cook_torrance(albedo, normal, roughness, metallic, specular, view_dir=view_dir, light=lt[l], light_intensity=it[l if rows > 1 else 0],
-                            **kwargs) for l in range(L)]
+    vt = _view_rows(view_dir) if per_shot else None
+    images = [cook_torrance(albedo, normal, roughness, metallic, specular, view_dir=vt[l] if per_shot else view_dir, light=lt[l],
+                            light_intensity=it[l if rows > 1 else 0], **kwargs) for l in range(L)]
     return torch.stack(images, dim=-4)
 
 
@@ -1172,14 +1236,16 @@ class _MseStackFitFn(torch.autograd.Function):
 
 
 def _fit_step_backward(ctx, grad_loss):
-    """What a fit step's backward returns (_MseStackFitFn, _CameraStackFitFn): the kept map gradients and the block [view | lights L x 3 |
-    intensities L x 3], both scaled by the upstream gradient on the device, the block sliced and shaped like the parameters.  Element 0:3 is
-    handed back as the entry point left it: the view direction's gradient behind its F.normalize Jacobian, or the camera position's own."""
+    """What a fit step's backward returns (_MseStackFitFn, _CameraStackFitFn, _ViewStackFitFn): the kept map gradients and the block [view |
+    lights L x 3 | intensities L x 3], both scaled by the upstream gradient on the device, the block sliced and shaped like the parameters.
+    The first block -- 3 floats, or 3 L for the view kinds' per-shot positions -- is handed back as the entry point left it: the view
+    direction's gradient behind its F.normalize Jacobian, or the camera positions' own."""
     grads, gp = _kept_step(ctx)
     _scale_step_gradients(grads, grad_loss)
     k = grad_loss.detach().to(gp.device, torch.float32).reshape(1).contiguous()
     launch(gp.device, N.lib().pbr_scale_by_device_scalar, gp.data_ptr(), gp.numel(), N.F32, k.data_ptr())
-    L = (gp.numel() - 3) // 6
+    L = gp.numel() // 9 if ctx.kind in _VIEW_KINDS else (gp.numel() - 3) // 6
+    first = 3 * L if ctx.kind in _VIEW_KINDS else 3
     need = [ctx.needs_input_grad[5 + i] for i in range(3)]
     host = gp.cpu() if any(n and not p.is_cuda for n, p in zip(need, ctx.params)) else None      # ONE copy for every parameter held on the CPU
 
@@ -1188,7 +1254,7 @@ def _fit_step_backward(ctx, grad_loss):
             return None
         g = (gp if ctx.params[i].is_cuda else host)[first:first + 3 * rows]
         return _param_grad(g if i == 0 else g.reshape(rows, 3), ctx.params[i], L if i == 2 else 1)
-    pgrads = [part(0, 0, 1), part(1, 3, L), part(2, 3 + 3 * L, L)]
+    pgrads = [part(0, 0, first // 3), part(1, first, L), part(2, first + 3 * L, L)]
     return (*grads, *pgrads, None, None)
 
 
@@ -1223,6 +1289,44 @@ class _CameraStackFitFn(torch.autograd.Function):
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
         bufs, gp, loss = _launch_loss_step("camera_fit", _step_plan(maps, kwargs, params), maps, targets, wanted)
         _keep_step(ctx, "camera_fit", maps, targets, kwargs, wanted, (bufs, gp), params)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        return _fit_step_backward(ctx, grad_loss)
+
+
+class _ViewStackStepFn(torch.autograd.Function):
+    """_CameraStackStepFn with one camera position per shot (`view_dir` [L,3]): ONE kernel, pbr_cook_torrance_view_mse_stack_step, gives the
+    loss over the L images and the map gradients summed over the shots.  The positions, lights and intensities are inputs here (not
+    differentiated: that is _ViewStackFitFn) because the positions travel beside the plan."""
+
+    @staticmethod
+    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs):
+        maps, params = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity)
+        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
+        bufs, _, loss = _plan_and_launch("view_stack", maps, kwargs, params, targets, wanted)
+        _keep_step(ctx, "view_stack", maps, targets, kwargs, wanted, (bufs, None), params)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        grads, _ = _kept_step(ctx)
+        _scale_step_gradients(grads, grad_loss)
+        return (*grads, None, None, None, None, None)
+
+
+class _ViewStackFitFn(torch.autograd.Function):
+    """_CameraStackFitFn with one camera position per shot: ONE kernel (pbr_cook_torrance_view_mse_stack_fit_step) gives the loss, the map
+    gradients and the 9 L gradients of the L positions, the lights and the intensities.  Positions on the device are read there at every
+    launch; host positions are re-read at every call; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
+
+    @staticmethod
+    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs):
+        maps, params = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity)
+        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
+        bufs, gp, loss = _plan_and_launch("view_fit", maps, kwargs, params, targets, wanted)
+        _keep_step(ctx, "view_fit", maps, targets, kwargs, wanted, (bufs, gp), params)
         return loss
 
     @staticmethod
@@ -1267,6 +1371,23 @@ def _camera_stack_route(maps, params, targets, kwargs, on_device=None):
     return "step" if _needs_grad(*maps) else None
 
 
+def _view_stack_route(maps, params, targets, kwargs, on_device=None):
+    """_camera_stack_route for `view_dir` [L,3], one camera position per shot: "fit" (_ViewStackFitFn: the positions, a light or an intensity
+    requires grad, with or without the maps), "step" (_ViewStackStepFn: only maps do) or None (the composition: L camera renders and torch's
+    MSE).  The camera stack's conditions: view_type="point", plain arguments, untiled maps, every map with its own planes, targets that need
+    no grad, maps on a ROCm device (`on_device`: None = ask the albedo)."""
+    return _camera_stack_route(maps, params, targets, kwargs, on_device)
+
+
+def _view_loss_step(route, maps, params, targets, kwargs):
+    """The fused per-shot-camera step `_view_stack_route` chose, or None when the library does not serve the descriptor as one pass."""
+    kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED + _PARAM_KEYS}
+    try:
+        return (_ViewStackFitFn if route == "fit" else _ViewStackStepFn).apply(*maps, *params, targets, kw)
+    except _StepNotServed:
+        return None
+
+
 def _camera_loss_step(route, maps, params, targets, kwargs):
     """The fused camera step `_camera_stack_route` chose, or None when the library does not serve the descriptor as one pass."""
     kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED}
@@ -1290,9 +1411,12 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
     axis being fitted, with or without the maps: their gradients come out of the same pass; a [3] / [1,3] intensity owns the sum over the
     lights, a parameter on the CPU receives a CPU gradient).  With view_type="point" (`view_dir` is the camera's position) the two passes are
     pbr_cook_torrance_camera_mse_stack_step and pbr_cook_torrance_camera_mse_stack_fit_step under the same conditions, and the view's
-    gradient is the position's.  Every other case (tiled maps, maps shared by the batch, targets that require grad, no gradients wanted) is
-    the stack followed by torch's MSE: same value to fp32 rounding, same gradients."""
+    gradient is the position's.  `view_dir` [L,3] is one view per shot (`cook_torrance_stack`): with view_type="point" the two passes are
+    pbr_cook_torrance_view_mse_stack_step and pbr_cook_torrance_view_mse_stack_fit_step, and the positions' gradient comes back [L,3] like
+    the tensor passed; with view_type="directional" it is the composition.  Every other case (tiled maps, maps shared by the batch, targets
+    that require grad, no gradients wanted) is the stack followed by torch's MSE: same value to fp32 rounding, same gradients."""
     L, _ = _stack_lights(kwargs.get("light"), kwargs.get("light_intensity"))
+    per_shot = kwargs.get("view_dir") is not None and _stack_views(kwargs["view_dir"], L) > 1
     if not isinstance(albedo, torch.Tensor) or albedo.dim() not in (3, 4):
         raise ValueError("albedo must be [3,H,W] or [B,3,H,W]")
     ny, nx = tile_counts(kwargs.get("tile", 1))
@@ -1303,11 +1427,11 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
     maps = (albedo, normal, roughness, metallic, specular)
     params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
     if _view_type(kwargs) == "point":
-        route = _camera_stack_route(maps, params, targets, kwargs)
-        loss = _camera_loss_step(route, maps, params, targets, kwargs) if route is not None else None
+        route = (_view_stack_route if per_shot else _camera_stack_route)(maps, params, targets, kwargs)
+        loss = (_view_loss_step if per_shot else _camera_loss_step)(route, maps, params, targets, kwargs) if route is not None else None
         if loss is not None:
             return loss
-    route = _stack_route(maps, params, targets, kwargs)
+    route = None if per_shot else _stack_route(maps, params, targets, kwargs)      # one orthographic direction per shot: the composition
     if route is not None:
         kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED}
         try:

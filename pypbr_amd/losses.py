@@ -82,12 +82,15 @@ class MultiLightRenderingLoss(nn.Module):
     (pbr_cook_torrance_mse_stack_fit_step); through a differentiably rendered ground truth they take the composition.  With
     view_type='point' (`view_dir` is the camera's position) the one launch and the two passes are the camera's own
     (pbr_cook_torrance_camera_stack, pbr_cook_torrance_camera_mse_stack_step, pbr_cook_torrance_camera_mse_stack_fit_step), under the same
-    rules; the gradient `view_dir` receives is the position's."""
+    rules; the gradient `view_dir` receives is the position's.  `view_dir` [L,3] is one view per shot -- with view_type='point' a handheld
+    capture, the camera moving with the flash -- and reaches functional's per-shot routes (pbr_cook_torrance_view_stack,
+    pbr_cook_torrance_view_mse_stack_step, pbr_cook_torrance_view_mse_stack_fit_step); its gradient comes back [L,3]."""
 
     def __init__(self, light_type='point', view_dir=torch.tensor([0.0, 0.0, 1.0]), lights=torch.tensor([[0.1, 0.1, 1.0]]),
                  light_intensities=torch.tensor([1.0, 1.0, 1.0]), light_size=None, view_type='directional'):
         super().__init__()
         self.n_lights, self._rows = F_._stack_lights(lights, light_intensities)          # ValueError before any device work
+        self._views = F_._stack_views(view_dir, self.n_lights)                           # 1, or L: one view per shot (a handheld capture)
         self.brdf = CookTorranceBRDF(light_type=light_type, view_type=view_type)         # 'point': `view_dir` is the camera's position
         self.view_dir = view_dir
         self.lights = lights
@@ -118,7 +121,8 @@ class MultiLightRenderingLoss(nn.Module):
             return F_.cook_torrance_stack(*maps, **self._kwargs(material))
         lt = torch.as_tensor(self.lights, dtype=torch.float32).reshape(-1, 3)
         it = torch.as_tensor(self.light_intensities, dtype=torch.float32).reshape(-1, 3)
-        return torch.stack([self.brdf(material, self.view_dir, lt[l], it[l if self._rows > 1 else 0], self.light_size)
+        vt = F_._view_rows(self.view_dir)
+        return torch.stack([self.brdf(material, vt[l] if self._views > 1 else self.view_dir, lt[l], it[l if self._rows > 1 else 0], self.light_size)
                             for l in range(self.n_lights)], dim=-4)
 
     def forward(self, predicted_material, ground_truth):
