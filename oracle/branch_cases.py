@@ -33,9 +33,22 @@ only, puts three lights on different sides of the surface, so that the set of li
 
 BLEND MODE (build_blend, BLEND_ENTRY_CONFIGS; held by tests/test_blend_branches_host.py, run on the GPU by tests/test_gpu_blend_branches.py):
 two materials and a mask whose BLEND is the case, for the fused blend's backward (csrc/ct_blend_backward.hpp); see the section at the end.
+
+CAMERA MODE (build(..., camera="fixed" | "per_shot"), CAMERA_ENTRY_CONFIGS; held by tests/test_camera_branches_host.py, run on the GPU by
+tests/test_gpu_camera_branches.py): the same cases under the PERSPECTIVE CAMERA (view_type="point": csrc/ct_camera.hip, ct_camera_stack.hip,
+ct_view_stack.hip).  A case carries `camera`, [3] or -- stack mode only -- [L,3], one position per shot, fp32-exact, in the point light's
+coordinates; light_size is 1.0 for both light types (the camera's grid is the point light's).  `render` evaluates
+tools/camera_oracle.cook_torrance_camera (image l of a per-shot stack: camera l and light l), `gradients` differentiates it and returns the
+position's gradient as 'view', shaped like `camera`.  N.V, the half vector and N.H are read from the per-pixel view map F.normalize(C - P)
+(of shot l), so they change sign from pixel to pixel; `decisions` lists n.v[l] per shot, and the angle grid skips angles against the
+per-pixel dots.  Maps other than the normals (and `dark`'s solved albedo), lights, intensities and `view` are those of the build without a
+camera.  `split_views`, per-shot mode only, puts three cameras on different sides of the surface under lights near +Z, so that the set of
+shots that see the FRONT of the surface changes from pixel to pixel while all of them add into one pixel adjoint.
 """
 import functools
 import math
+import os
+import sys
 
 import torch
 import torch.nn.functional as TF
@@ -50,6 +63,7 @@ ALBEDO_VALUES = (-0.2, 0.01, 0.03, 0.06, 0.5, 0.97, 1.3)
 
 CASE_NAMES = ("backlit", "backview", "half_clamp", "saturated", "dark", "albedo_range", "closed_ends")
 STACK_CASE_NAMES = CASE_NAMES + ("split_lights",)          # `split_lights` exists in stack mode only
+VIEW_STACK_CASE_NAMES = STACK_CASE_NAMES + ("split_views",)    # `split_views` exists with one camera position per shot only
 
 # name -> the variants of the case that the tests run (keyword arguments of `build`)
 VARIANTS = {
@@ -66,6 +80,7 @@ VARIANTS = {
         dict(workflow="converted", quirk=True, albedo_is_srgb=False))],
     "closed_ends": [dict()],
     "split_lights": [dict(return_srgb=True), dict(return_srgb=False)],
+    "split_views": [dict(return_srgb=True), dict(return_srgb=False)],
 }
 
 
@@ -98,7 +113,37 @@ STACK_ENTRY_CONFIGS = {
 }
 
 
+# Camera mode: (h, w, light type, lights, fp16 maps, mode) of every entry point of the perspective camera -- "sum": cook_torrance and the
+# loss step with view_type="point" (csrc/ct_camera.hip); "camera_stack": the light stack under one camera position (csrc/ct_camera_stack.hip);
+# "view_stack": one camera position per shot (csrc/ct_view_stack.hip).  The smallest shapes at which the angle grid still fills every branch
+CAMERA_ENTRY_CONFIGS = {
+    "camera-vector-lanes": (24, 40, "directional", 1, False, "sum"),           # forward 4-pixel lanes, backward pairs
+    "camera-vector-lanes-point": (24, 40, "point", 1, False, "sum"),
+    "camera-one-pixel": (23, 37, "point", 1, False, "sum"),                    # odd width: one pixel per lane
+    "camera-multi-point": (24, 40, "point", 3, False, "sum"),                  # MULTI
+    "camera-multi-directional": (24, 40, "directional", 3, False, "sum"),
+    "camera-fp16": (16, 64, "directional", 1, True, "sum"),                    # the __half instantiations
+    "camera-fp16-point": (16, 64, "point", 1, True, "sum"),
+    "camera-stack-pairs-point": (24, 40, "point", 3, False, "camera_stack"),
+    "camera-stack-one-pixel": (23, 37, "point", 3, False, "camera_stack"),     # and the forward stack's overlapping last lane
+    "camera-stack-pairs": (24, 40, "directional", 3, False, "camera_stack"),
+    "camera-stack-fp16": (16, 64, "point", 3, True, "camera_stack"),
+    "view-stack-pairs-point": (24, 40, "point", 3, False, "view_stack"),
+    "view-stack-one-pixel": (23, 37, "point", 3, False, "view_stack"),
+    "view-stack-pairs": (24, 40, "directional", 3, False, "view_stack"),
+    "view-stack-fp16": (16, 64, "directional", 3, True, "view_stack"),
+}
+
+
+def camera_entries(mode):
+    return [e for e, c in CAMERA_ENTRY_CONFIGS.items() if c[5] == mode]
+
+
 def build_for(entry, name, kw, seed=0):
+    if entry in CAMERA_ENTRY_CONFIGS:
+        h, w, light_type, n_lights, _, mode = CAMERA_ENTRY_CONFIGS[entry]
+        return build(name, h, w, light_type=light_type, n_lights=n_lights, seed=seed, stack=mode != "sum",
+                     camera="per_shot" if mode == "view_stack" else "fixed", **kw)
     if entry in STACK_ENTRY_CONFIGS:
         h, w, light_type, n_lights, _ = STACK_ENTRY_CONFIGS[entry]
         return build(name, h, w, light_type=light_type, n_lights=n_lights, seed=seed, stack=True, **kw)
@@ -113,6 +158,15 @@ def stack_target(entry, name, kw, seed=0):
     light 0's image as its target instead, so that a light that must be masked has an upstream gradient that is not 0."""
     target = render(build_for(entry, name, kw, seed=seed ^ 1)).float()
     if name == "dark":
+        target[1] = target[0]
+    return target
+
+
+def camera_target(entry, name, kw, seed=0):
+    """The MSE target of the camera tests for build_for(entry, name, kw, seed), float32: the oracle's rendering of ANOTHER material of the
+    same case (seed ^ 1), [3,H,W] for a "sum" entry, [L,3,H,W] for a stack entry (`dark`: as stack_target)."""
+    target = render(build_for(entry, name, kw, seed=seed ^ 1)).float()
+    if name == "dark" and target.dim() == 4:
         target[1] = target[0]
     return target
 
@@ -142,6 +196,15 @@ def all_stack_variants():
     return [(n, kw) for n in STACK_CASE_NAMES for kw in VARIANTS[n]]
 
 
+def all_view_stack_variants():
+    return [(n, kw) for n in VIEW_STACK_CASE_NAMES for kw in VARIANTS[n]]
+
+
+def camera_variants(entry):
+    """The variants a camera entry runs: the summed-lights ones, the stack ones, and with one camera per shot `split_views` too."""
+    return {"sum": all_variants, "camera_stack": all_stack_variants, "view_stack": all_view_stack_variants}[CAMERA_ENTRY_CONFIGS[entry][5]]()
+
+
 def _h(t):
     """Round to fp16-exact values."""
     return t.to(torch.float16).to(torch.float64)
@@ -153,8 +216,14 @@ class Case:
     `stack`: the case is a LIGHT STACK -- L images, one per light, each with its own clamp and encode, instead of one image of the
     summed lights; weight is then [L,3,H,W]."""
 
+    camera = None          # camera mode: [3] one position, or [L,3] one per shot (stack mode only); fp32-exact
+
     def __init__(self, **kw):
         self.__dict__.update(kw)
+
+    @property
+    def per_shot(self):
+        return self.camera is not None and self.camera.dim() == 2
 
     @property
     def n_lights(self):
@@ -185,6 +254,8 @@ class Case:
             kw.update(specular_is_srgb=self.specular_is_srgb)
         if self.tile != 1:
             kw.update(tile=self.tile)
+        if self.camera is not None:
+            kw.update(view_type="point")
         return kw
 
 
@@ -208,9 +279,49 @@ def _render_inputs(case, maps, view, lights, intens):
     return a, n, r, m, s, kw
 
 
-def render(case, maps=None, view=None, lights=None, intens=None, dtype=torch.float64):
-    """The oracle's rendering of the case (of other maps / parameters when given), in `dtype`."""
+def _camera_oracle():
+    """tools/camera_oracle.py, the statement of view_type="point" that tests/test_camera_host.py pins to upstream pixel by pixel."""
+    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    import camera_oracle
+    return camera_oracle
+
+
+def view_maps(case, camera=None, dtype=torch.float64):
+    """-> list of L unit view maps [3,H,W] on the output grid, the one of shot l for light l: the expanded view direction, or in camera
+    mode F.normalize(C - P) over the point light's grid (one map for every light, or with one camera per shot the map of camera l)."""
+    H, W = case.out_shape
+    L = case.n_lights
+    if case.camera is None:
+        v = TF.normalize(case.view.to(dtype), dim=0).view(3, 1, 1).expand(3, H, W)
+        return [v] * L
+    CO = _camera_oracle()
+    cam = (case.camera if camera is None else camera).to(dtype)
+    rows = cam.reshape(-1, 3)
+    maps = [TF.normalize(CO.view_offsets(c, H, W, case.light_size), dim=0) for c in rows]
+    return maps if len(maps) == L else maps * L
+
+
+def _camera_render(case, maps, camera, lights, intens, dtype, view_map):
+    CO = _camera_oracle()
+    a, n, r, m, s, kw = _render_inputs(case, maps, None, lights, intens)
+    common = dict(light_type=case.light_type, light_size=case.light_size, albedo_is_srgb=kw["albedo_is_srgb"],
+                  specular_is_srgb=kw["specular_is_srgb"], return_srgb=case.return_srgb, dtype=dtype)
+    if not case.stack:
+        return CO.cook_torrance_camera(a, n, r, m, s, camera=camera, lights=lights, intensities=intens, view_map=view_map, **common)
+    cams = camera.reshape(-1, 3)          # image l: camera l (or the one camera) and light l alone
+    return torch.stack([CO.cook_torrance_camera(a, n, r, m, s, camera=cams[l if cams.shape[0] > 1 else 0], lights=lights[l:l + 1],
+                                                intensities=intens[l:l + 1], view_map=view_map, **common) for l in range(lights.shape[0])])
+
+
+def render(case, maps=None, view=None, lights=None, intens=None, dtype=torch.float64, view_map=None):
+    """The oracle's rendering of the case (of other maps / parameters when given), in `dtype`.  Camera mode: `view` is the camera position(s),
+    and `view_map` [3,H,W] forces one map of unit view vectors on every image instead."""
     maps = [None if t is None else t.to(dtype) for t in (case.maps() if maps is None else maps)]
+    if case.camera is not None:
+        return _camera_render(case, maps, (case.camera if view is None else view).to(dtype), (case.lights if lights is None else lights).to(dtype),
+                              (case.intensities if intens is None else intens).to(dtype), dtype, view_map)
     view = (case.view if view is None else view).to(dtype)
     lights = (case.lights if lights is None else lights).to(dtype)
     intens = (case.intensities if intens is None else intens).to(dtype)
@@ -226,12 +337,13 @@ def render(case, maps=None, view=None, lights=None, intens=None, dtype=torch.flo
 def gradients(case, dtype=torch.float64, params=False, loss_target=None):
     """Autograd through the oracle of sum(out * weight) -- or of mse_loss(out, loss_target) -- in `dtype`.
     -> dict: map name -> gradient (map-sized: a tiled map owns the sum over its repeats), 'out' -> the rendering, and with
-    params=True also 'view', 'lights', 'intensities'.  A blend case: see _blend_gradients."""
+    params=True also 'view', 'lights', 'intensities' (camera mode: 'view' is the gradient of the camera position(s), shaped like them).
+    A blend case: see _blend_gradients."""
     if getattr(case, "blend", False):
         assert not params and loss_target is None
         return _blend_gradients(case, dtype)
     leaves = [None if t is None else t.to(dtype).clone().requires_grad_(True) for t in case.maps()]
-    P = [t.to(dtype).clone().requires_grad_(params) for t in (case.view, case.lights, case.intensities)]
+    P = [t.to(dtype).clone().requires_grad_(params) for t in (case.view if case.camera is None else case.camera, case.lights, case.intensities)]
     out = render(case, leaves, P[0], P[1], P[2], dtype)
     if loss_target is None:
         (out * case.weight.to(dtype)).sum().backward()
@@ -246,23 +358,23 @@ def gradients(case, dtype=torch.float64, params=False, loss_target=None):
 
 def _terms(case, maps=None):
     """The reference's intermediate quantities in float64, from torch_oracle's own pieces (cooktorrance.py:92-182).
-    -> dict with ndv [1,H,W]; per light lists ndl, ndh [1,H,W] and u [3,H,W] (the contribution BEFORE its clamp); base, f0."""
+    -> dict with ndv [1,H,W] (ndv_l: per light, the N.V of its shot); per light lists ndl, ndh [1,H,W] and u [3,H,W] (the contribution
+    BEFORE its clamp); base, f0.  Camera mode: N.V, the half vector and N.H come from the per-pixel view map (of shot l)."""
     dt = torch.float64
     maps = [None if t is None else t.to(dt) for t in (case.maps() if maps is None else maps)]
     a, n, r, m, s, kw = _render_inputs(case, maps, case.view, case.lights, case.intensities)
-    v = TF.normalize(case.view.to(dt), dim=0)
     base = O.srgb_to_linear(a) if kw["albedo_is_srgb"] else a
     if m is not None:
         f0 = torch.lerp(torch.full_like(base, 0.04), base, m)
     else:
         f0 = O.srgb_to_linear(s) if kw["specular_is_srgb"] else s
     _, H, W = base.shape
-    vmap = v.view(3, 1, 1).expand(3, H, W)
+    vmaps = view_maps(case)                # per light: the view map of its shot (one and the same unless there is a camera per shot)
     nn = TF.normalize(n, dim=0)
-    ndv_raw = (nn * vmap).sum(dim=0, keepdim=True)
-    ndv = ndv_raw.clamp(0, 1)
-    res = dict(ndv=ndv_raw, ndl=[], ndh=[], u=[], base=base, f0=f0, shade=[], rad=[])
+    ndv_raws = [(nn * vmap).sum(dim=0, keepdim=True) for vmap in vmaps]
+    res = dict(ndv=ndv_raws[0], ndv_l=ndv_raws, ndl=[], ndh=[], u=[], base=base, f0=f0, shade=[], rad=[])
     for l in range(case.n_lights):
+        vmap, ndv = vmaps[l], ndv_raws[l].clamp(0, 1)
         lmap, att = O._light_geometry(case.light_type, case.lights[l].to(dt), case.light_size, H, W, dt, 0, H)
         half = TF.normalize(vmap + lmap, dim=0)
         cos_theta = torch.clamp((half * vmap).sum(dim=0, keepdim=True), 0.0, 1.0)
@@ -285,7 +397,10 @@ def decisions(case, maps=None):
     t = _terms(case, maps)
     maps = case.maps() if maps is None else maps
     k = case.tile
-    out = [("n.v", t["ndv"], 0.0, None, False)]
+    if case.per_shot:
+        out = [("n.v[%d]" % l, x, 0.0, None, False) for l, x in enumerate(t["ndv_l"])]
+    else:
+        out = [("n.v", t["ndv"], 0.0, None, False)]
     for l in range(case.n_lights):
         lit = t["ndl"][l] > -MARGIN          # skipped only where N.L is DECIDED negative (<= -MARGIN): the contribution is then 0 in any precision
         out.append(("n.l[%d]" % l, t["ndl"][l], 0.0, None, False))
@@ -396,11 +511,17 @@ def branches(case):
     t = _terms(case)
     L = case.n_lights
     ndv, ndl, ndh, u = t["ndv"][0], [x[0] for x in t["ndl"]], [x[0] for x in t["ndh"]], t["u"]
+    ndvs = [x[0] for x in t["ndv_l"]]
     name = case.name
     if name == "backlit":
         return dict(named=functools.reduce(torch.logical_and, [x < 0 for x in ndl]), complement=functools.reduce(torch.logical_or, [x > 0 for x in ndl]))
-    if name == "backview":
-        return dict(named=ndv < 0, complement=ndv > 0)
+    if name == "backview":      # one camera per shot: some shot seen from behind / every shot from the front
+        return dict(named=functools.reduce(torch.logical_or, [x < 0 for x in ndvs]), complement=functools.reduce(torch.logical_and, [x > 0 for x in ndvs]))
+    if name == "split_views":
+        n_front = sum((x > 0).long() for x in ndvs)
+        res = dict(named=(n_front >= 1) & (n_front < L), complement=n_front == L, one_front=n_front == 1, two_front=n_front == 2)
+        res.update({"from_behind_%d" % l: x < 0 for l, x in enumerate(ndvs)})
+        return res
     if name == "half_clamp":
         # several lights: a pixel is on the branch as soon as ONE light has N.H < 0 < N.L (each light runs the GGX term by itself),
         # and on the complementary branch only if no light has, while some light is lit with N.H > 0
@@ -486,7 +607,7 @@ def _tilted_normals(h, w, max_x, max_y, case_geom, reverse, min_x=None, keep=Non
     for step in range(1, 24):
         dots = case_geom(n).abs()
         floor = torch.full((dots.shape[0], 1, 1), 0.02, dtype=torch.float64)
-        floor[1::2] = 0.15                               # rows 1, 3, 5 ...: N.L of each light
+        floor[1:getattr(case_geom, "light_rows", None):2] = 0.15      # rows 1, 3, 5 ...: N.L of each light
         near = (dots < floor).any(dim=0)
         if keep is not None:
             near = near | ~keep(n)
@@ -498,17 +619,27 @@ def _tilted_normals(h, w, max_x, max_y, case_geom, reverse, min_x=None, keep=Non
     return n
 
 
-def _geom_dots(view, lights, light_type, light_size, tile):
-    """-> function(normal [3,h,w]) -> [1 + 2 L, H, W] raw N.V, N.L and N.H on the output grid."""
+def _geom_dots(view, lights, light_type, light_size, tile, camera=None):
+    """-> function(normal [3,h,w]) -> [1 + 2 L, H, W] raw N.V, N.L and N.H on the output grid.  `camera` [3] | [L,3]: the view is the
+    per-pixel map of the camera (of camera l for light l, and the N.V of shots 1 .. L-1 follow as rows 1 + 2 L ...)."""
+    L = lights.shape[0]
+
     def f(n):
         n = TF.normalize(_rep(n, tile), dim=0)
         _, H, W = n.shape
-        v = TF.normalize(view, dim=0).view(3, 1, 1).expand(3, H, W)
-        rows = [(n * v).sum(0)]
-        for l in range(lights.shape[0]):
+        if camera is None:
+            vs = [TF.normalize(view, dim=0).view(3, 1, 1).expand(3, H, W)] * L
+        else:
+            CO = _camera_oracle()
+            vs = [TF.normalize(CO.view_offsets(c, H, W, light_size), dim=0) for c in camera.reshape(-1, 3)]
+            vs = vs if len(vs) == L else vs * L
+        rows = [(n * vs[0]).sum(0)]
+        for l in range(L):
             lmap, _ = O._light_geometry(light_type, lights[l], light_size, H, W, torch.float64, 0, H)
             rows.append((n * lmap).sum(0))
-            rows.append((n * TF.normalize(v + lmap, dim=0)).sum(0))
+            rows.append((n * TF.normalize(vs[l] + lmap, dim=0)).sum(0))
+        if camera is not None and camera.dim() == 2:
+            rows += [(n * v).sum(0) for v in vs[1:]]
         d = torch.stack(rows, 0)
         if tile != 1:          # a texel must be clear at every repeat
             k = tile
@@ -516,6 +647,7 @@ def _geom_dots(view, lights, light_type, light_size, tile):
             worst = d.abs().amin(dim=(1, 3))
             return worst
         return d
+    f.light_rows = 1 + 2 * L                              # what follows is N.V again (of the other shots), not N.L
     return f
 
 
@@ -556,15 +688,34 @@ STACK_INTENSITIES = {
 }
 
 
+# Camera mode: the camera sits CAMERA_DISTANCE along the case's own view direction (the map spans [-0.5, 0.5]^2, so the view direction
+# changes by up to +-25 degrees across it); with one camera per shot, shot l is moved by CAMERA_DELTAS[l] (a handheld capture).
+CAMERA_DISTANCE = 1.5
+CAMERA_DELTAS = [[0.0, 0.0, 0.0], [0.15, -0.10, 0.05], [-0.20, 0.12, -0.04]]
+# `half_clamp` (N.H < 0 < N.L lives at the steepest tilts towards +x, seen at a grazing angle from -x): under a point light the branch holds
+# 6.0-6.5 % with the camera at 1.5 along the case's view, 9 % at 3.0, 0.1 % at 0.6.  Its camera is lower and further away (name -> direction,
+# distance) and the columns sweep [-40, 80] degrees instead of [-80, 80] (name -> min_x, max_x): 12.5 % at the worst entry and seed.
+CAMERA_PLACES = {"half_clamp": ([-0.995, 0.0, 0.1], 3.0)}
+CAMERA_TILTS = {"half_clamp": (-40.0, 80.0)}
+# `split_views`: low cameras on three sides.  The tilt grid runs with the pixel position, so perspective adds to the tilt at one seed and takes
+# from it at the mirrored one; at elevation 0.5 the mirrored seed keeps one_front at 4 %, at 0.2 every (sub-)branch holds 19 % at both seeds.
+SPLIT_VIEW_CAMERAS = [[0.8, 0.1, 0.2], [-0.8, 0.1, 0.2], [0.1, 0.8, 0.2]]
+SPLIT_VIEW_TILTS = (75.0, 60.0)
+
+
 def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, workflow="metallic", albedo_is_srgb=True,
-          return_srgb=True, quirk=True, stack=False, flat=False):
+          return_srgb=True, quirk=True, stack=False, flat=False, camera=None):
     """The case `name` on an h x w map (output tile*h x tile*w), one or three lights of one type.  stack=True: the same inputs read as a
     light stack (untiled); `split_lights` exists only so.  flat=True (build_blend only): every normal is one that a [0,1]-ENCODED map
-    with three positive components decodes to (_flat_reachable); `backlit` is then lit and seen from the mirrored side."""
-    assert name in STACK_CASE_NAMES and n_lights in (1, 3)
+    with three positive components decodes to (_flat_reachable); `backlit` is then lit and seen from the mirrored side.
+    camera="fixed": CAMERA MODE, one camera position; camera="per_shot" (stack only): one position per light; `split_views` exists only so."""
+    assert name in VIEW_STACK_CASE_NAMES and n_lights in (1, 3)
     assert not flat or (name != "half_clamp" and not stack)
     assert not stack or tile == 1
     assert name != "split_lights" or (stack and n_lights == 3)
+    assert camera in (None, "fixed", "per_shot") and (camera is None or (tile == 1 and not flat))
+    assert camera != "per_shot" or stack
+    assert name != "split_views" or (camera == "per_shot" and n_lights == 3)
     specular_is_srgb = albedo_is_srgb
     # per case: view, light directions (the first is the case's own), intensities, tilt range, colours
     behind = [[0.1, -0.2, -1.0], [-0.3, 0.1, -0.9]]                      # lights under the surface: N.L < 0 at every tilt used with them
@@ -588,6 +739,12 @@ def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, w
         view, dirs = [0.1, 0.05, 1.0], [[0.8, 0.1, 0.5], [-0.8, 0.1, 0.5], [0.1, 0.8, 0.5]]
         intens = [[4.0, 3.5, 4.5], [3.0, 4.0, 3.5], [3.5, 3.0, 4.0]]
         max_y = 60.0
+    elif name == "split_views":
+        # three cameras on different sides of the surface (SPLIT_VIEW_CAMERAS), every light near +Z: which shots see the front of the
+        # surface changes from pixel to pixel, while almost every pixel is lit in every shot
+        view, dirs = [0.1, 0.05, 1.0], [[0.15, 0.2, 1.0], [0.3, -0.1, 0.9], [-0.1, 0.3, 0.95]]
+        intens = [[4.0, 3.5, 4.5], [3.0, 4.0, 3.5], [3.5, 3.0, 4.0]]
+        max_x, max_y = SPLIT_VIEW_TILTS
     elif name == "saturated":
         view, dirs = [0.1, -0.1, 1.0], [[0.2, 0.1, 1.0], [-0.2, 0.2, 1.0], [0.1, -0.3, 1.0]]
         intens = [[9.0, 1.2, 2.4], [7.0, 0.6, 0.5], [7.0, 0.5, 0.6]]
@@ -623,9 +780,21 @@ def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, w
     lights, intensities = lights.float().double(), intensities.float().double()          # fp32-exact: the kernels take them as floats
     view = torch.tensor(view, dtype=torch.float32).double()
     light_size = 1.0 if light_type == "point" else None
+    cam = None
+    if camera is not None:
+        light_size = 1.0                                  # the camera's grid is the point light's, for both light types
+        direction, distance = CAMERA_PLACES.get(name, (view.tolist(), CAMERA_DISTANCE))
+        cam = TF.normalize(torch.tensor(direction, dtype=torch.float64), dim=0) * distance
+        if camera == "per_shot":
+            cam = cam.view(1, 3) + torch.tensor(CAMERA_DELTAS[:n_lights], dtype=torch.float64)
+            if name == "split_views":
+                cam = TF.normalize(torch.tensor(SPLIT_VIEW_CAMERAS, dtype=torch.float64), dim=1) * CAMERA_DISTANCE
+        cam = cam.float().double()                        # fp32-exact: the kernels take it as floats
+        if name in CAMERA_TILTS:
+            min_x, max_x = CAMERA_TILTS[name]
     # half_clamp's branch lives at the steepest tilts towards +x: they come FIRST, so that cutting a map's last columns keeps them
     reverse = (seed % 2 == 1) != (name == "half_clamp")
-    normal = _tilted_normals(h, w, max_x, max_y, _geom_dots(view, lights, light_type, light_size, tile), reverse,
+    normal = _tilted_normals(h, w, max_x, max_y, _geom_dots(view, lights, light_type, light_size, tile, camera=cam), reverse,
                              min_x=min_x, keep=_flat_reachable if flat else None)
     rough = _pattern(rough_values, 1, h, w, seed + 1, step=(3, 1, 0))
     albedo = _pattern(albedo_values, 3, h, w, seed)
@@ -657,7 +826,7 @@ def build(name, h, w, *, light_type="directional", n_lights=1, tile=1, seed=0, w
     H, W = h * tile, w * tile
     case = Case(name=name, albedo=albedo, normal=normal, roughness=rough, metallic=metallic, specular=specular, view=view, lights=lights,
                 intensities=intensities, light_type=light_type, light_size=light_size, workflow=workflow, albedo_is_srgb=albedo_is_srgb,
-                specular_is_srgb=specular_is_srgb, return_srgb=return_srgb, quirk=quirk, tile=tile, stack=stack,
+                specular_is_srgb=specular_is_srgb, return_srgb=return_srgb, quirk=quirk, tile=tile, stack=stack, camera=cam,
                 weight=_weight(H, W, 1000 + seed) if not stack else torch.stack([_weight(H, W, 1000 + seed + 100 * l) for l in range(n_lights)]))
     if name == "dark":
         case = _solve_dark(case, seed)
