@@ -397,6 +397,43 @@ size_t pbr_view_mse_stack_fit_workspace_bytes(const pbr_render_desc *desc);
 int pbr_cook_torrance_view_mse_stack_fit_step(const pbr_render_desc *desc, const float *cameras_host, const void *cameras_device, const void *targets,
                                               void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic, void *g_specular,
                                               void *g_params, void *loss, void *workspace, void *stream);
+/*
+ * The six stack loss steps with a weight per pixel -- a capture with a mask: coverage that differs from shot to shot, clipped highlights,
+ * confidence.  *loss = mean over all 3 B L H W elements of w (image - target)^2, the weight the same for the three channels; N stays 3 B L H W,
+ * the sum of the weights is not used (a caller who wants the mean over valid pixels divides by the constant mean of the weights).  Every g_*
+ * and g_params is the gradient of that loss.  `weights` is fp32 DEVICE memory, never NULL; the weight of pixel (y, x) of shot l of material b is
+ * weights[b * w_batch_stride + l * w_light_stride + y * W + x], the strides in elements, the address formed in 64-bit arithmetic.
+ * `w_light_stride` is H W (a plane per shot) or 0 (one plane for all shots); `w_batch_stride` is the caller's (L H W or H W for dense weights).
+ * Everything else -- `targets`, the g_*, `g_params` and its layout, *loss, the camera pointers of the view calls -- is the unweighted call's,
+ * and so are the workspaces: pbr_mse_step_workspace_bytes for the steps, pbr_mse_stack_fit_workspace_bytes /
+ * pbr_camera_mse_stack_fit_workspace_bytes / pbr_view_mse_stack_fit_workspace_bytes for the fit steps; the weights add no workspace.
+ * Bytes per pixel (fp32 maps, metallic workflow): 64 + 16 L with a plane per shot, 68 + 12 L with one plane.  One pass, deterministic.
+ * No sign check: a negative weight is the caller's business.  A weight of exactly 0 beside a finite target and a finite render contributes
+ * exactly +-0 to the loss and to every gradient; a NaN target under a zero weight still gives NaN (0 * NaN).
+ * Before any launch: the codes of the unweighted call, NULL `weights` PBR_ERR_NULL_MAP like the other pointers, then a `w_light_stride` that is
+ * neither 0 nor H W PBR_ERR_SHAPE.
+ */
+int pbr_cook_torrance_weighted_mse_stack_step(const pbr_render_desc *desc, const void *targets, const void *weights, int64_t w_batch_stride,
+                                              int64_t w_light_stride, void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic,
+                                              void *g_specular, void *loss, void *workspace, void *stream);
+int pbr_cook_torrance_weighted_mse_stack_fit_step(const pbr_render_desc *desc, const void *targets, const void *weights, int64_t w_batch_stride,
+                                                  int64_t w_light_stride, void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic,
+                                                  void *g_specular, void *g_params, void *loss, void *workspace, void *stream);
+int pbr_cook_torrance_camera_weighted_mse_stack_step(const pbr_render_desc *desc, const void *targets, const void *weights, int64_t w_batch_stride,
+                                                     int64_t w_light_stride, void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic,
+                                                     void *g_specular, void *loss, void *workspace, void *stream);
+int pbr_cook_torrance_camera_weighted_mse_stack_fit_step(const pbr_render_desc *desc, const void *targets, const void *weights,
+                                                         int64_t w_batch_stride, int64_t w_light_stride, void *g_albedo, void *g_normal,
+                                                         void *g_roughness, void *g_metallic, void *g_specular, void *g_params, void *loss,
+                                                         void *workspace, void *stream);
+int pbr_cook_torrance_view_weighted_mse_stack_step(const pbr_render_desc *desc, const float *cameras_host, const void *cameras_device,
+                                                   const void *targets, const void *weights, int64_t w_batch_stride, int64_t w_light_stride,
+                                                   void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic, void *g_specular,
+                                                   void *loss, void *workspace, void *stream);
+int pbr_cook_torrance_view_weighted_mse_stack_fit_step(const pbr_render_desc *desc, const float *cameras_host, const void *cameras_device,
+                                                       const void *targets, const void *weights, int64_t w_batch_stride, int64_t w_light_stride,
+                                                       void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic, void *g_specular,
+                                                       void *g_params, void *loss, void *workspace, void *stream);
 /* ABI 5: view / light / intensity from DEVICE memory.  `view_dir` [3], `lights` [n_lights][3], `intensities` [intensity_rows][3] with
  * intensity_rows = 1 (one intensity for every light) or n_lights: fp32 device pointers; a NULL pointer takes that parameter from the descriptor
  * (d->view_dir / d->lights / d->intensities: host values), so only what lives on the device needs to be there.  Writes `block` (pbr_device_params_bytes() bytes,

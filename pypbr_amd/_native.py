@@ -56,6 +56,9 @@ EXPORTS = (
     "pbr_camera_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_camera_mse_stack_fit_step",
     "pbr_cook_torrance_view_stack", "pbr_cook_torrance_view_mse_stack_step",
     "pbr_view_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_view_mse_stack_fit_step",
+    "pbr_cook_torrance_weighted_mse_stack_step", "pbr_cook_torrance_weighted_mse_stack_fit_step",
+    "pbr_cook_torrance_camera_weighted_mse_stack_step", "pbr_cook_torrance_camera_weighted_mse_stack_fit_step",
+    "pbr_cook_torrance_view_weighted_mse_stack_step", "pbr_cook_torrance_view_weighted_mse_stack_fit_step",
 )
 
 
@@ -220,6 +223,13 @@ def lib():
     L.pbr_view_mse_stack_fit_workspace_bytes.restype = ctypes.c_size_t
     L.pbr_cook_torrance_view_mse_stack_fit_step.argtypes = [ctypes.POINTER(RenderDesc), fp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pbr_cook_torrance_view_mse_stack_fit_step.restype = ctypes.c_int
+    # the weighted stack steps: the unweighted call's arguments with (weights, w_batch_stride, w_light_stride) behind the targets
+    i64 = ctypes.c_int64
+    for family, before in (("", []), ("camera_", []), ("view_", [fp, vp])):
+        for step, pointers in (("step", 8), ("fit_step", 9)):      # the g_* (5), [g_params], loss, workspace, stream
+            fn = getattr(L, "pbr_cook_torrance_%sweighted_mse_stack_%s" % (family, step))
+            fn.argtypes = [ctypes.POINTER(RenderDesc)] + before + [vp, vp, i64, i64] + [vp] * pointers
+            fn.restype = ctypes.c_int
     L.pbr_cook_torrance_mse_stack_step.argtypes =[ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.pbr_cook_torrance_mse_stack_step.restype = ctypes.c_int
     L.pbr_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]

@@ -32,15 +32,17 @@ struct BArgs {
 //   (clamp, encode, difference) runs INSIDE the light loop, once per light, and the adjoints of all lights add up in the shared accumulators
 //   before the light-independent tail runs once.  `stack` selects that: the light loop runs over a.n_lights although MULTI is false.
 //   With PGRAD (the stack-fit step) light l's six sums leave the lane inside the loop, as for MULTI; a lane outside the map carries scale = 0.
-struct NoLoss { static constexpr bool on = false, stack = false; };
+//   WeightedStackMseLoss<VEC> -- StackMseLoss with a weight per pixel and shot (ct_stack_weighted.hip): `weighted` selects the colour
+//   adjoint that forms d (scale w) and hands back w d d (loss_colour_adjoint).
+struct NoLoss { static constexpr bool on = false, stack = false, weighted = false; };
 template <int VEC> struct MseLoss {
-    static constexpr bool on = true, stack = false;
+    static constexpr bool on = true, stack = false, weighted = false;
     float tgt[3][VEC];      // the lane's pixels of the target image
     float scale;            // 2 / N  (d mean((out - target)^2) / d out = scale * (out - target))
     float sq;               // sum of squared differences over the lane's pixels
 };
 template <int VEC> struct StackMseLoss {
-    static constexpr bool on = true, stack = true;
+    static constexpr bool on = true, stack = true, weighted = false;
     float tgt[3][VEC];      // the lane's pixels of the CURRENT light's target image
     float scale;            // 2 / N, N = 3 B L H W
     float sq;               // sum of squared differences over the lane's pixels and all lights
@@ -60,6 +62,34 @@ template <int VEC> struct StackMseLoss {
         prefetch(l + 1 < n_lights ? l + 1 : l);
     }
 };
+// StackMseLoss with a weight per pixel and shot, one value for the three channels (the weighted light-stack steps: masked captures): the loss
+// is mean(w (out - target)^2) over the same 3 B L H W elements.  Shot l + 1's weights leave together with shot l + 1's target pixels, one shot
+// ahead, through the same loads; with one plane for all shots (wstep = 0) the one load before the loop is all there is.  A lane outside the map
+// reads its clamped position's weight, as it reads that position's targets: every load is in bounds.
+template <int VEC> struct WeightedStackMseLoss : StackMseLoss<VEC> {
+    static constexpr bool weighted = true;
+    float w[VEC];           // the lane's pixels of the CURRENT shot's weight plane
+    float wnxt[VEC];        // ... of the NEXT shot's
+    const float *wlane;     // the lane's first pixel in shot 0's plane of its material: weights + b w_batch_stride + pix (64-bit, by the kernel)
+    int64_t wstep;          // elements from one shot's plane to the next: H W, or 0 for one plane shared by all shots
+    __device__ __forceinline__ void prefetch_first() {
+        StackMseLoss<VEC>::prefetch(0);
+        Ld<float, VEC>::template load<true>(wlane, 0, wnxt);
+    }
+    __device__ __forceinline__ void begin_light(int l, int n_lights) {
+        const int nxt_l = l + 1 < n_lights ? l + 1 : l;
+        StackMseLoss<VEC>::begin_light(l, n_lights);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) w[j] = wnxt[j];
+        if (wstep) Ld<float, VEC>::template load<true>(wlane, (int64_t)nxt_l * wstep, wnxt);      // wave-uniform
+    }
+};
+// The colour adjoint of one image under a loss policy, weighted or not: group g's pixels against `ref`, their targets.
+template <class R, class Loss>
+__device__ __forceinline__ void loss_colour_adjoint(bool srgb, const R (&uc)[3], const R (&ref)[3], const Loss &loss, int g, R (&g_col)[3], float (&sqd)[3]) {
+    if constexpr (Loss::weighted) colour_adjoint(srgb, uc, ref, loss.scale, gather<R>(loss.w, g), g_col, sqd);
+    else colour_adjoint<true>(srgb, uc, ref, loss.scale, g_col, sqd);
+}
 
 // The way of the light / view sums (PGRAD) out of the lanes: eight of the lane's sums -> their wave totals (wave_sum8: lane l holds value
 // (l >> 3) & 7) -> the first n of them added to the workgroup's LDS row, values 0..2 at first3[0..2], values 3.. at rest[0..].
@@ -154,7 +184,7 @@ __device__ __forceinline__ void backward_body_to(const KArgs &a, const BArgs &b,
                 load_ref();
                 if constexpr (Loss::on) {
                     float sqd[3];
-                    colour_adjoint<true>(a.out_srgb != 0, e.uc, ref, loss.scale, g_col, sqd);
+                    loss_colour_adjoint(a.out_srgb != 0, e.uc, ref, loss, g, g_col, sqd);
                     loss.sq += sqd[0]; loss.sq += sqd[1]; loss.sq += sqd[2];
                 } else {
                     colour_adjoint(a.out_srgb != 0, e.uc, ref, g_col);

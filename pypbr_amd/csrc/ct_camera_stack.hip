@@ -12,7 +12,7 @@
 // type (pixel_view, material_terms / bwd_decode, light_geom, shade_light / eval_light, colour_adjoint<true>, backprop_light, bwd_tail, the
 // StackMseLoss policy); the frame loss_step / backward_body_to is not used, because it reads ONE view for the launch (view_of).  The gradient
 // of the position is ct_camera.hip's: (g_v - v (v . g_v)) / |C - P| per pixel, applied BEFORE the sum over pixels.
-#include "ct_camera.hpp"
+#include "ct_camera_stack.hpp"
 
 namespace pbr {
 
@@ -76,6 +76,8 @@ void cook_torrance_camera_stack_kernel(const KArgs a) {
 // PGRAD (the fit step): light l's six sums leave the lane inside the loop (pgrad_add8 -> the workgroup's LDS row of 3 + 6 L floats:
 // camera, lights L x 3, intensities L x 3); after the tail the camera's per-pixel Jacobian, then the row goes to b.g_param_partials.  With one
 // wave per workgroup the order of the LDS additions is fixed, and the rows are added up in fp64 in a fixed order: deterministic.
+// The same statements over a loss policy are camera_stack_step (ct_camera_stack.hpp: the weighted sibling is built from it); this kernel keeps
+// them inline, because through that function it is scheduled differently.  Change the two together.
 template <int LIGHT, int WF, int VEC, typename TM, bool PGRAD>
 __global__ __launch_bounds__(64)
 void cook_torrance_camera_mse_stack_step_kernel(const KArgs a, const BArgs b, const float *__restrict__ targets, float scale, float *__restrict__ partials) {
@@ -166,22 +168,6 @@ template <int L, int W, bool PGRAD>
 static LossStepFn pick_camera_stack_step(bool half_maps, int vec) {
     if (half_maps) return vec == 2 ? cook_torrance_camera_mse_stack_step_kernel<L, W, 2, __half, PGRAD> : cook_torrance_camera_mse_stack_step_kernel<L, W, 1, __half, PGRAD>;
     return vec == 2 ? cook_torrance_camera_mse_stack_step_kernel<L, W, 2, float, PGRAD> : cook_torrance_camera_mse_stack_step_kernel<L, W, 1, float, PGRAD>;
-}
-
-// launch_loss_step (ct_loss.hip) with the camera's kernel arguments: that launcher fills them itself (fill_args normalises the view), and
-// here the view must stay the position as given (camera_args).  Everything else is its statements: one-wave workgroups of `vec` pixels per
-// lane, contiguous target and gradient planes, scale = 2 / count, never more workgroups than the rows' size query promised.
-static int launch_camera_loss_step(const pbr_render_desc *d, LossStepFn fn, int vec, const BArgs &b, const void *targets, double count,
-                                   float *partials, hipStream_t st, KArgs &k) {
-    camera_args(d, vec, k, 6);
-    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
-    if (b.g_param_partials) {
-        const int64_t most = max_tiles(d);
-        if (most < 0 || k.n_tiles > most) return PBR_ERR_SHAPE;
-    }
-    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(targets), (float)(2.0 / count), partials);
-    return launch_status();
 }
 
 }  // namespace pbr

@@ -275,6 +275,21 @@ __device__ __forceinline__ void colour_adjoint(bool srgb, const R (&uc)[3], cons
 #pragma unroll
     for (int c = 0; c < 3; ++c) g_col[c] = colour_adjoint<LOSS>(srgb, uc[c], ref[c], scale, sqd[c]);
 }
+// ... with a weight `w` per pixel, the same for the three channels (the weighted light-stack steps): the loss is mean(w (out - ref)^2), so the
+// upstream value is d (scale w) and `sqd` receives w d d.  A weight of exactly 0 beside finite values gives exactly +-0 in both; nothing is
+// tested, so 0 * NaN stays NaN.
+template <class R>
+__device__ __forceinline__ void colour_adjoint(bool srgb, const R (&uc)[3], const R (&ref)[3], float scale, R w, R (&g_col)[3], float (&sqd)[3]) {
+    const R ws = w * scale;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        R out, slope;
+        encode_and_slope(srgb, uc[c], out, slope);
+        const R d = out - ref[c];
+        sqd[c] = hsum(w * d * d);
+        g_col[c] = behind_encode(srgb, d * ws, slope);
+    }
+}
 // SEVERAL lights (H12: per-light clamp, sum, clamp, encode), the same adjoint for all of them: pass 1 over the lights -- the summed colour
 // decides the outer clamp, and the encode is taken at clamp01(sum).  Pass 2, every light's backprop_light with this g_col, is the caller's.
 template <int LIGHT, bool LOSS, class R, class VT>

@@ -19,27 +19,9 @@
 // The positions come beside the descriptor (desc->view_dir and the device block's view are not read): [L][3] host values, which travel in the
 // kernel arguments, or a plain fp32 [L][3] device pointer that the kernel reads, wave-uniformly, when it runs -- no read-back, nothing baked in,
 // so a captured graph sees the positions' current values at every replay.  Lights and intensities: the descriptor or its device_params block.
-#include "ct_camera.hpp"
+#include "ct_camera_stack.hpp"
 
 namespace pbr {
-
-// The shots' camera positions: kernel arguments, or device memory when `dev` is set.  Device memory is read through the CONSTANT address space
-// like the DevParams block (ct_kernel.hpp: dev_params): written by an earlier kernel of the stream, never by this one -- scalar loads.
-struct ViewArgs {
-    float cam[PBR_MAX_LIGHTS][3];
-    uint64_t dev;
-};
-__device__ __forceinline__ Vec3 camera_at(const ViewArgs &v, int l) {
-    if (v.dev) {
-        typedef const __attribute__((address_space(4))) float *ConstFloats;
-        const ConstFloats p = (ConstFloats)v.dev;
-        return Vec3{p[3 * l], p[3 * l + 1], p[3 * l + 2]};
-    }
-    return Vec3{v.cam[l][0], v.cam[l][1], v.cam[l][2]};
-}
-// The view that material_terms / bwd_decode / bwd_tail are handed where the real one is per shot: what they form from it is replaced
-// (view_terms) or multiplied by an adjoint that is exactly 0 (bwd_tail: g_ndv).
-__device__ __forceinline__ Vec3 no_view() { return Vec3{0.0f, 0.0f, 1.0f}; }
 
 // ------------------------------------------------------------------ forward: the stack itself
 // cook_torrance_camera_stack_kernel with the view inside the light loop.
@@ -94,6 +76,8 @@ void cook_torrance_view_stack_kernel(const KArgs a, const ViewArgs va) {
 // lane inside the loop (pgrad_add8: the light's six, and the cameras' three of two shots together).  At L = 16 a row holds 144 floats, more
 // than the wave has lanes: the zeroing and the copy-out stride.  One wave per workgroup, so the order of the LDS additions is fixed, and the
 // rows are added up in fp64 in a fixed order: deterministic.
+// The same statements over a loss policy are view_stack_step (ct_camera_stack.hpp: the weighted sibling is built from it); this kernel keeps
+// them inline, because through that function it is scheduled differently.  Change the two together.
 template <int LIGHT, int WF, int VEC, typename TM, bool PGRAD>
 __global__ __launch_bounds__(64)
 void cook_torrance_view_mse_stack_step_kernel(const KArgs a, const BArgs b, const ViewArgs va, const float *__restrict__ targets, float scale,
@@ -201,30 +185,6 @@ static ViewStepFn pick_view_stack_step(bool half_maps, int vec) {
     return vec == 2 ? cook_torrance_view_mse_stack_step_kernel<L, W, 2, float, PGRAD> : cook_torrance_view_mse_stack_step_kernel<L, W, 1, float, PGRAD>;
 }
 
-// Exactly one source of positions: host values (copied into the kernel arguments now) or a device pointer (read when the kernel runs).
-static bool one_camera_source(const float *cameras_host, const void *cameras_device) { return (cameras_host != nullptr) != (cameras_device != nullptr); }
-static ViewArgs view_args(const pbr_render_desc *d, const float *cameras_host, const void *cameras_device) {
-    ViewArgs v;
-    std::memset(&v, 0, sizeof(v));
-    if (cameras_host) std::memcpy(v.cam, cameras_host, sizeof(float) * 3 * (size_t)d->n_lights);
-    v.dev = reinterpret_cast<uint64_t>(cameras_device);
-    return v;
-}
-
-// launch_camera_loss_step (ct_camera_stack.hip) with the shots' positions as a kernel argument of their own.
-static int launch_view_loss_step(const pbr_render_desc *d, ViewStepFn fn, int vec, const BArgs &b, const ViewArgs &va, const void *targets,
-                                 double count, float *partials, hipStream_t st, KArgs &k) {
-    camera_args(d, vec, k, 6);
-    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
-    if (b.g_param_partials) {
-        const int64_t most = max_tiles(d);
-        if (most < 0 || k.n_tiles > most) return PBR_ERR_SHAPE;
-    }
-    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, va, static_cast<const float *>(targets), (float)(2.0 / count), partials);
-    return launch_status();
-}
-
 }  // namespace pbr
 
 extern "C" {
@@ -266,7 +226,7 @@ int pbr_cook_torrance_view_mse_stack_step(const pbr_render_desc *d, const float 
     float *const partials = static_cast<float *>(workspace);
     const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
     KArgs k;
-    const int e = launch_view_loss_step(d, fn, vec, b, view_args(d, cameras_host, cameras_device), targets, count, partials, st, k);
+    const int e = launch_camera_loss_step(d, fn, vec, b, targets, count, partials, st, k, view_args(d, cameras_host, cameras_device));
     return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
 }
 
@@ -297,7 +257,7 @@ int pbr_cook_torrance_view_mse_stack_fit_step(const pbr_render_desc *d, const fl
     float *const rows = reinterpret_cast<float *>(static_cast<char *>(workspace) + pbr_mse_step_workspace_bytes(d));      // one row per workgroup
     const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, rows};
     KArgs k;
-    int e = launch_view_loss_step(d, fn, vec, b, view_args(d, cameras_host, cameras_device), targets, count, partials, st, k);
+    int e = launch_camera_loss_step(d, fn, vec, b, targets, count, partials, st, k, view_args(d, cameras_host, cameras_device));
     if (e == PBR_OK) e = param_rows_finish(d, rows, k.n_tiles, 3 * d->n_lights, d->n_lights, k.dev, static_cast<float *>(g_params), st);
     return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
 }

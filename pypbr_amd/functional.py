@@ -31,7 +31,7 @@ sibling modules, one per file of csrc/, and their names are imported back below,
   functional    descriptors, RenderPlan, cook_torrance, the autograd bridges, rendering_loss_mse,       csrc/ct_*.hip/.hpp, torch_ops.cpp
                 light stacks (cook_torrance_stack, rendering_loss_mse_stack)
 
-The one-pass loss steps (_MseStepFn, _MseStackStepFn, _MseStackFitFn) are three autograd classes over one frame, said once in front of
+The one-pass loss steps (_MseStepFn, _MseStackStepFn, _MseStackFitFn ...; the stack classes take optional per-pixel weights) are autograd classes over one frame, said once in front of
 _MseStepFn: two predicates for the callers (_shared_by_batch, _plain_kwargs), one launch (_step_plan, _launch_loss_step), one ctx idiom
 (_keep_step, _kept_step) and the one scaling launch (_scale_step_gradients).
 
@@ -884,9 +884,17 @@ _STEP_KINDS = {"step": ("pbr_cook_torrance_mse_step", "pbr_mse_step_workspace_by
                "camera_fit": ("pbr_cook_torrance_camera_mse_stack_fit_step", "pbr_camera_mse_stack_fit_workspace_bytes"),
                "view_stack": ("pbr_cook_torrance_view_mse_stack_step", "pbr_mse_step_workspace_bytes"),
                "view_fit": ("pbr_cook_torrance_view_mse_stack_fit_step", "pbr_view_mse_stack_fit_workspace_bytes")}
-_FIT_KINDS = ("fit", "camera_fit", "view_fit")
-_VIEW_KINDS = ("view_stack", "view_fit")          # one camera position per shot: the positions travel beside the plan, and a fit row is 9 L floats
-_POINT_KINDS = ("camera_stack", "camera_fit") + _VIEW_KINDS
+# ... and the six stack kinds with a weight per pixel (kind + "_w"): the weighted entry point, the unweighted kind's workspace
+_WEIGHTED_KINDS = tuple(k + "_w" for k in _STEP_KINDS if k != "step")
+_STEP_KINDS.update({k + "_w": (e.replace("mse_stack", "weighted_mse_stack"), q) for k, (e, q) in _STEP_KINDS.items() if k != "step"})
+_FIT_KINDS = ("fit", "camera_fit", "view_fit", "fit_w", "camera_fit_w", "view_fit_w")
+_VIEW_KINDS = ("view_stack", "view_fit", "view_stack_w", "view_fit_w")      # one camera position per shot: the positions travel beside the plan, and a fit row is 9 L floats
+_POINT_KINDS = ("camera_stack", "camera_fit", "camera_stack_w", "camera_fit_w") + _VIEW_KINDS
+
+
+def _step_kind(kind, weights):
+    """The kind a step class launches: its own, or its weighted sibling when the call carries weights."""
+    return kind if weights is None else kind + "_w"
 
 
 def _camera_rows(view_dir, L, device):
@@ -904,10 +912,12 @@ def _camera_rows(view_dir, L, device):
     return (ctypes.c_float * (3 * L))(*[x for r in rows for x in r]), None
 
 
-def _launch_loss_step(kind, plan, maps, targets, wanted, cameras=None):
+def _launch_loss_step(kind, plan, maps, targets, wanted, cameras=None, weights=None):
     """ONE launch of a loss step -> (gradient buffers | None per map, parameter gradients [3 + 6 L] | None, loss).  Raises _StepNotServed
     before anything is launched when the library does not serve the descriptor as one pass (e.g. tiled maps with several lights).
-    `cameras`: the view kinds' [L,3] positions (the plan's own view is not read); their parameter gradients are [9 L]."""
+    `cameras`: the view kinds' [L,3] positions (the plan's own view is not read); their parameter gradients are [9 L].
+    `weights`: the weighted kinds' per-pixel weights, in a shape `_stack_weights` accepts; brought to the maps' device as float32 like the
+    targets (a copy for any other dtype or device) and handed over as a pointer and two strides in elements."""
     entry, query = _STEP_KINDS[kind]
     if (kind in _POINT_KINDS) != (plan.view_type == "point"):
         raise ValueError("loss step %r does not take a plan with view_type=%r" % (kind, plan.view_type))
@@ -927,13 +937,18 @@ def _launch_loss_step(kind, plan, maps, targets, wanted, cameras=None):
     if kind in _VIEW_KINDS:
         cam_host, cam_dev = _camera_rows(cameras, d.n_lights, dev)
         where = (cam_host, ptr(cam_dev))
+    beside = ()
+    if kind in _WEIGHTED_KINDS:
+        plane = d.height * d.width
+        w = weights.detach().to(dev, torch.float32).reshape(d.batch, -1, d.height, d.width).contiguous()      # [B, L | 1, H, W]
+        beside = (w.data_ptr(), w.shape[1] * plane, plane if w.shape[1] == d.n_lights else 0)
     lib = N.lib()
     ws_bytes = getattr(lib, query)(ctypes.byref(d))
     if ws_bytes == 0:
         raise _StepNotServed()
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev)      # at least the bytes asked for, 8-byte aligned
-    launch(dev, getattr(lib, entry), ctypes.byref(d), *where, tgt.data_ptr(), *[ptr(b) for b in bufs], *([] if gp is None else [gp.data_ptr()]),
-           loss.data_ptr(), ws.data_ptr())
+    launch(dev, getattr(lib, entry), ctypes.byref(d), *where, tgt.data_ptr(), *beside, *[ptr(b) for b in bufs],
+           *([] if gp is None else [gp.data_ptr()]), loss.data_ptr(), ws.data_ptr())
     if kind != "step":
         STACK_LAUNCHES[entry[len("pbr_cook_torrance_"):]] += 1
     return bufs, gp, loss
@@ -942,21 +957,22 @@ def _launch_loss_step(kind, plan, maps, targets, wanted, cameras=None):
 _NO_VIEW = (0.0, 0.0, 1.0)      # the view of a view-stack plan: never read (the positions come beside the descriptor)
 
 
-def _plan_and_launch(kind, maps, kwargs, params, targets, wanted):
+def _plan_and_launch(kind, maps, kwargs, params, targets, wanted, weights=None):
     """_step_plan and _launch_loss_step for any kind.  The view kinds plan with a placeholder view and hand `params[0]`, the [L,3] positions,
     to the launch."""
     if kind in _VIEW_KINDS:
         plan = _step_plan(maps, kwargs, (_NO_VIEW, params[1], params[2]))
-        return _launch_loss_step(kind, plan, maps, targets, wanted, cameras=params[0])
-    return _launch_loss_step(kind, _step_plan(maps, kwargs, params), maps, targets, wanted)
+        return _launch_loss_step(kind, plan, maps, targets, wanted, cameras=params[0], weights=weights)
+    return _launch_loss_step(kind, _step_plan(maps, kwargs, params), maps, targets, wanted, weights=weights)
 
 
-def _keep_step(ctx, kind, maps, targets, kwargs, wanted, kept, params=None):
+def _keep_step(ctx, kind, maps, targets, kwargs, wanted, kept, params=None, weights=None):
     """Forward's bookkeeping: the gradients the launch left stay in ctx until backward hands them over.  The plan (descriptor + strong
-    references to every map) is NOT kept: a second backward rebuilds it from the saved tensors."""
+    references to every map) is NOT kept: a second backward rebuilds it from the saved tensors -- the weights, saved next to the targets,
+    among them."""
     ctx.kind, ctx.kwargs, ctx.wanted, ctx.grads, ctx.params = kind, kwargs, wanted, kept, params
     ctx.present = [t is not None for t in maps]
-    ctx.save_for_backward(*[t for t in maps if t is not None], targets)
+    ctx.save_for_backward(*[t for t in maps if t is not None], targets, *([] if weights is None else [weights]))
 
 
 def _kept_step(ctx):
@@ -966,9 +982,10 @@ def _kept_step(ctx):
     saved = ctx.saved_tensors                               # in-place edits of the maps since forward are detected, as for any op
     kept, ctx.grads = ctx.grads, None
     if kept is None:
-        it = iter(saved[:-1])
+        it = iter(saved)
         maps = [next(it) if p else None for p in ctx.present]
-        kept = _plan_and_launch(ctx.kind, maps, ctx.kwargs, ctx.params, saved[-1], ctx.wanted)[:2]
+        targets, weights = next(it), next(it, None)
+        kept = _plan_and_launch(ctx.kind, maps, ctx.kwargs, ctx.params, targets, ctx.wanted, weights)[:2]
     return kept
 
 
@@ -1068,7 +1085,7 @@ class _MseStepFn(torch.autograd.Function):
 
 def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], roughness: torch.Tensor,
                        metallic: Optional[torch.Tensor] = None, specular: Optional[torch.Tensor] = None, *,
-                       target: torch.Tensor, **kwargs) -> torch.Tensor:
+                       target: torch.Tensor, weights: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
     """`torch.nn.MSELoss()(cook_torrance(albedo, normal, roughness, metallic | specular, **kwargs), target)` -- the rendering loss of
     docs/source/tutorials/06_advanced.rst:73-107 for the predicted material -- as a 0-dim tensor on the maps' device.  When a map
     requires grad and the evaluation qualifies (whole untiled maps of the batch, fp32 result, light / view parameters without
@@ -1077,9 +1094,28 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
     (`view_dir` is the camera's position) and ONE light the call is the light stack of one image -- the same quantity: one image, its own
     clamp and encode, the mean over 3 B H W values -- and takes its one pass under `rendering_loss_mse_stack`'s conditions:
     pbr_cook_torrance_camera_mse_stack_step, or pbr_cook_torrance_camera_mse_stack_fit_step when `view_dir`, `light` or `light_intensity`
-    requires grad; several lights summed into one image under the camera stay the composition."""
+    requires grad; several lights summed into one image under the camera stay the composition.
+
+    `weights` (optional): one weight per pixel, [1,H,W] / [B,1,H,W]; the loss is `(weights * (image - target) ** 2).mean()` over all 3 B H W
+    elements.  With ONE light the call is `rendering_loss_mse_stack(weights=)` at L = 1 -- in both view types: its routes, its conversion of
+    the weights (a copy for anything but float32 on the maps' device), its rules for zeros and NaNs; several lights summed into one image
+    are the evaluation followed by the weighted mean.  `weights=None` goes where it went before."""
     maps = (albedo, normal, roughness, metallic, specular)
     params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
+    if weights is not None:
+        if not isinstance(albedo, torch.Tensor) or albedo.dim() not in (3, 4) or not isinstance(target, torch.Tensor):
+            raise ValueError("albedo must be [3,H,W] or [B,3,H,W], target a tensor")
+        want = tuple(target.shape[:-3]) + (1,) + tuple(target.shape[-2:])
+        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != want or target.dim() != albedo.dim():
+            raise ValueError("weights must be %s, got %s" % (want, tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights)))
+        try:
+            one_light = _stack_lights(params[1], params[2]) == (1, 1)
+        except (ValueError, TypeError, AttributeError, RuntimeError):
+            one_light = False                                # whatever is wrong with the lights is the evaluation's to say
+        if one_light:                                        # the stack of one image: the same quantity
+            return rendering_loss_mse_stack(albedo, normal, roughness, metallic, specular, targets=target.unsqueeze(-4),
+                                            weights=weights.unsqueeze(-4), **kwargs)
+        return _weighted_mse(cook_torrance(albedo, normal, roughness, metallic, specular, **kwargs), target, weights)
     grad_maps = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in maps)
     grad_other = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in params + (target,))
     B = albedo.shape[0] if albedo.dim() == 4 else 1
@@ -1112,7 +1148,10 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
 # light moved between the shots; image l of the stack is what `cook_torrance` gives for light l alone, and the loss is the MSE over all of them.
 STACK_LAUNCHES = {"cook_torrance_stack": 0, "mse_stack_step": 0, "mse_stack_fit_step": 0,       # calls of the stack entry points (the tests count launches)
                   "camera_stack": 0, "camera_mse_stack_step": 0, "camera_mse_stack_fit_step": 0,     # ... and of their forms under the perspective camera
-                  "view_stack": 0, "view_mse_stack_step": 0, "view_mse_stack_fit_step": 0}            # ... with one camera position per shot
+                  "view_stack": 0, "view_mse_stack_step": 0, "view_mse_stack_fit_step": 0,            # ... with one camera position per shot
+                  "weighted_mse_stack_step": 0, "weighted_mse_stack_fit_step": 0,                     # ... and of the six loss steps with per-pixel weights
+                  "camera_weighted_mse_stack_step": 0, "camera_weighted_mse_stack_fit_step": 0,
+                  "view_weighted_mse_stack_step": 0, "view_weighted_mse_stack_fit_step": 0}
 
 
 def _stack_lights(light, light_intensity) -> Tuple[int, int]:
@@ -1202,18 +1241,18 @@ class _MseStackStepFn(torch.autograd.Function):
     gradients, backward hands them over scaled by the upstream gradient on the device; a second backward evaluates again -- as _MseStepFn."""
 
     @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, targets, kwargs):
-        maps = (albedo, normal, roughness, metallic, specular)
+    def forward(ctx, albedo, normal, roughness, metallic, specular, targets, kwargs, weights):
+        maps, kind = (albedo, normal, roughness, metallic, specular), _step_kind("stack", weights)
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, _, loss = _launch_loss_step("stack", _step_plan(maps, kwargs), maps, targets, wanted)
-        _keep_step(ctx, "stack", maps, targets, kwargs, wanted, (bufs, None))
+        bufs, _, loss = _launch_loss_step(kind, _step_plan(maps, kwargs), maps, targets, wanted, weights=weights)
+        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, None), weights=weights)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         grads, _ = _kept_step(ctx)
         _scale_step_gradients(grads, grad_loss)
-        return (*grads, None, None)
+        return (*grads, None, None, None)
 
 
 class _MseStackFitFn(torch.autograd.Function):
@@ -1223,11 +1262,11 @@ class _MseStackFitFn(torch.autograd.Function):
     read-back, so a whole step captures into a graph; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
 
     @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs):
-        maps, params = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity)
+    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs, weights):
+        maps, params, kind = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity), _step_kind("fit", weights)
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, gp, loss = _launch_loss_step("fit", _step_plan(maps, kwargs, params), maps, targets, wanted)
-        _keep_step(ctx, "fit", maps, targets, kwargs, wanted, (bufs, gp), params)
+        bufs, gp, loss = _launch_loss_step(kind, _step_plan(maps, kwargs, params), maps, targets, wanted, weights=weights)
+        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, gp), params, weights)
         return loss
 
     @staticmethod
@@ -1255,7 +1294,7 @@ def _fit_step_backward(ctx, grad_loss):
         g = (gp if ctx.params[i].is_cuda else host)[first:first + 3 * rows]
         return _param_grad(g if i == 0 else g.reshape(rows, 3), ctx.params[i], L if i == 2 else 1)
     pgrads = [part(0, 0, first // 3), part(1, first, L), part(2, first + 3 * L, L)]
-    return (*grads, *pgrads, None, None)
+    return (*grads, *pgrads, None, None, None)
 
 
 class _CameraStackStepFn(torch.autograd.Function):
@@ -1263,18 +1302,18 @@ class _CameraStackStepFn(torch.autograd.Function):
     pbr_cook_torrance_camera_mse_stack_step, gives the loss over the L images and the map gradients summed over the lights."""
 
     @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, targets, kwargs):
-        maps = (albedo, normal, roughness, metallic, specular)
+    def forward(ctx, albedo, normal, roughness, metallic, specular, targets, kwargs, weights):
+        maps, kind = (albedo, normal, roughness, metallic, specular), _step_kind("camera_stack", weights)
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, _, loss = _launch_loss_step("camera_stack", _step_plan(maps, kwargs), maps, targets, wanted)
-        _keep_step(ctx, "camera_stack", maps, targets, kwargs, wanted, (bufs, None))
+        bufs, _, loss = _launch_loss_step(kind, _step_plan(maps, kwargs), maps, targets, wanted, weights=weights)
+        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, None), weights=weights)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         grads, _ = _kept_step(ctx)
         _scale_step_gradients(grads, grad_loss)
-        return (*grads, None, None)
+        return (*grads, None, None, None)
 
 
 class _CameraStackFitFn(torch.autograd.Function):
@@ -1284,11 +1323,11 @@ class _CameraStackFitFn(torch.autograd.Function):
     device are read there at every launch; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
 
     @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs):
-        maps, params = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity)
+    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs, weights):
+        maps, params, kind = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity), _step_kind("camera_fit", weights)
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, gp, loss = _launch_loss_step("camera_fit", _step_plan(maps, kwargs, params), maps, targets, wanted)
-        _keep_step(ctx, "camera_fit", maps, targets, kwargs, wanted, (bufs, gp), params)
+        bufs, gp, loss = _launch_loss_step(kind, _step_plan(maps, kwargs, params), maps, targets, wanted, weights=weights)
+        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, gp), params, weights)
         return loss
 
     @staticmethod
@@ -1302,18 +1341,18 @@ class _ViewStackStepFn(torch.autograd.Function):
     differentiated: that is _ViewStackFitFn) because the positions travel beside the plan."""
 
     @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs):
-        maps, params = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity)
+    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs, weights):
+        maps, params, kind = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity), _step_kind("view_stack", weights)
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, _, loss = _plan_and_launch("view_stack", maps, kwargs, params, targets, wanted)
-        _keep_step(ctx, "view_stack", maps, targets, kwargs, wanted, (bufs, None), params)
+        bufs, _, loss = _plan_and_launch(kind, maps, kwargs, params, targets, wanted, weights)
+        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, None), params, weights)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         grads, _ = _kept_step(ctx)
         _scale_step_gradients(grads, grad_loss)
-        return (*grads, None, None, None, None, None)
+        return (*grads, None, None, None, None, None, None)
 
 
 class _ViewStackFitFn(torch.autograd.Function):
@@ -1322,11 +1361,11 @@ class _ViewStackFitFn(torch.autograd.Function):
     launch; host positions are re-read at every call; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
 
     @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs):
-        maps, params = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity)
+    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs, weights):
+        maps, params, kind = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity), _step_kind("view_fit", weights)
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, gp, loss = _plan_and_launch("view_fit", maps, kwargs, params, targets, wanted)
-        _keep_step(ctx, "view_fit", maps, targets, kwargs, wanted, (bufs, gp), params)
+        bufs, gp, loss = _plan_and_launch(kind, maps, kwargs, params, targets, wanted, weights)
+        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, gp), params, weights)
         return loss
 
     @staticmethod
@@ -1334,29 +1373,31 @@ class _ViewStackFitFn(torch.autograd.Function):
         return _fit_step_backward(ctx, grad_loss)
 
 
-def _stack_route(maps, params, targets, kwargs, on_device=None):
+def _stack_route(maps, params, targets, kwargs, on_device=None, weights=None):
     """Which one-pass form serves a rendering_loss_mse_stack call: "fit" (_MseStackFitFn: view, a light or an intensity requires grad, with or
     without the maps), "step" (_MseStackStepFn: only maps do) or None (the composition).  Both need plain arguments, untiled maps, every map with
     its own planes, targets that need no grad and maps on a ROCm device (`on_device`: None = ask the albedo).  No rule by L: the fit step was
-    ahead of the composition at every L measured (profiles/light_stack_fit_step.json)."""
+    ahead of the composition at every L measured (profiles/light_stack_fit_step.json).  `weights` (rendering_loss_mse_stack(weights=)) do
+    not change the answer -- "fit" and "step" are then the weighted siblings, _step_kind; no rule by L either: ahead of the composition at every
+    L measured in all three families (profiles/weighted_stack_probe.json) -- unless they require grad: the composition."""
     albedo = maps[0]
     B = albedo.shape[0] if albedo.dim() == 4 else 1
     shared = B > 1 and any(_shared_by_batch(t, B) for t in maps)
     if on_device is None:
         on_device = albedo.is_cuda
-    if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets) or _view_type(kwargs) == "point":
+    if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets, weights) or _view_type(kwargs) == "point":
         return None
     if _needs_grad(*params):
         return "fit"
     return "step" if _needs_grad(*maps) else None
 
 
-def _camera_stack_route(maps, params, targets, kwargs, on_device=None):
+def _camera_stack_route(maps, params, targets, kwargs, on_device=None, weights=None):
     """_stack_route for view_type="point" (`view_dir` is the camera's position): "fit" (_CameraStackFitFn: the position, a light or an
     intensity requires grad, with or without the maps), "step" (_CameraStackStepFn: only maps do) or None (the composition: the stack of
     camera renders and torch's MSE).  The same conditions -- plain arguments, untiled maps, every map with its own planes, targets that need
     no grad, maps on a ROCm device (`on_device`: None = ask the albedo) -- and the view type itself.  No rule by L: both steps were ahead of the
-    composition at every L measured, the single photograph included (profiles/camera_stack_probe.json)."""
+    composition at every L measured, the single photograph included (profiles/camera_stack_probe.json).  `weights`: as for _stack_route."""
     if _view_type(kwargs) != "point":
         return None
     albedo = maps[0]
@@ -1364,45 +1405,62 @@ def _camera_stack_route(maps, params, targets, kwargs, on_device=None):
     shared = B > 1 and any(_shared_by_batch(t, B) for t in maps)
     if on_device is None:
         on_device = albedo.is_cuda
-    if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets):
+    if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets, weights):
         return None
     if _needs_grad(*params):
         return "fit"
     return "step" if _needs_grad(*maps) else None
 
 
-def _view_stack_route(maps, params, targets, kwargs, on_device=None):
+def _view_stack_route(maps, params, targets, kwargs, on_device=None, weights=None):
     """_camera_stack_route for `view_dir` [L,3], one camera position per shot: "fit" (_ViewStackFitFn: the positions, a light or an intensity
     requires grad, with or without the maps), "step" (_ViewStackStepFn: only maps do) or None (the composition: L camera renders and torch's
     MSE).  The camera stack's conditions: view_type="point", plain arguments, untiled maps, every map with its own planes, targets that need
-    no grad, maps on a ROCm device (`on_device`: None = ask the albedo)."""
-    return _camera_stack_route(maps, params, targets, kwargs, on_device)
+    no grad, maps on a ROCm device (`on_device`: None = ask the albedo).  `weights`: as for _stack_route."""
+    return _camera_stack_route(maps, params, targets, kwargs, on_device, weights)
 
 
-def _view_loss_step(route, maps, params, targets, kwargs):
+def _view_loss_step(route, maps, params, targets, kwargs, weights=None):
     """The fused per-shot-camera step `_view_stack_route` chose, or None when the library does not serve the descriptor as one pass."""
     kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED + _PARAM_KEYS}
     try:
-        return (_ViewStackFitFn if route == "fit" else _ViewStackStepFn).apply(*maps, *params, targets, kw)
+        return (_ViewStackFitFn if route == "fit" else _ViewStackStepFn).apply(*maps, *params, targets, kw, weights)
     except _StepNotServed:
         return None
 
 
-def _camera_loss_step(route, maps, params, targets, kwargs):
+def _camera_loss_step(route, maps, params, targets, kwargs, weights=None):
     """The fused camera step `_camera_stack_route` chose, or None when the library does not serve the descriptor as one pass."""
     kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED}
     try:
         if route == "fit":
             kw = {k: v for k, v in kw.items() if k not in _PARAM_KEYS}
-            return _CameraStackFitFn.apply(*maps, *params, targets, kw)
-        return _CameraStackStepFn.apply(*maps, targets, kw)
+            return _CameraStackFitFn.apply(*maps, *params, targets, kw, weights)
+        return _CameraStackStepFn.apply(*maps, targets, kw, weights)
     except _StepNotServed:
         return None
 
 
+def _stack_weights(weights, want) -> None:
+    """Checks the per-pixel weights of a stack loss against the targets' shape `want` = ([B,] L, 3, H, W), from shapes alone: one plane per
+    shot, ([B,] L, 1, H, W), or one plane for all shots, ([B,] 1, 1, H, W).  Raises ValueError for anything else."""
+    per_shot = tuple(want[:-3]) + (1,) + tuple(want[-2:])
+    shared = per_shot[:-4] + (1,) + per_shot[-3:]
+    if not isinstance(weights, torch.Tensor) or tuple(weights.shape) not in (per_shot, shared):
+        raise ValueError("weights must be %s (one plane per shot) or %s (one plane for all shots), got %s"
+                         % (per_shot, shared, tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights)))
+
+
+def _weighted_mse(out, targets, weights):
+    """mean(w (out - targets)^2) over all elements of `out`, `w` broadcast over the channels (and over the shots, for one plane): what the
+    weighted steps compute, composed from torch ops -- differentiable in everything, the weights included."""
+    d = out.float() - targets.to(out.device, torch.float32).reshape(out.shape)
+    return (weights.to(out.device, torch.float32) * d * d).mean()
+
+
 def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], roughness: torch.Tensor,
                              metallic: Optional[torch.Tensor] = None, specular: Optional[torch.Tensor] = None, *,
-                             targets: torch.Tensor, **kwargs) -> torch.Tensor:
+                             targets: torch.Tensor, weights: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
     """`torch.nn.MSELoss()(cook_torrance_stack(albedo, normal, roughness, metallic | specular, **kwargs), targets)`: the rendering loss over a
     stack of L photographs `targets` [L,3,H,W] / [B,L,3,H,W], as a 0-dim tensor on the maps' device; the gradient of each map is the sum over
     the lights.  ONE pass over the maps under the conditions `rendering_loss_mse` uses -- something requires grad, the targets do not, plain
@@ -1414,7 +1472,18 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
     gradient is the position's.  `view_dir` [L,3] is one view per shot (`cook_torrance_stack`): with view_type="point" the two passes are
     pbr_cook_torrance_view_mse_stack_step and pbr_cook_torrance_view_mse_stack_fit_step, and the positions' gradient comes back [L,3] like
     the tensor passed; with view_type="directional" it is the composition.  Every other case (tiled maps, maps shared by the batch, targets
-    that require grad, no gradients wanted) is the stack followed by torch's MSE: same value to fp32 rounding, same gradients."""
+    that require grad, no gradients wanted) is the stack followed by torch's MSE: same value to fp32 rounding, same gradients.
+
+    `weights` (optional) is one weight per pixel for a capture with a mask -- coverage that differs from shot to shot, clipped highlights,
+    confidence: [L,1,H,W] / [B,L,1,H,W], one plane per shot, or [1,1,H,W] / [B,1,1,H,W], one plane for all shots, H and W the targets'.  The
+    loss is then `(weights * (stack - targets) ** 2).mean()`, the weight broadcast over the three channels: the mean is still over all
+    3 B L H W elements, the sum of the weights is not used (for the mean over valid pixels divide by the constant `weights.mean()`).  The
+    one-pass routes are taken under the same conditions, through the weighted siblings of the six entry points
+    (pbr_cook_torrance_weighted_mse_stack_step ...); weights that require grad take the composition, which honours them too.  The kernels
+    read contiguous float32 weights on the maps' device: any other dtype (`bool` and `uint8` masks included) or device is converted with
+    `.to(float32)` at every call, which is a copy.  No sign check: a negative weight is the caller's business.  A weight of exactly 0 beside
+    a finite target and a finite render contributes exactly 0 to the loss and to every gradient; a NaN target under a zero weight still
+    gives NaN (0 * NaN).  `weights=None` is the unweighted call in every respect."""
     L, _ = _stack_lights(kwargs.get("light"), kwargs.get("light_intensity"))
     per_shot = kwargs.get("view_dir") is not None and _stack_views(kwargs["view_dir"], L) > 1
     if not isinstance(albedo, torch.Tensor) or albedo.dim() not in (3, 4):
@@ -1424,22 +1493,26 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
     want = ((L, 3, H, nx * albedo.shape[-1]) if albedo.dim() == 3 else (albedo.shape[0], L, 3, H, nx * albedo.shape[-1]))
     if not isinstance(targets, torch.Tensor) or tuple(targets.shape) != want:
         raise ValueError("targets must be the stack %s, got %s" % (want, tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets)))
+    if weights is not None:
+        _stack_weights(weights, want)
     maps = (albedo, normal, roughness, metallic, specular)
     params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
     if _view_type(kwargs) == "point":
-        route = (_view_stack_route if per_shot else _camera_stack_route)(maps, params, targets, kwargs)
-        loss = (_view_loss_step if per_shot else _camera_loss_step)(route, maps, params, targets, kwargs) if route is not None else None
+        route = (_view_stack_route if per_shot else _camera_stack_route)(maps, params, targets, kwargs, None, weights)
+        loss = (_view_loss_step if per_shot else _camera_loss_step)(route, maps, params, targets, kwargs, weights) if route is not None else None
         if loss is not None:
             return loss
-    route = None if per_shot else _stack_route(maps, params, targets, kwargs)      # one orthographic direction per shot: the composition
+    route = None if per_shot else _stack_route(maps, params, targets, kwargs, None, weights)      # one orthographic direction per shot: the composition
     if route is not None:
         kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED}
         try:
             if route == "fit":
                 kw = {k: v for k, v in kw.items() if k not in _PARAM_KEYS}
-                return _MseStackFitFn.apply(albedo, normal, roughness, metallic, specular, *params, targets, kw)
-            return _MseStackStepFn.apply(albedo, normal, roughness, metallic, specular, targets, kw)
+                return _MseStackFitFn.apply(albedo, normal, roughness, metallic, specular, *params, targets, kw, weights)
+            return _MseStackStepFn.apply(albedo, normal, roughness, metallic, specular, targets, kw, weights)
         except _StepNotServed:
             pass
     out = cook_torrance_stack(albedo, normal, roughness, metallic, specular, **kwargs)
+    if weights is not None:
+        return _weighted_mse(out, targets, weights)
     return torch.nn.functional.mse_loss(out.float(), targets.to(out.device, torch.float32))

@@ -35,8 +35,10 @@ class RenderingLoss(nn.Module):
         store = material.__dict__.get("_store", {})
         return [store.get(k) for k in ("albedo", "normal", "roughness", "metallic", "specular")]
 
-    def forward(self, predicted_material, ground_truth_material):
-        """`ground_truth_material`: a material, or the reference rendering itself ((3,H,W) / (B,3,H,W) tensor)."""
+    def forward(self, predicted_material, ground_truth_material, weights=None):
+        """`ground_truth_material`: a material, or the reference rendering itself ((3,H,W) / (B,3,H,W) tensor).  `weights` (an extension):
+        one weight per pixel, (1,H,W) / (B,1,H,W); the loss is `(weights * (rendering - reference) ** 2).mean()`
+        (functional.rendering_loss_mse(weights=))."""
         if isinstance(ground_truth_material, torch.Tensor):
             rendered_gt = ground_truth_material
         else:
@@ -59,12 +61,14 @@ class RenderingLoss(nn.Module):
                    and (self.brdf.view_type != "point" or predicted_material.lazy_tile == (1, 1)))   # the camera renders real maps: the module materialises
         if not fusable:
             rendered_pred = self.brdf(predicted_material, self.view_dir, self.light_dir, self.light_intensity, self.light_size)
+            if weights is not None:
+                return F_._weighted_mse(rendered_pred, rendered_gt, weights)
             return nn.MSELoss()(rendered_pred, rendered_gt.to(rendered_pred.device))
         if m is not None:
             s = None
         return F_.rendering_loss_mse(a, n, r, m, s, target=rendered_gt.to(a.device), view_dir=self.view_dir, light=self.light_dir,
                                      light_intensity=self.light_intensity, light_type=self.brdf.light_type, light_size=self.light_size,
-                                     view_type=self.brdf.view_type,
+                                     view_type=self.brdf.view_type, **({} if weights is None else {"weights": weights}),
                                      tile=predicted_material.lazy_tile,      # a recorded tile(n): evaluated and differentiated at every repeat
                                      albedo_is_srgb=bool(predicted_material.albedo_is_srgb),
                                      specular_is_srgb=bool(getattr(predicted_material, "specular_is_srgb", True)))
@@ -84,7 +88,10 @@ class MultiLightRenderingLoss(nn.Module):
     (pbr_cook_torrance_camera_stack, pbr_cook_torrance_camera_mse_stack_step, pbr_cook_torrance_camera_mse_stack_fit_step), under the same
     rules; the gradient `view_dir` receives is the position's.  `view_dir` [L,3] is one view per shot -- with view_type='point' a handheld
     capture, the camera moving with the flash -- and reaches functional's per-shot routes (pbr_cook_torrance_view_stack,
-    pbr_cook_torrance_view_mse_stack_step, pbr_cook_torrance_view_mse_stack_fit_step); its gradient comes back [L,3]."""
+    pbr_cook_torrance_view_mse_stack_step, pbr_cook_torrance_view_mse_stack_fit_step); its gradient comes back [L,3].
+    `forward(..., weights=)` takes one weight per pixel -- a mask of what each photograph covers, clipped highlights, confidence --
+    [L,1,H,W] / [B,L,1,H,W] or one plane for all shots, [1,1,H,W] / [B,1,1,H,W]: the loss is `(weights * (stack - photographs) ** 2).mean()`
+    and the one-pass forms are the weighted ones (functional.rendering_loss_mse_stack(weights=))."""
 
     def __init__(self, light_type='point', view_dir=torch.tensor([0.0, 0.0, 1.0]), lights=torch.tensor([[0.1, 0.1, 1.0]]),
                  light_intensities=torch.tensor([1.0, 1.0, 1.0]), light_size=None, view_type='directional'):
@@ -125,8 +132,8 @@ class MultiLightRenderingLoss(nn.Module):
         return torch.stack([self.brdf(material, vt[l] if self._views > 1 else self.view_dir, lt[l], it[l if self._rows > 1 else 0], self.light_size)
                             for l in range(self.n_lights)], dim=-4)
 
-    def forward(self, predicted_material, ground_truth):
-        """`ground_truth`: a material, or the stack of photographs ([L,3,H,W] / [B,L,3,H,W] tensor)."""
+    def forward(self, predicted_material, ground_truth, weights=None):
+        """`ground_truth`: a material, or the stack of photographs ([L,3,H,W] / [B,L,3,H,W] tensor); `weights`: see the class."""
         if isinstance(ground_truth, torch.Tensor):
             targets = ground_truth
         else:
@@ -141,5 +148,8 @@ class MultiLightRenderingLoss(nn.Module):
         maps = self._plain_maps(predicted_material)
         if maps is None:
             rendered = self._render(predicted_material)
+            if weights is not None:
+                return F_._weighted_mse(rendered, targets, weights)
             return nn.MSELoss()(rendered, targets.to(rendered.device))
-        return F_.rendering_loss_mse_stack(*maps, targets=targets.to(maps[0].device), **self._kwargs(predicted_material))
+        return F_.rendering_loss_mse_stack(*maps, targets=targets.to(maps[0].device), **({} if weights is None else {"weights": weights}),
+                                           **self._kwargs(predicted_material))
