@@ -745,6 +745,42 @@ typedef struct pbr_image_pack {
 int pbr_pack_images(const pbr_image_pack *maps, int32_t n_maps, int32_t height, int32_t width, void *stream);
 
 /*
+ * Photograph rectification (no upstream counterpart; csrc/rectify.hip): n_images photographs, uint8 samples as PIL hands them out, are
+ * warped onto the height x width texture grid by one 3x3 homography each, and come out as what the light-stack loss steps take:
+ * targets [n_images][3][height][width] and coverage weights [n_images][height][width], float32, dense.  The definition, for output pixel
+ * (y, x) of image l with M = homographies[l] (row-major), S = supersample and the sub-samples i, j < S:
+ *   1. X = x + (i + 0.5) / S, Y = y + (j + 0.5) / S: output pixel centres sit at + 0.5, the grid spans [0, width] x [0, height];
+ *   2. d = m20 X + m21 Y + m22, u = (m00 X + m01 Y + m02) / d - 0.5, v = (m10 X + m11 Y + m12) / d - 0.5: source pixel centres sit at
+ *      + 0.5, so u, v are in index units;
+ *   3. the sub-sample is OUTSIDE when d <= 0, u or v is not finite, u <= -1, u >= src_width, v <= -1 or v >= src_height;
+ *   4. otherwise the bilinear taps at (floor u, floor v) and its three neighbours, weights from fx = u - floor u, fy = v - floor v.  A tap
+ *      whose index lies outside the image contributes 0 (zeros padding: F.grid_sample(mode="bilinear", padding_mode="zeros",
+ *      align_corners=False)); with clip_level = k in 1..255 a tap with any of its three samples >= k (an exact integer comparison)
+ *      counts as outside the image too, in the value and in the coverage.
+ *   value_c = sum of w_t * sample_tc / 255 over all taps of all sub-samples, / S^2; coverage = the sum of w_t over the same taps, / S^2;
+ *   with to_linear every tap's sample / 255 goes through pbr_srgb_to_linear's function before it is weighted.
+ *   weights = coverage, in [0, 1]; targets_c = clamp(value_c / coverage, 0, 1) where coverage > 0 and exactly 0 where coverage == 0, so a
+ *   masked-out target is always finite.  No per-pixel threshold: value and coverage are continuous in the coordinates.
+ * sample / 255 is the IEEE quotient of pbr_unpack_image: for a homography that is an integer translation, with S = 1, the targets are
+ * pbr_unpack_image's floats bit for bit and the weights exactly 1 inside the image, exactly 0 outside.  The projective map is evaluated in
+ * float64 (u = numerator * (1 / d): 1.5 ulp of a double), fx and fy are rounded to float32 after the floor, weights and sums are float32:
+ * within (4 S^2 + 4) * 2^-24 <= 4.1e-6 of the definition in exact arithmetic, for source images of any size.
+ * `src` is addressed as src[l*src_image_stride + y*src_stride_h + x*src_stride_w + c*src_stride_c] (strides in samples, none negative);
+ * only channels c = 0..2 are read, so an RGBA array travels as it is (stride_w 4) and a dense RGB array has stride_w 3.  `homographies`
+ * is HOST memory, [n_images][9], read at the call: the matrices travel in the kernel arguments (1152 bytes at most), ONE launch serves
+ * all images.  A width % 4 == 0 with both outputs 16-byte aligned is written 4 pixels per lane, one 16-byte store per plane; everything
+ * else one pixel per lane, with the same bits.  Every element of both outputs is written exactly once; no workspace, no atomics;
+ * deterministic.  Caller errors, before anything is launched: a NULL pointer PBR_ERR_NULL_MAP; n_images outside
+ * [1, PBR_MAX_RECTIFY_IMAGES], an extent < 1, height or width > 2^30, height * width > 2^40, supersample not 1, 2 or 4, clip_level outside
+ * [0, 255] (0: off), a negative stride, a homography entry that is not finite PBR_ERR_SHAPE.  (ABI 9: an entry point added, nothing changed.)
+ */
+#define PBR_MAX_RECTIFY_IMAGES 16
+int pbr_rectify_images(const void *src, int32_t n_images, int32_t src_height, int32_t src_width, int64_t src_image_stride,
+                       int64_t src_stride_h, int64_t src_stride_w, int64_t src_stride_c, const double *homographies, float *targets,
+                       float *weights, int32_t height, int32_t width, int32_t supersample, int32_t clip_level, int32_t to_linear,
+                       void *stream);
+
+/*
  * MaterialBase.resize, base.py:490-504 (torchvision resize of a float (C,H,W) map ==
  * F.interpolate(mode="bilinear", align_corners=False, antialias=...)).  fp32 planar
  * [planes][h_in][w_in] -> [planes][h_out][w_out]; `workspace` holds the width-pass

@@ -28,6 +28,7 @@ sibling modules, one per file of csrc/, and their names are imported back below,
   _geometry     PlaneMap, fold_stages, check_crop, remap_planes                                         csrc/geometry.hip
   _packing      unpack_planes, pack_planes, the plane-op tables                                         csrc/packing.hip
   _rotate_ops   rotate_plan, rotate_indices, rotate_maps                                                csrc/rotation.hip
+  capture       homography_from_corners, rectify, camera_positions (photographs -> targets and weights)  csrc/rectify.hip
   functional    descriptors, RenderPlan, cook_torrance, the autograd bridges, rendering_loss_mse,       csrc/ct_*.hip/.hpp, torch_ops.cpp
                 light stacks (cook_torrance_stack, rendering_loss_mse_stack)
 
@@ -66,6 +67,7 @@ from ._packing import (  # noqa: F401
     _unpack_raw, pack_planes, unpack_planes)
 from ._rotate_ops import (  # noqa: F401
     PADDING_MODES, _ROTATE_PLANS, RotatePlan, _RotateFn, _make_rotate_plan, _rotate_geom, _rotate_raw, rotate_indices, rotate_maps, rotate_plan)
+from .capture import camera_positions, homography_from_corners, rectify  # noqa: F401
 
 TensorLike = Union[torch.Tensor, Sequence[float]]
 
