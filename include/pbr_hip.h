@@ -781,6 +781,47 @@ int pbr_rectify_images(const void *src, int32_t n_images, int32_t src_height, in
                        void *stream);
 
 /*
+ * Photometric-stereo initialisation (no upstream counterpart; csrc/photometric.hip): a rectified light stack -- what pbr_rectify_images
+ * writes -- becomes the maps a fit starts from, by a Lambertian least-squares solve per pixel with reweighting passes against attached
+ * shadows.  Inputs: `targets` [n_shots][3][height][width] float32, dense; `weights` [n_shots][height][width], or ONE plane
+ * [height][width] for all shots (weights_shared != 0), or NULL (every weight 1); `lights` and `intensities`, HOST memory, [n_shots][3]
+ * floats each, read at the call (they travel in the kernel arguments: 16 x 6 values at most) -- point-light positions or directions
+ * (light_type PBR_LIGHT_POINT | PBR_LIGHT_DIRECTIONAL) and the RGB intensity of every shot.  The definition, for output pixel (y, x) at
+ * P = (xs[x], -ys[y], 0), xs and ys the point light's grid (linspace(-s/2, s/2, .) per axis in float32, s = light_size, 0 meaning 1.0,
+ * exactly as pbr_cook_torrance forms it; cooktorrance.py:132-140):
+ *   1. geometry per shot l.  Point light: d = light_l - P, w_l = d / (|d| + 1e-7), a_l = 1 / (|d|^2 + 1e-7).  Directional light:
+ *      w_l = light_l / max(|light_l|, 1e-12), a_l = 1.
+ *   2. observation per shot.  r_lc = lin(T_lc) / (I_lc a_l), lin = pbr_srgb_to_linear's function (input clamped to [0, 1]) with
+ *      targets_srgb, the identity without; y_l = (r_l0 + r_l1 + r_l2) / 3.
+ *   3. reweighted least squares.  m_l = 1; for pass k = 0 .. iterations - 1: u_l = weight_l m_l.  Shots with u_l == 0 are SKIPPED BY
+ *      SELECTION, not multiplied: a NaN target under a zero weight does no harm (unlike the loss steps, where 0 * NaN is NaN).
+ *      A = sum u_l w_l w_l^T, b = sum u_l y_l w_l; t = tr A; c = det A / (t/3)^3 if t > 0, else 0 (c is in [0, 1] by the AM-GM
+ *      inequality).  c < min_condition: the pixel is INVALID, stop.  g = A^-1 b through the adjugate.  |g| zero or not finite, or
+ *      g_z <= 0: INVALID, stop.  If k < iterations - 1: m_l = [w_l . g > shadow_cos |g|], the attached-shadow mask the current solution
+ *      predicts.  (A pass whose mask equals the one before it repeats that pass: an implementation may stop there.)
+ *   4. normal.  Valid: n = g / |g|, with u_l and c of the last pass.  Invalid: n = (0, 0, 1) exactly, and u_l = weight_l.
+ *   5. albedo.  s_l = max(w_l . n, 0); albedo_c = clamp(pi sum u_l s_l r_lc / sum u_l s_l^2, 0, 1), exactly 0 where the denominator
+ *      is 0 (shots with u_l == 0 skipped as in 3.); with albedo_srgb the result goes through pbr_linear_to_srgb's function.
+ *   6. outputs, float32, dense: `normal` [3][height][width], the vector form a material's normal holds; `albedo` [3][height][width];
+ *      `confidence` [height][width], c for a valid pixel and exactly 0 for an invalid one -- confidence > 0 is the validity mask, since
+ *      min_condition > 0.
+ * The solve is Lambertian and view-independent: no camera enters.  Arithmetic is float32 (hardware rcp, rsqrt, sqrt, log2, exp2 at
+ * about 1 ulp each; 1 / I_lc is formed in double on the host); the error grows with 1 / c.  A width % 4 == 0 with all
+ * five device pointers 16-byte aligned is read and written 4 pixels per lane, 16 bytes per access; everything else one pixel per lane,
+ * with the same bits.  ONE launch; every element of the three outputs is written exactly once; no workspace, no atomics; deterministic.
+ * Caller errors, before anything is launched: a NULL `targets`, `lights`, `intensities`, `normal`, `albedo` or `confidence`
+ * PBR_ERR_NULL_MAP; n_shots outside [1, PBR_MAX_PHOTOMETRIC_SHOTS], an extent < 1, height or width > 2^30, height * width > 2^40,
+ * iterations outside [1, 4], shadow_cos outside [0, 1), min_condition outside (0, 1), an unknown light_type, a light or intensity entry
+ * (or, for a point light, a light_size) that is not finite, an intensity <= 0 PBR_ERR_SHAPE.  (ABI 9: an entry point added, nothing
+ * changed.)
+ */
+#define PBR_MAX_PHOTOMETRIC_SHOTS 16
+int pbr_photometric_stereo(const float *targets, const float *weights, int32_t weights_shared, int32_t n_shots, int32_t height,
+                           int32_t width, const float *lights, const float *intensities, int32_t light_type, float light_size,
+                           int32_t targets_srgb, int32_t iterations, float shadow_cos, float min_condition, int32_t albedo_srgb,
+                           float *normal, float *albedo, float *confidence, void *stream);
+
+/*
  * MaterialBase.resize, base.py:490-504 (torchvision resize of a float (C,H,W) map ==
  * F.interpolate(mode="bilinear", align_corners=False, antialias=...)).  fp32 planar
  * [planes][h_in][w_in] -> [planes][h_out][w_out]; `workspace` holds the width-pass

@@ -48,7 +48,7 @@ EXPORTS = (
     "pbr_rotate_planes", "pbr_rotate_planes_backward",
     "pbr_normal_divergence", "pbr_normal_divergence_backward", "pbr_poisson_scale", "pbr_height_workspace_bytes", "pbr_height_stats",
     "pbr_height_normalize", "pbr_height_normalize_backward",
-    "pbr_pack_images", "pbr_rectify_images",
+    "pbr_pack_images", "pbr_rectify_images", "pbr_photometric_stereo",
     "pbr_cook_torrance_stack", "pbr_cook_torrance_mse_stack_step",
     "pbr_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_mse_stack_fit_step",
     "pbr_cook_torrance_camera", "pbr_camera_backward_workspace_bytes", "pbr_cook_torrance_camera_backward",
@@ -128,6 +128,7 @@ class PlaneOp(ctypes.Structure):
 
 MAX_IMAGE_PACKS = 8
 MAX_RECTIFY_IMAGES = 16
+MAX_PHOTOMETRIC_SHOTS = 16
 
 
 class ImagePack(ctypes.Structure):
@@ -277,6 +278,11 @@ def lib():
     #  height, width, supersample, clip_level, to_linear, stream)
     L.pbr_rectify_images.argtypes = [vp, i32, i32, i32, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_double), vp, vp, i32, i32, i32, i32, i32, vp]
     L.pbr_rectify_images.restype = ctypes.c_int
+    # (targets, weights | NULL, weights_shared, n_shots, height, width, HOST lights float[L][3], HOST intensities float[L][3], light_type,
+    #  light_size, targets_srgb, iterations, shadow_cos, min_condition, albedo_srgb, normal, albedo, confidence, stream)
+    L.pbr_photometric_stereo.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), i32,
+                                         ctypes.c_float, i32, i32, ctypes.c_float, ctypes.c_float, i32, vp, vp, vp, vp]
+    L.pbr_photometric_stereo.restype = ctypes.c_int
     f32 = ctypes.c_float
     L.pbr_normal_from_height.argtypes = [vp, i64, vp, i64, i64, i32, i32, i32, f32, i32, ctypes.c_int, vp]
     L.pbr_normal_from_height_backward.argtypes = [vp, i64, vp, i64, i64, vp, i64, i32, i32, i32, f32, i32, vp]

@@ -5,6 +5,10 @@
                             on the texture grid, ONE kernel pass (csrc/rectify.hip, pbr_rectify_images)
   camera_positions          homographies + a focal length -> where each shot was taken from, the [L,3] `view_dir` of view_type="point"
                                                                                                         (host, float64)
+  photometric_stereo        targets, weights and the lights of the shots -> the normal, albedo and confidence a fit STARTS from: a
+                            Lambertian least-squares solve per pixel, re-solved with the predicted attached shadows masked out, ONE kernel
+                            pass (csrc/photometric.hip, pbr_photometric_stereo)
+  initial_material          ... as a BasecolorMetallicMaterial with a constant roughness and metallic 0
 
 The conventions (include/pbr_hip.h, pbr_rectify_images, is the definition; tools/rectify_oracle.py restates it in numpy float64):
 output pixel (y, x) has its centre at (x + 0.5, y + 0.5), so the grid spans [0, W] x [0, H]; a homography M maps such a continuous grid
@@ -25,7 +29,8 @@ from . import _native as N
 from . import _upload as U
 from ._dispatch import launch
 
-CALLS = {"rectify_images": 0}            # pbr_rectify_images calls since import (one per chunk of N.MAX_RECTIFY_IMAGES photographs)
+# calls since import: pbr_rectify_images (one per chunk of N.MAX_RECTIFY_IMAGES photographs), pbr_photometric_stereo (one per call)
+CALLS = {"rectify_images": 0, "photometric_stereo": 0}
 
 
 def _size(size, what: str) -> Tuple[int, int]:
@@ -230,3 +235,122 @@ def camera_positions(homographies, size, source_size, focal_px: float, principal
         R = Uu @ np.diag([1.0, 1.0, np.linalg.det(Uu @ Vt)]) @ Vt
         out[l] = -R.T @ G[:, 2]
     return torch.from_numpy(out)
+
+
+_LIGHT_TYPES = {"directional": N.LIGHT_DIRECTIONAL, "point": N.LIGHT_POINT}
+
+
+def _host_rows(v, what: str) -> np.ndarray:
+    """A tensor on any device or a sequence -> float64 [rows,3] on the host (a device tensor is read back: one synchronisation)."""
+    try:
+        m = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        if m.dtype.kind not in "fiu":
+            raise TypeError
+        m = m.astype(np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("photometric_stereo: %s must be numbers, got %r" % (what, type(v))) from None
+    if m.ndim == 1 and m.shape[0] == 3:
+        m = m[None]
+    if m.ndim != 2 or m.shape[1] != 3 or m.shape[0] < 1:
+        raise ValueError("photometric_stereo: %s must be [L,3]%s, got %s" % (what, " or [3]" if what == "light_intensity" else "", m.shape))
+    return m
+
+
+def photometric_stereo(targets: torch.Tensor, weights: Optional[torch.Tensor] = None, *, light, light_intensity, light_type: str = "point",
+                       light_size: Optional[float] = None, targets_srgb: bool = True, iterations: int = 3, shadow_cos: float = 0.1,
+                       min_condition: float = 1e-4, albedo_srgb: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """A rectified light stack -> (normal [3,H,W], albedo [3,H,W], confidence [1,H,W]), float32 on the targets' device: the maps to START a
+    fit from, in one pass of csrc/photometric.hip (include/pbr_hip.h, pbr_photometric_stereo, is the definition).
+
+    targets          [L,3,H,W] float32 on a ROCm device, 1 <= L <= 16 (`rectify`'s first result); made contiguous if it is not.
+    weights          [L,1,H,W] (`rectify`'s second result), [1,1,H,W] (one plane for all shots) or None (all 1).  Another dtype (`bool` and
+                     `uint8` masks included) or device is converted with `.to(float32)`, as the stack loss steps do.  A shot whose weight is
+                     exactly 0 at a pixel is SKIPPED there, not multiplied by 0: a NaN target under a zero weight does no harm -- unlike the
+                     loss steps, where 0 * NaN is NaN.
+    light            [L,3]: point-light positions on the grid P = (xs, -ys, 0), xs, ys = linspace(-s/2, s/2, .), s = light_size or 1.0 --
+                     the coordinates `cook_torrance(light_type="point")` uses -- or directions for light_type="directional".
+    light_intensity  [3] / [1,3] for all shots, or [L,3]; every entry > 0.
+                     Both may be tensors on any device or sequences; they are read to the HOST at the call and travel in the kernel's
+                     arguments, so a device tensor costs a synchronisation -- acceptable for a step that runs once per fit.
+    targets_srgb     the targets are sRGB-encoded (what `rectify` gives without to_linear, what return_srgb=True renders).
+    iterations       1..4 solves: the first uses every shot, each later one masks the shots the solution before it puts in attached shadow
+                     (w_l . n <= shadow_cos).  The clamp in N.L is what breaks linearity; on exactly Lambertian data with 17 % of the
+                     observations shadowed one solve leaves 50.5 % of the pixels more than 0.01 degrees off, two 8.7 %, three none.
+    shadow_cos       in [0, 1).
+    min_condition    in (0, 1): a pixel whose normal matrix has det A / (tr A / 3)^3 below it (fewer than three independent lit shots) is
+                     INVALID: normal exactly (0, 0, 1), confidence exactly 0, albedo from all its shots.  `confidence > 0` is the validity mask.
+    albedo_srgb      sRGB-encode the albedo (what a material with albedo_is_srgb=True holds).
+
+    The solve is Lambertian and view-independent: no camera enters, and a specular lobe biases it (a rough dielectric: half a degree in
+    the median).  Not differentiable.  Every bad argument raises ValueError before any device work."""
+    what = "photometric_stereo"
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 4 or targets.shape[1] != 3 or min(targets.shape) < 1:
+        raise ValueError("%s: targets must be [L,3,H,W] (batched captures are not supported), got %s"
+                         % (what, tuple(targets.shape) if isinstance(targets, torch.Tensor) else type(targets)))
+    if targets.dtype != torch.float32:
+        raise ValueError("%s: targets must be float32, got %s" % (what, targets.dtype))
+    L, _, H, W = targets.shape
+    if L > N.MAX_PHOTOMETRIC_SHOTS:
+        raise ValueError("%s: at most %d shots, got %d" % (what, N.MAX_PHOTOMETRIC_SHOTS, L))
+    shared = False
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or tuple(weights.shape) not in ((L, 1, H, W), (1, 1, H, W)):
+            raise ValueError("%s: weights must be %s (one plane per shot) or %s (one plane for all shots), got %s"
+                             % (what, (L, 1, H, W), (1, 1, H, W), tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights)))
+        shared = weights.shape[0] == 1 and L > 1
+    if light_type not in _LIGHT_TYPES:
+        raise ValueError("%s: light_type must be 'point' or 'directional', got %r" % (what, light_type))
+    lights = _host_rows(light, "light")
+    inten = _host_rows(light_intensity, "light_intensity")
+    if lights.shape[0] != L:
+        raise ValueError("%s: %d lights for %d shots" % (what, lights.shape[0], L))
+    if inten.shape[0] not in (1, L):
+        raise ValueError("%s: light_intensity must be [3], [1,3] or [%d,3], got %s" % (what, L, inten.shape))
+    inten = np.ascontiguousarray(np.broadcast_to(inten, (L, 3)))
+    if not np.isfinite(lights).all() or not np.isfinite(inten).all():
+        raise ValueError("%s: a light or intensity entry is not finite" % what)
+    if not (inten > 0).all() or not (inten.astype(np.float32) > 0).all():
+        raise ValueError("%s: every light_intensity entry must be > 0" % what)
+    size = float(light_size) if light_size else 0.0                                 # `light_size or 1.0`: None and 0 mean 1.0 (the library's rule)
+    if not np.isfinite(size):
+        raise ValueError("%s: light_size must be finite, got %r" % (what, light_size))
+    if isinstance(iterations, bool) or int(iterations) != iterations or not 1 <= int(iterations) <= 4:
+        raise ValueError("%s: iterations must be 1, 2, 3 or 4, got %r" % (what, iterations))
+    tau, kappa = float(shadow_cos), float(min_condition)
+    if not 0.0 <= tau < 1.0 or not np.float32(tau) < 1.0:
+        raise ValueError("%s: shadow_cos must be in [0, 1), got %r" % (what, shadow_cos))
+    if not 0.0 < kappa < 1.0 or not 0.0 < np.float32(kappa) < 1.0:
+        raise ValueError("%s: min_condition must be in (0, 1), got %r" % (what, min_condition))
+    if not targets.is_cuda:
+        raise ValueError("%s: targets must be on a ROCm device, got %s (there is no CPU path)" % (what, targets.device))
+    N.require_device()
+    dev = targets.device
+    t = targets.detach().contiguous()
+    w = None if weights is None else weights.detach().to(dev, torch.float32).contiguous()
+    normal = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    albedo = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+    confidence = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+    rows = (ctypes.c_float * (3 * L))(*lights.reshape(-1).tolist())
+    ints = (ctypes.c_float * (3 * L))(*inten.reshape(-1).tolist())
+    launch(dev, N.lib().pbr_photometric_stereo, t.data_ptr(), None if w is None else w.data_ptr(), 1 if shared else 0, L, H, W, rows, ints,
+           _LIGHT_TYPES[light_type], size, 1 if targets_srgb else 0, int(iterations), tau, kappa, 1 if albedo_srgb else 0,
+           normal.data_ptr(), albedo.data_ptr(), confidence.data_ptr())
+    CALLS["photometric_stereo"] += 1
+    return normal, albedo, confidence
+
+
+def initial_material(targets: torch.Tensor, weights: Optional[torch.Tensor] = None, roughness: float = 0.5, **kwargs):
+    """`photometric_stereo(targets, weights, **kwargs)` as the material a fit starts from: a BasecolorMetallicMaterial holding that normal,
+    the albedo sRGB-encoded (albedo_is_srgb=True), a constant `roughness` plane and metallic 0 -- ready to have `requires_grad_` set on its
+    maps and to go into MultiLightRenderingLoss.  `albedo_srgb` is not a keyword here: the material's albedo is always encoded."""
+    from .materials import BasecolorMetallicMaterial
+    if "albedo_srgb" in kwargs:
+        raise ValueError("initial_material: the material's albedo is always sRGB-encoded; albedo_srgb is not an argument")
+    rough = float(roughness)
+    if not 0.0 <= rough <= 1.0:
+        raise ValueError("initial_material: roughness must be in [0, 1], got %r" % (roughness,))
+    normal, albedo, _ = photometric_stereo(targets, weights, albedo_srgb=True, **kwargs)
+    H, W = albedo.shape[-2:]
+    return BasecolorMetallicMaterial(albedo=albedo, albedo_is_srgb=True, normal=normal,
+                                     roughness=torch.full((1, H, W), rough, dtype=torch.float32, device=albedo.device),
+                                     metallic=torch.zeros((1, H, W), dtype=torch.float32, device=albedo.device))
