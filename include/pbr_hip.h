@@ -876,6 +876,79 @@ int pbr_blend_sigmoid_mask_backward(const void *mask, const void *grad_out, void
                                     void *stream);
 int pbr_blend_gradient_mask(void *mask, int32_t height, int32_t width, int vertical, void *stream);
 
+/* ---- the optimiser step of a fit (csrc/adam.hip; pypbr_amd.optim.MaterialAdam) ------ */
+
+/*
+ * Projected Adam over a table of at most PBR_MAX_ADAM_TENSORS tensors, ONE launch.  Per element, with the coefficients of the entry's
+ * group (a = lr / (1 - beta1^t), c = 1 / sqrt(1 - beta2^t), formed in float64 by the caller or by pbr_adam_advance):
+ *     m <- m + (g - m) (1 - beta1)        v <- beta2 v + (1 - beta2) g g        delta = a m / (sqrt(v) c + eps)        p <- p - delta
+ * -- torch.optim.Adam (weight_decay 0, no amsgrad, no maximize) in exact arithmetic -- and then the entry's projection of p:
+ *   PBR_ADAM_NONE   nothing
+ *   PBR_ADAM_BOX    min(max(p, lo), hi); -INFINITY / +INFINITY leave a side open
+ *   PBR_ADAM_UNIT   (channels == 3) z <- max(z, min_z) (-INFINITY: no floor), then p / max(|p|, 1e-12) over the pixel's three planes
+ * An element whose delta is exactly 0 (for UNIT: all three of the pixel) keeps the bits of its parameter: it is neither clamped nor
+ * renormalised (a pixel no gradient ever reached).  Non-finite gradients propagate.  m, v (and `master`) are dense fp32 in the
+ * parameter's logical order [batch][channels][pixels]; the parameter and its gradient, of the entry's `dtype`, have dense planes of
+ * `pixels` elements at the given plane / batch strides (in elements).  PBR_F16 parameters carry an fp32 `master` copy: the update and the
+ * projection run on the master, and the parameter receives the master rounded to nearest even in the same pass (an element that keeps
+ * its bits keeps the master's too); PBR_F32 parameters pass master = NULL.  Every element of p, m, v, master is read once and written
+ * once, g is read once.  Accesses are 16 bytes wide (8 for fp16) for an entry whose pointers, strides and `pixels` are whole quads,
+ * element by element otherwise.
+ * The coefficients: `coeffs_host` (n_groups rows, copied into the kernel's arguments) or `coeffs_device` (n_groups rows of device memory
+ * the kernel reads when it RUNS: a captured graph replays with whatever pbr_adam_advance wrote there) -- exactly one of the two.
+ * Caller errors, before anything is launched: a NULL table, both or neither coefficient table, a NULL p / g / m / v, a PBR_F16 entry
+ * without master PBR_ERR_NULL_MAP; n_tensors or n_groups outside [1, PBR_MAX_ADAM_TENSORS], batch / channels / pixels < 1, a negative
+ * stride, planes or images of p on top of each other, lo > hi, a group index outside the table, a pointer off its element's alignment,
+ * anything written that overlaps anything else the launch reads or writes (p and g of one entry included) PBR_ERR_SHAPE; UNIT with
+ * channels != 3 PBR_ERR_CHANNELS; an unknown projection, a master behind a PBR_F32 entry PBR_ERR_UNSUPPORTED; a dtype PBR_ERR_DTYPE.
+ * No workspace.  (ABI 9: entry points added, nothing changed.)
+ */
+enum { PBR_ADAM_NONE = 0, PBR_ADAM_BOX = 1, PBR_ADAM_UNIT = 2 };
+#define PBR_MAX_ADAM_TENSORS 16
+#define PBR_ADAM_BLOCK 256            /* lanes of a workgroup; a lane takes one quad (or one element) of a plane per trip of its loop */
+#define PBR_ADAM_MAX_BLOCKS 1024      /* workgroups per tensor at the most: planes of more than 256 x 1024 quads make a lane loop */
+typedef struct pbr_adam_tensor {
+    void *param;
+    const void *grad;
+    float *exp_avg;               /* m */
+    float *exp_avg_sq;            /* v */
+    float *master;                /* PBR_F16: the fp32 copy the update runs on; PBR_F32: NULL */
+    int64_t pixels;               /* elements of one plane */
+    int64_t param_batch_stride, param_plane_stride;
+    int64_t grad_batch_stride, grad_plane_stride;
+    int32_t batch, channels;
+    int32_t dtype;                /* PBR_F32 | PBR_F16: param and grad */
+    int32_t project;              /* PBR_ADAM_* */
+    float lo, hi;                 /* BOX */
+    float min_z;                  /* UNIT */
+    int32_t group;                /* row of the coefficient table */
+} pbr_adam_tensor;
+typedef struct pbr_adam_coeffs {
+    float a, c, one_minus_beta1, beta2, one_minus_beta2, eps;
+} pbr_adam_coeffs;
+int pbr_adam_step(const pbr_adam_tensor *tensors, int32_t n_tensors, const pbr_adam_coeffs *coeffs_host, const void *coeffs_device,
+                  int32_t n_groups, void *stream);
+/* What pbr_adam_step checks about its table before it launches, alone: PBR_OK, or the caller error it would return.  Launches nothing.
+ * The overlap test is exact for strided entries (plane by plane where the planes are not back to back): the maps of a batch packed
+ * material by material interleave -- material 0's normal lies between material 0's and material 1's albedo -- and are accepted. */
+int pbr_adam_check(const pbr_adam_tensor *tensors, int32_t n_tensors, int32_t n_groups);
+/* sizeof(pbr_adam_tensor) as compiled: bindings check their struct layout against it. */
+size_t pbr_adam_tensor_size(void);
+/*
+ * The step counters of a capturable optimiser, ONE lane: for every row i < n_groups, *step <- *step + 1 (a DEVICE float, torch's
+ * capturable `step`; every counter appears in one row only), t = the new value, and row i of `coeffs_device` (pbr_adam_coeffs) receives
+ * a = lr / (1 - beta1^t), c = 1 / sqrt(1 - beta2^t), formed in float64 on the device and rounded once, with 1 - beta1, beta2, 1 - beta2
+ * and eps.  lr is `lr`, or -- `lr_device` not NULL -- the DEVICE float it points to, read when the kernel runs.  The only place where t
+ * enters: a captured graph of pbr_adam_advance + pbr_adam_step(coeffs_device) replays correctly.  A NULL table, counter or coefficient
+ * table PBR_ERR_NULL_MAP; n_groups outside [1, PBR_MAX_ADAM_TENSORS] PBR_ERR_SHAPE.
+ */
+typedef struct pbr_adam_group {
+    void *step;
+    const void *lr_device;
+    double lr, beta1, beta2, eps;
+} pbr_adam_group;
+int pbr_adam_advance(const pbr_adam_group *groups, int32_t n_groups, void *coeffs_device, void *stream);
+
 /* ---- introspection; the process-global tuning hook (tests, benches, profiling) ------ */
 int pbr_abi_version(void);
 /* First 16 hex digits of the SHA-256 over the sources this library was built from (every .hip and .hpp file of csrc, this header, the Makefile,

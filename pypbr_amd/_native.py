@@ -59,6 +59,7 @@ EXPORTS = (
     "pbr_cook_torrance_weighted_mse_stack_step", "pbr_cook_torrance_weighted_mse_stack_fit_step",
     "pbr_cook_torrance_camera_weighted_mse_stack_step", "pbr_cook_torrance_camera_weighted_mse_stack_fit_step",
     "pbr_cook_torrance_view_weighted_mse_stack_step", "pbr_cook_torrance_view_weighted_mse_stack_fit_step",
+    "pbr_adam_step", "pbr_adam_check", "pbr_adam_tensor_size", "pbr_adam_advance",
 )
 
 
@@ -136,6 +137,33 @@ class ImagePack(ctypes.Structure):
     _fields_ = [("src", ctypes.c_void_p), ("stride_c", ctypes.c_int64), ("stride_h", ctypes.c_int64), ("stride_w", ctypes.c_int64),
                 ("dst", ctypes.c_void_p), ("channels", ctypes.c_int32), ("bits", ctypes.c_int32), ("encode_normal", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+
+ADAM_NONE, ADAM_BOX, ADAM_UNIT = 0, 1, 2
+MAX_ADAM_TENSORS = 16
+ADAM_BLOCK, ADAM_MAX_BLOCKS = 256, 1024      # PBR_ADAM_BLOCK, PBR_ADAM_MAX_BLOCKS: a lane loops on planes of more than 256 x 1024 quads
+
+
+class AdamTensor(ctypes.Structure):
+    """pbr_adam_tensor: one parameter of a pbr_adam_step table (strides in elements; m, v, master dense fp32)."""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("master", ctypes.c_void_p), ("pixels", ctypes.c_int64),
+                ("param_batch_stride", ctypes.c_int64), ("param_plane_stride", ctypes.c_int64),
+                ("grad_batch_stride", ctypes.c_int64), ("grad_plane_stride", ctypes.c_int64),
+                ("batch", ctypes.c_int32), ("channels", ctypes.c_int32), ("dtype", ctypes.c_int32), ("project", ctypes.c_int32),
+                ("lo", ctypes.c_float), ("hi", ctypes.c_float), ("min_z", ctypes.c_float), ("group", ctypes.c_int32)]
+
+
+class AdamCoeffs(ctypes.Structure):
+    """pbr_adam_coeffs: what one group's step needs (a = lr / (1 - beta1^t), c = 1 / sqrt(1 - beta2^t))."""
+    _fields_ = [("a", ctypes.c_float), ("c", ctypes.c_float), ("one_minus_beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+                ("one_minus_beta2", ctypes.c_float), ("eps", ctypes.c_float)]
+
+
+class AdamGroup(ctypes.Structure):
+    """pbr_adam_group: one row of pbr_adam_advance (a DEVICE float counter; lr from the host value or a DEVICE float)."""
+    _fields_ = [("step", ctypes.c_void_p), ("lr_device", ctypes.c_void_p), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
 
 
 class RotateGeom(ctypes.Structure):
@@ -337,6 +365,14 @@ def lib():
     L.pbr_blend_sigmoid_mask_backward.restype = ctypes.c_int
     for name in ("pbr_blend_maps", "pbr_blend_sigmoid_mask", "pbr_blend_gradient_mask"):
         getattr(L, name).restype = ctypes.c_int
+    L.pbr_adam_step.argtypes = [ctypes.POINTER(AdamTensor), i32, ctypes.POINTER(AdamCoeffs), vp, i32, vp]
+    L.pbr_adam_step.restype = ctypes.c_int
+    L.pbr_adam_check.argtypes = [ctypes.POINTER(AdamTensor), i32, i32]
+    L.pbr_adam_check.restype = ctypes.c_int
+    L.pbr_adam_tensor_size.argtypes = []
+    L.pbr_adam_tensor_size.restype = ctypes.c_size_t
+    L.pbr_adam_advance.argtypes = [ctypes.POINTER(AdamGroup), i32, vp, vp]
+    L.pbr_adam_advance.restype = ctypes.c_int
     L.pbr_render_desc_size.restype = ctypes.c_size_t
     L.pbr_build_id.argtypes = []
     L.pbr_build_id.restype = ctypes.c_char_p
@@ -345,6 +381,8 @@ def lib():
     if L.pbr_render_desc_size() != ctypes.sizeof(RenderDesc):
         raise NativeLibraryError("pbr_render_desc layout mismatch: library %d bytes, binding %d"
                                  % (L.pbr_render_desc_size(), ctypes.sizeof(RenderDesc)))
+    if L.pbr_adam_tensor_size() != ctypes.sizeof(AdamTensor):
+        raise NativeLibraryError("pbr_adam_tensor layout mismatch: library %d bytes, binding %d" % (L.pbr_adam_tensor_size(), ctypes.sizeof(AdamTensor)))
     if L.pbr_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libpbr_hip.so ABI %d, binding expects %d" % (L.pbr_abi_version(), ABI_VERSION))
     for env, knob in tuple(("PBR_TUNE_" + name.upper(), index) for name, index in TUNE_NAMES.items()):      # profiling runs: knobs from the environment
