@@ -237,35 +237,20 @@ def lib():
     L.pbr_cook_torrance_camera_backward.restype = ctypes.c_int
     L.pbr_cook_torrance_camera_stack.argtypes = [ctypes.POINTER(RenderDesc), vp]
     L.pbr_cook_torrance_camera_stack.restype = ctypes.c_int
-    L.pbr_cook_torrance_camera_mse_stack_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_camera_mse_stack_step.restype = ctypes.c_int
-    L.pbr_camera_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_camera_mse_stack_fit_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_cook_torrance_camera_mse_stack_fit_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_camera_mse_stack_fit_step.restype = ctypes.c_int
     # one camera position per shot: (desc, cameras_host float[L][3] | NULL, cameras_device | NULL, ...) -- exactly one of the two
     fp = ctypes.POINTER(ctypes.c_float)
     L.pbr_cook_torrance_view_stack.argtypes = [ctypes.POINTER(RenderDesc), fp, vp, vp]
     L.pbr_cook_torrance_view_stack.restype = ctypes.c_int
-    L.pbr_cook_torrance_view_mse_stack_step.argtypes = [ctypes.POINTER(RenderDesc), fp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_view_mse_stack_step.restype = ctypes.c_int
-    L.pbr_view_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_view_mse_stack_fit_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_cook_torrance_view_mse_stack_fit_step.argtypes = [ctypes.POINTER(RenderDesc), fp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_view_mse_stack_fit_step.restype = ctypes.c_int
-    # the weighted stack steps: the unweighted call's arguments with (weights, w_batch_stride, w_light_stride) behind the targets
-    i64 = ctypes.c_int64
+    # the twelve light-stack loss steps: (desc, [the shots' cameras,] targets, [weights, w_batch_stride, w_light_stride,] g_* (5), [g_params,]
+    # loss, workspace, stream), and the three families' fit-size queries
     for family, before in (("", []), ("camera_", []), ("view_", [fp, vp])):
-        for step, pointers in (("step", 8), ("fit_step", 9)):      # the g_* (5), [g_params], loss, workspace, stream
-            fn = getattr(L, "pbr_cook_torrance_%sweighted_mse_stack_%s" % (family, step))
-            fn.argtypes = [ctypes.POINTER(RenderDesc)] + before + [vp, vp, i64, i64] + [vp] * pointers
-            fn.restype = ctypes.c_int
-    L.pbr_cook_torrance_mse_stack_step.argtypes =[ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_mse_stack_step.restype = ctypes.c_int
-    L.pbr_mse_stack_fit_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_mse_stack_fit_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_cook_torrance_mse_stack_fit_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_mse_stack_fit_step.restype = ctypes.c_int
+        for weighted, beside in (("", []), ("weighted_", [vp, i64, i64])):
+            for step, pointers in (("step", 8), ("fit_step", 9)):
+                fn = getattr(L, "pbr_cook_torrance_%s%smse_stack_%s" % (family, weighted, step))
+                fn.argtypes = [ctypes.POINTER(RenderDesc)] + before + [vp] + beside + [vp] * pointers
+                fn.restype = ctypes.c_int
+        query = getattr(L, "pbr_%smse_stack_fit_workspace_bytes" % family)
+        query.argtypes, query.restype = [ctypes.POINTER(RenderDesc)], ctypes.c_size_t
     L.pbr_scale_by_device_scalar.argtypes = [vp, sz, ctypes.c_int, vp, vp]
     L.pbr_scale_by_device_scalar.restype = ctypes.c_int
     L.pbr_scale_list_by_device_scalar.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_int, ctypes.c_int, vp, vp]

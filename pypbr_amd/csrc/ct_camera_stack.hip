@@ -12,7 +12,7 @@
 // type (pixel_view, material_terms / bwd_decode, light_geom, shade_light / eval_light, colour_adjoint<true>, backprop_light, bwd_tail, the
 // StackMseLoss policy); the frame loss_step / backward_body_to is not used, because it reads ONE view for the launch (view_of).  The gradient
 // of the position is ct_camera.hip's: (g_v - v (v . g_v)) / |C - P| per pixel, applied BEFORE the sum over pixels.
-#include "ct_camera_stack.hpp"
+#include "ct_stack_host.hpp"
 
 namespace pbr {
 
@@ -170,6 +170,9 @@ static LossStepFn pick_camera_stack_step(bool half_maps, int vec) {
     return vec == 2 ? cook_torrance_camera_mse_stack_step_kernel<L, W, 2, float, PGRAD> : cook_torrance_camera_mse_stack_step_kernel<L, W, 1, float, PGRAD>;
 }
 
+static const auto camera_stack_kernel = [](auto L, auto W, bool half_maps, int vec) { return pick_camera_stack<L(), W()>(half_maps, vec); };
+static const auto camera_stack_step_kernel = [](auto L, auto W, auto PGRAD, bool half_maps, int vec) { return pick_camera_stack_step<L(), W(), PGRAD()>(half_maps, vec); };
+
 }  // namespace pbr
 
 extern "C" {
@@ -178,68 +181,27 @@ int pbr_cook_torrance_camera_stack(const pbr_render_desc *d, void *stream) {
     using namespace pbr;
     const TuningScope tuning(d);
     const int rc = camera_gate(d);
-    if (rc != PBR_OK) return rc;
-    if (d->out_batch_stride != 0 || d->out_channel_stride != 0) return PBR_ERR_UNSUPPORTED;      // the stack is one contiguous block
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t plane = (int64_t)d->height * d->width;
-    if (nan_grid(d))             // every view vector, hence every value of every image, is NaN
-        return call_status(hipMemsetD32Async((hipDeviceptr_t)d->out, 0x7fc00000, (size_t)(plane * 3 * d->n_lights * d->batch), st));
-    const int vec = (g_max_vec == 1 || d->width < 4) ? 1 : 4;       // ragged widths: the last lane of a row overlaps its neighbour (lane_pos)
-    KArgs k;
-    camera_args(d, vec, k, 0);
-    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
-    k.o_cs = plane; k.o_bs = 3 * plane * d->n_lights;
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const KernelFn fn = with_light_workflow(d, [&](auto L, auto W) -> KernelFn { return pick_camera_stack<L(), W()>(half_maps, vec); });
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), 0, st, k);
-    return launch_status();
+    return rc != PBR_OK ? rc : launch_stack(d, nan_grid(d), camera_args, camera_stack_kernel, stream);
 }
 
 int pbr_cook_torrance_camera_mse_stack_step(const pbr_render_desc *d, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
                                             void *g_metallic, void *g_specular, void *loss, void *workspace, void *stream) {
     using namespace pbr;
-    const TuningScope tuning(d);
-    const int rc = camera_step_gate(d, targets && loss && workspace);
-    if (rc != PBR_OK) return rc;
-    const int vec = mse_vec(d);
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const LossStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> LossStepFn { return pick_camera_stack_step<L(), W(), false>(half_maps, vec); });
-    const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *const partials = static_cast<float *>(workspace);
-    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
-    KArgs k;
-    const int e = launch_camera_loss_step(d, fn, vec, b, targets, count, partials, st, k);
-    return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
+    return stack_loss_step<kCamera, false>(d, false, camera_stack_step_kernel,
+                                           {targets, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr, loss, workspace, stream, {}, {}});
 }
 
-size_t pbr_camera_mse_stack_fit_workspace_bytes(const pbr_render_desc *d) {
+size_t pbr_camera_mse_stack_fit_workspace_bytes(const pbr_render_desc *d) {      // the orthographic fit layout
     using namespace pbr;
-    {
-        const TuningScope tuning(d);
-        if (camera_step_gate(d, true) != PBR_OK) return 0;
-    }
-    return pbr_mse_stack_fit_workspace_bytes(d);      // the orthographic fit layout: loss partials and their stage sums, the rows, their stage sums
+    const TuningScope tuning(d);
+    return stack_fit_workspace_bytes(d, camera_step_gate(d, true) == PBR_OK, 3, 6);
 }
 
 int pbr_cook_torrance_camera_mse_stack_fit_step(const pbr_render_desc *d, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
                                                 void *g_metallic, void *g_specular, void *g_params, void *loss, void *workspace, void *stream) {
     using namespace pbr;
-    const TuningScope tuning(d);
-    const int rc = camera_step_gate(d, g_params && targets && loss && workspace);
-    if (rc != PBR_OK) return rc;
-    const int vec = mse_vec(d);
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const LossStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> LossStepFn { return pick_camera_stack_step<L(), W(), true>(half_maps, vec); });
-    const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *const partials = static_cast<float *>(workspace);
-    float *const rows = reinterpret_cast<float *>(static_cast<char *>(workspace) + pbr_mse_step_workspace_bytes(d));      // one row per workgroup
-    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, rows};
-    KArgs k;
-    int e = launch_camera_loss_step(d, fn, vec, b, targets, count, partials, st, k);
-    if (e == PBR_OK) e = param_grad_finish(d, rows, k.n_tiles, k.dev, static_cast<float *>(g_params), st, true);
-    return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
+    return stack_loss_step<kCamera, false>(d, true, camera_stack_step_kernel,
+                                           {targets, g_albedo, g_normal, g_roughness, g_metallic, g_specular, g_params, loss, workspace, stream, {}, {}});
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 // ct_view_stack.hip hold the same statements INLINE and stay that way: called through these functions every one of their 96 instantiations
 // comes out with other scalar loads and another schedule (tried three ways; backward_body_to keeps its decode inline for the same reason),
 // and their instructions are what the measurements of DESIGN.md 3.19 / 3.20 stand on.  Change the two together.
-// Also here: the shots' camera positions as a kernel argument (ViewArgs) and the host-side launch with arguments beside BArgs.
+// Also here: the shots' camera positions as a kernel argument (ViewArgs).  The host side of the steps: ct_stack_host.hpp.
 #pragma once
 #include "ct_camera.hpp"
 
@@ -226,24 +226,6 @@ static ViewArgs view_args(const pbr_render_desc *d, const float *cameras_host, c
     if (cameras_host) std::memcpy(v.cam, cameras_host, sizeof(float) * 3 * (size_t)d->n_lights);
     v.dev = reinterpret_cast<uint64_t>(cameras_device);
     return v;
-}
-
-// launch_loss_step (ct_loss.hip) with the camera's kernel arguments: that launcher fills them itself (fill_args normalises the view), and
-// here the view must stay the position as given (camera_args).  Everything else is its statements: one-wave workgroups of `vec` pixels per
-// lane, contiguous target and gradient planes, scale = 2 / count, never more workgroups than the rows' size query promised.  `beside`: what
-// the kernel takes between BArgs and the targets (the shots' positions, the weights), as kernel arguments of their own.
-template <class Fn, class... Beside>
-static int launch_camera_loss_step(const pbr_render_desc *d, Fn fn, int vec, const BArgs &b, const void *targets, double count,
-                                   float *partials, hipStream_t st, KArgs &k, const Beside &...beside) {
-    camera_args(d, vec, k, 6);
-    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
-    if (b.g_param_partials) {
-        const int64_t most = max_tiles(d);
-        if (most < 0 || k.n_tiles > most) return PBR_ERR_SHAPE;
-    }
-    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, beside..., static_cast<const float *>(targets), (float)(2.0 / count), partials);
-    return launch_status();
 }
 
 }  // namespace pbr

@@ -300,19 +300,16 @@ int launch_repeat_backward(const pbr_render_desc *d, const void *upstream, void 
 bool repeat_blend_backward_serves(const pbr_render_desc *d);
 int launch_repeat_blend_backward(const pbr_render_desc *d, const void *kblend, const void *grad_out, const void *g1, const void *g2, hipStream_t st);
 
-// The loss steps (ct_loss.hip; the light-stack steps of ct_stack.hip are built from the same pieces).  An entry point is: mse_gate, pick the
-// kernel, launch_loss_step, mse_finish.
+// The loss steps (ct_loss.hip; the light-stack steps are built from the same pieces: ct_stack_host.hpp).  An entry point is: mse_gate, pick the
+// kernel, launch_loss_step (ct_stack_host.hpp: the one-wave launch; leaves its KArgs in `k`), mse_finish.
 //   mse_gate: valid descriptor, the caller's pointers, fp32 result, no NaN grid, untiled maps unless the step has a tiled form that serves them
 //   mse_vec: pixels per lane of a loss step (no lane may count a pixel twice)
-//   launch_loss_step: the one-wave launch of a kernel over ct_backward.hpp's loss_step frame; leaves its KArgs in `k`
 //   mse_finish: the step's partial sums -> *loss = sum / count through the reduction kernels (fp64, fixed order), the stage sums where
 //   pbr_mse_step_workspace_bytes put them
 struct BArgs;
 using LossStepFn = void (*)(const KArgs, const BArgs, const float *, float, float *);
 int mse_gate(const pbr_render_desc *d, bool pointers_given, bool tiled_form);
 int mse_vec(const pbr_render_desc *d);
-int launch_loss_step(const pbr_render_desc *d, LossStepFn fn, int vec, const BArgs &b, const void *targets, double count, float *partials,
-                     hipStream_t st, KArgs &k);
 int mse_finish(const pbr_render_desc *d, float *partials, int64_t n_partials, double count, float *loss, hipStream_t st);
 
 // ct_backward.hip: the streamed form (fp16 maps, one light), shared by the backward launcher and the loss step.  stream_run: rounds of the

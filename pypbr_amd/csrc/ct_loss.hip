@@ -14,10 +14,10 @@
 // adds the rows in fp64 in a fixed order (deterministic) and writes mean = sum / N.
 //
 // This file is also the home of what every loss step shares on the host -- this one and the two over light stacks (ct_stack.hip): an entry
-// point is mse_gate, pick the kernel, launch_loss_step, mse_finish (declared in ct_launch.hpp).  What they share on the device is the frame
-// loss_step (ct_backward.hpp, beside the loss policies): a step kernel is that frame with its policy and its first target loads.
+// point is mse_gate, pick the kernel, launch_loss_step (ct_stack_host.hpp), mse_finish (declared in ct_launch.hpp).  What they share on the
+// device is the frame loss_step (ct_backward.hpp, beside the loss policies): a step kernel is that frame with its policy and its first target loads.
 #include "ct_backward_stream.hpp"
-#include "ct_launch.hpp"
+#include "ct_stack_host.hpp"
 
 namespace pbr {
 
@@ -185,23 +185,6 @@ int mse_gate(const pbr_render_desc *d, bool pointers_given, bool tiled_form) {
     return PBR_OK;
 }
 
-// The launch of a one-wave loss step (ct_backward.hpp: loss_step): `vec` pixels per lane (mse_vec) in 64-lane workgroups, one partial sum per
-// workgroup, no LDS reduction; target and gradient planes are contiguous (the stack's strides follow from o_cs and n_lights); scale = 2 / count.
-// With a row of light / view sums per workgroup (b.g_param_partials) never more workgroups than the size query promised.  Leaves the launch's
-// KArgs in `k` (n_tiles = the partial sums to finish, dev for param_grad_finish).
-int launch_loss_step(const pbr_render_desc *d, LossStepFn fn, int vec, const BArgs &b, const void *targets, double count, float *partials,
-                     hipStream_t st, KArgs &k) {
-    fill_args(d, vec, k, 6);
-    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
-    if (b.g_param_partials) {
-        const int64_t most = max_tiles(d);
-        if (most < 0 || k.n_tiles > most) return PBR_ERR_SHAPE;
-    }
-    k.o_cs = (int64_t)d->height * d->width; k.o_bs = 3 * k.o_cs;
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(64, 1, 1), 0, st, k, b, static_cast<const float *>(targets), (float)(2.0 / count), partials);
-    return launch_status();
-}
-
 }  // namespace pbr
 
 extern "C" {
@@ -251,7 +234,7 @@ int pbr_cook_torrance_mse_step(const pbr_render_desc *d, const void *target, voi
         const int vec = mse_vec(d);
         const bool multi = d->n_lights > 1, half_maps = d->map_dtype == PBR_F16;
         const LossStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> LossStepFn { return pick_mse<L(), W()>(half_maps, vec, multi); });
-        e = launch_loss_step(d, fn, vec, b, target, count, partials, st, k);
+        e = launch_loss_step(d, fill_args, fn, vec, b, target, count, partials, st, k);
         n_partials = k.n_tiles;
     }
     return e != PBR_OK ? e : mse_finish(d, partials, n_partials, count, static_cast<float *>(loss), st);

@@ -13,13 +13,12 @@
 // 76 L + 96 (L - 1).  Here the maps are read once, the L targets once, and the summed gradients are written once: 64 + 12 L.  At L = 8 that is
 // 160 against 1280.
 //
-// The step is the frame of the one-wave loss steps (ct_backward.hpp: loss_step; host side ct_loss.hip: mse_gate, launch_loss_step, mse_finish)
+// The step is the frame of the one-wave loss steps (ct_backward.hpp: loss_step; host side ct_stack_host.hpp: stack_loss_step)
 // around backward_body_to with the StackMseLoss policy: texels loaded and decoded once, pixel_terms once, then per light
 // eval_light -> encode with slope -> difference to THAT light's target -> backprop_light into the shared accumulators, and the light-independent
 // tail and the stores once.  No second pass over the lights: the summed-lights form needs one because the summed colour decides the outer clamp;
 // in a stack every image is clamped and encoded by itself.  Light l + 1's target pixels are loaded before light l's arithmetic.
-#include "ct_backward.hpp"
-#include "ct_launch.hpp"
+#include "ct_stack_host.hpp"
 
 namespace pbr {
 
@@ -123,12 +122,14 @@ static KernelFn pick_stack(bool half_maps, int vec) {
     return vec == 4 ? cook_torrance_stack_kernel<L, W, float, 4> : cook_torrance_stack_kernel<L, W, float, 1>;
 }
 
-// What both entry points serve: untiled maps, an fp32 stack, contiguous.
+// What the stack's entry point serves beyond a valid descriptor: an fp32 stack of untiled maps (contiguous: launch_stack asks).
 static int stack_serves(const pbr_render_desc *d) {
     if (d->out_dtype != PBR_F32) return PBR_ERR_DTYPE;
-    if (is_tiled(d) || d->out_batch_stride != 0 || d->out_channel_stride != 0) return PBR_ERR_UNSUPPORTED;
-    return PBR_OK;
+    return is_tiled(d) ? PBR_ERR_UNSUPPORTED : PBR_OK;
 }
+
+static const auto stack_kernel = [](auto L, auto W, bool half_maps, int vec) { return pick_stack<L(), W()>(half_maps, vec); };
+static const auto stack_step_kernel = [](auto L, auto W, auto PGRAD, bool half_maps, int vec) { return pick_stack_step<L(), W(), PGRAD()>(half_maps, vec); };
 
 }  // namespace pbr
 
@@ -139,66 +140,27 @@ int pbr_cook_torrance_stack(const pbr_render_desc *d, void *stream) {
     const TuningScope tuning(d);
     int rc = validate(d);
     if (rc == PBR_OK) rc = stack_serves(d);
-    if (rc != PBR_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t plane = (int64_t)d->height * d->width;
-    if (nan_light_size(d))       // every value of every image is NaN upstream (ct_launch.hpp: fill_result_nan); the stack is one contiguous block
-        return call_status(hipMemsetD32Async((hipDeviceptr_t)d->out, 0x7fc00000, (size_t)(plane * 3 * d->n_lights * d->batch), st));
-    const int vec = (g_max_vec == 1 || d->width < 4) ? 1 : 4;       // ragged widths: the last lane of a row overlaps its neighbour (lane_pos)
-    KArgs k;
-    fill_args(d, vec, k);
-    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
-    k.o_cs = plane; k.o_bs = 3 * plane * d->n_lights;
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const KernelFn fn = with_light_workflow(d, [&](auto L, auto W) -> KernelFn { return pick_stack<L(), W()>(half_maps, vec); });
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), 0, st, k);
-    return launch_status();
+    return rc != PBR_OK ? rc : launch_stack(d, nan_light_size(d), fill_args, stack_kernel, stream);
 }
 
 int pbr_cook_torrance_mse_stack_step(const pbr_render_desc *d, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
                                      void *g_metallic, void *g_specular, void *loss, void *workspace, void *stream) {
     using namespace pbr;
-    const TuningScope tuning(d);
-    const int rc = mse_gate(d, targets && loss && workspace, false);
-    if (rc != PBR_OK) return rc;
-    const int vec = mse_vec(d);
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const LossStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> LossStepFn { return pick_stack_step<L(), W(), false>(half_maps, vec); });
-    const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *const partials = static_cast<float *>(workspace);
-    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
-    KArgs k;
-    const int e = launch_loss_step(d, fn, vec, b, targets, count, partials, st, k);
-    return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
+    return stack_loss_step<kOrthographic, false>(d, false, stack_step_kernel,
+                                                 {targets, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr, loss, workspace, stream, {}, {}});
 }
 
 size_t pbr_mse_stack_fit_workspace_bytes(const pbr_render_desc *d) {
     using namespace pbr;
     const TuningScope tuning(d);
-    if (mse_gate(d, true, false) != PBR_OK) return 0;
-    const size_t loss_part = pbr_mse_step_workspace_bytes(d);      // the loss partials and their stage sums, then the rows, then their stage sums
-    return loss_part == 0 ? 0 : loss_part + param_rows_bytes(d) + param_stage_bytes(d);
+    return stack_fit_workspace_bytes(d, mse_gate(d, true, false) == PBR_OK, 3, 6);
 }
 
 int pbr_cook_torrance_mse_stack_fit_step(const pbr_render_desc *d, const void *targets, void *g_albedo, void *g_normal, void *g_roughness,
                                          void *g_metallic, void *g_specular, void *g_params, void *loss, void *workspace, void *stream) {
     using namespace pbr;
-    const TuningScope tuning(d);
-    const int rc = mse_gate(d, g_params && targets && loss && workspace, false);
-    if (rc != PBR_OK) return rc;
-    const int vec = mse_vec(d);
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const LossStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> LossStepFn { return pick_stack_step<L(), W(), true>(half_maps, vec); });
-    const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *const partials = static_cast<float *>(workspace);
-    float *const rows = reinterpret_cast<float *>(static_cast<char *>(workspace) + pbr_mse_step_workspace_bytes(d));      // one row per workgroup
-    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, rows};
-    KArgs k;
-    int e = launch_loss_step(d, fn, vec, b, targets, count, partials, st, k);
-    if (e == PBR_OK) e = param_grad_finish(d, rows, k.n_tiles, k.dev, static_cast<float *>(g_params), st);
-    return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
+    return stack_loss_step<kOrthographic, false>(d, true, stack_step_kernel,
+                                                 {targets, g_albedo, g_normal, g_roughness, g_metallic, g_specular, g_params, loss, workspace, stream, {}, {}});
 }
 
 }  // extern "C"

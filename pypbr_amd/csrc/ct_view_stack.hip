@@ -19,7 +19,7 @@
 // The positions come beside the descriptor (desc->view_dir and the device block's view are not read): [L][3] host values, which travel in the
 // kernel arguments, or a plain fp32 [L][3] device pointer that the kernel reads, wave-uniformly, when it runs -- no read-back, nothing baked in,
 // so a captured graph sees the positions' current values at every replay.  Lights and intensities: the descriptor or its device_params block.
-#include "ct_camera_stack.hpp"
+#include "ct_stack_host.hpp"
 
 namespace pbr {
 
@@ -185,6 +185,9 @@ static ViewStepFn pick_view_stack_step(bool half_maps, int vec) {
     return vec == 2 ? cook_torrance_view_mse_stack_step_kernel<L, W, 2, float, PGRAD> : cook_torrance_view_mse_stack_step_kernel<L, W, 1, float, PGRAD>;
 }
 
+static const auto view_stack_kernel = [](auto L, auto W, bool half_maps, int vec) { return pick_view_stack<L(), W()>(half_maps, vec); };
+static const auto view_stack_step_kernel = [](auto L, auto W, auto PGRAD, bool half_maps, int vec) { return pick_view_stack_step<L(), W(), PGRAD()>(half_maps, vec); };
+
 }  // namespace pbr
 
 extern "C" {
@@ -195,71 +198,31 @@ int pbr_cook_torrance_view_stack(const pbr_render_desc *d, const float *cameras_
     const int rc = camera_gate(d);
     if (rc != PBR_OK) return rc;
     if (!one_camera_source(cameras_host, cameras_device)) return PBR_ERR_NULL_MAP;
-    if (d->out_batch_stride != 0 || d->out_channel_stride != 0) return PBR_ERR_UNSUPPORTED;      // the stack is one contiguous block
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t plane = (int64_t)d->height * d->width;
-    if (nan_grid(d))             // every view vector, hence every value of every image, is NaN
-        return call_status(hipMemsetD32Async((hipDeviceptr_t)d->out, 0x7fc00000, (size_t)(plane * 3 * d->n_lights * d->batch), st));
-    const int vec = (g_max_vec == 1 || d->width < 4) ? 1 : 4;       // ragged widths: the last lane of a row overlaps its neighbour (lane_pos)
-    KArgs k;
-    camera_args(d, vec, k, 0);
-    if (k.n_tiles < 0) return PBR_ERR_SHAPE;
-    k.o_cs = plane; k.o_bs = 3 * plane * d->n_lights;
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const ViewStackFn fn = with_light_workflow(d, [&](auto L, auto W) -> ViewStackFn { return pick_view_stack<L(), W()>(half_maps, vec); });
-    hipLaunchKernelGGL(fn, dim3((unsigned)k.n_tiles, 1, 1), dim3(1u << k.bt_log2, 1, 1), 0, st, k, view_args(d, cameras_host, cameras_device));
-    return launch_status();
+    return launch_stack(d, nan_grid(d), camera_args, view_stack_kernel, stream, view_args(d, cameras_host, cameras_device));
 }
 
 int pbr_cook_torrance_view_mse_stack_step(const pbr_render_desc *d, const float *cameras_host, const void *cameras_device, const void *targets,
                                           void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic, void *g_specular, void *loss,
                                           void *workspace, void *stream) {
     using namespace pbr;
-    const TuningScope tuning(d);
-    const int rc = camera_step_gate(d, targets && loss && workspace && one_camera_source(cameras_host, cameras_device));
-    if (rc != PBR_OK) return rc;
-    const int vec = mse_vec(d);
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const ViewStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> ViewStepFn { return pick_view_stack_step<L(), W(), false>(half_maps, vec); });
-    const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *const partials = static_cast<float *>(workspace);
-    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr};
-    KArgs k;
-    const int e = launch_camera_loss_step(d, fn, vec, b, targets, count, partials, st, k, view_args(d, cameras_host, cameras_device));
-    return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
+    return stack_loss_step<kShotCameras, false>(d, false, view_stack_step_kernel,
+                                                {targets, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr, loss, workspace, stream,
+                                                 {cameras_host, cameras_device}, {}});
 }
 
-size_t pbr_view_mse_stack_fit_workspace_bytes(const pbr_render_desc *d) {
+size_t pbr_view_mse_stack_fit_workspace_bytes(const pbr_render_desc *d) {      // the camera fit layout with rows of 9 L floats
     using namespace pbr;
-    {
-        const TuningScope tuning(d);
-        if (camera_step_gate(d, true) != PBR_OK || max_tiles(d) < 0) return 0;
-    }
-    const size_t loss_part = pbr_mse_step_workspace_bytes(d);      // the camera fit layout with rows of 9 L floats: loss partials and their stage sums, the rows, their stage sums
-    const int n_param = 9 * d->n_lights;
-    return loss_part == 0 ? 0 : loss_part + param_rows_bytes_of(d, n_param) + param_stage_bytes_of(n_param);
+    const TuningScope tuning(d);
+    return stack_fit_workspace_bytes(d, camera_step_gate(d, true) == PBR_OK && max_tiles(d) >= 0, 0, 9);
 }
 
 int pbr_cook_torrance_view_mse_stack_fit_step(const pbr_render_desc *d, const float *cameras_host, const void *cameras_device, const void *targets,
                                               void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic, void *g_specular,
                                               void *g_params, void *loss, void *workspace, void *stream) {
     using namespace pbr;
-    const TuningScope tuning(d);
-    const int rc = camera_step_gate(d, g_params && targets && loss && workspace && one_camera_source(cameras_host, cameras_device));
-    if (rc != PBR_OK) return rc;
-    const int vec = mse_vec(d);
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const ViewStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> ViewStepFn { return pick_view_stack_step<L(), W(), true>(half_maps, vec); });
-    const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *const partials = static_cast<float *>(workspace);
-    float *const rows = reinterpret_cast<float *>(static_cast<char *>(workspace) + pbr_mse_step_workspace_bytes(d));      // one row per workgroup
-    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, rows};
-    KArgs k;
-    int e = launch_camera_loss_step(d, fn, vec, b, targets, count, partials, st, k, view_args(d, cameras_host, cameras_device));
-    if (e == PBR_OK) e = param_rows_finish(d, rows, k.n_tiles, 3 * d->n_lights, d->n_lights, k.dev, static_cast<float *>(g_params), st);
-    return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
+    return stack_loss_step<kShotCameras, false>(d, true, view_stack_step_kernel,
+                                                {targets, g_albedo, g_normal, g_roughness, g_metallic, g_specular, g_params, loss, workspace, stream,
+                                                 {cameras_host, cameras_device}, {}});
 }
 
 }  // extern "C"

@@ -3,8 +3,7 @@
 // over all 3 B L H W elements (ct_weighted_stack.hpp) -- the handheld capture, whose rectified photographs cover a different part of the
 // texture grid in every shot.  The kernel is cook_torrance_view_mse_stack_step_kernel's sibling: the same body (ct_camera_stack.hpp:
 // view_stack_step), the WeightedStackMseLoss policy.  Workspaces are the unweighted steps'.
-#include "ct_camera_stack.hpp"
-#include "ct_weighted_stack.hpp"
+#include "ct_stack_host.hpp"
 
 namespace pbr {
 
@@ -24,31 +23,7 @@ static WeightedViewStepFn pick_weighted_stack_step(bool half_maps, int vec) {
     return vec == 2 ? cook_torrance_view_weighted_mse_stack_step_kernel<L, W, 2, float, PGRAD> : cook_torrance_view_weighted_mse_stack_step_kernel<L, W, 1, float, PGRAD>;
 }
 
-// Both entry points: g_params = NULL is the step, else the fit step (`fit`: its pointer was asked for).
-static int weighted_view_stack_step(const pbr_render_desc *d, const float *cameras_host, const void *cameras_device, const void *targets,
-                                    const void *weights, int64_t w_batch_stride, int64_t w_light_stride, void *g_albedo, void *g_normal,
-                                    void *g_roughness, void *g_metallic, void *g_specular, bool fit, void *g_params, void *loss, void *workspace,
-                                    void *stream) {
-    const TuningScope tuning(d);
-    int rc = camera_step_gate(d, (!fit || g_params) && targets && weights && loss && workspace && one_camera_source(cameras_host, cameras_device));
-    if (rc == PBR_OK) rc = weights_shape(d, w_light_stride);
-    if (rc != PBR_OK) return rc;
-    const bool half_maps = d->map_dtype == PBR_F16;
-    const int vec = mse_vec(d);
-    const WeightedViewStepFn fn = with_light_workflow(d, [&](auto L, auto W) -> WeightedViewStepFn {
-        return fit ? pick_weighted_stack_step<L(), W(), true>(half_maps, vec) : pick_weighted_stack_step<L(), W(), false>(half_maps, vec);
-    });
-    const double count = 3.0 * (double)d->batch * (double)d->n_lights * (double)d->height * (double)d->width;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    float *const partials = static_cast<float *>(workspace);
-    float *const rows = fit ? reinterpret_cast<float *>(static_cast<char *>(workspace) + pbr_mse_step_workspace_bytes(d)) : nullptr;      // one row per workgroup
-    const BArgs b = {nullptr, g_albedo, g_normal, g_roughness, g_metallic, g_specular, rows};
-    const WArgs w = {static_cast<const float *>(weights), w_batch_stride, w_light_stride};
-    KArgs k;
-    int e = launch_camera_loss_step(d, fn, vec, b, targets, count, partials, st, k, view_args(d, cameras_host, cameras_device), w);
-    if (e == PBR_OK && fit) e = param_rows_finish(d, rows, k.n_tiles, 3 * d->n_lights, d->n_lights, k.dev, static_cast<float *>(g_params), st);
-    return e != PBR_OK ? e : mse_finish(d, partials, k.n_tiles, count, static_cast<float *>(loss), st);
-}
+static const auto weighted_step_kernel = [](auto L, auto W, auto PGRAD, bool half_maps, int vec) { return pick_weighted_stack_step<L(), W(), PGRAD()>(half_maps, vec); };
 
 }  // namespace pbr
 
@@ -58,16 +33,20 @@ int pbr_cook_torrance_view_weighted_mse_stack_step(const pbr_render_desc *d, con
                                                    const void *targets, const void *weights, int64_t w_batch_stride, int64_t w_light_stride,
                                                    void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic, void *g_specular,
                                                    void *loss, void *workspace, void *stream) {
-    return pbr::weighted_view_stack_step(d, cameras_host, cameras_device, targets, weights, w_batch_stride, w_light_stride, g_albedo, g_normal,
-                                         g_roughness, g_metallic, g_specular, false, nullptr, loss, workspace, stream);
+    using namespace pbr;
+    return stack_loss_step<kShotCameras, true>(d, false, weighted_step_kernel,
+                                               {targets, g_albedo, g_normal, g_roughness, g_metallic, g_specular, nullptr, loss, workspace, stream,
+                                                {cameras_host, cameras_device}, {static_cast<const float *>(weights), w_batch_stride, w_light_stride}});
 }
 
 int pbr_cook_torrance_view_weighted_mse_stack_fit_step(const pbr_render_desc *d, const float *cameras_host, const void *cameras_device,
                                                        const void *targets, const void *weights, int64_t w_batch_stride, int64_t w_light_stride,
                                                        void *g_albedo, void *g_normal, void *g_roughness, void *g_metallic, void *g_specular,
                                                        void *g_params, void *loss, void *workspace, void *stream) {
-    return pbr::weighted_view_stack_step(d, cameras_host, cameras_device, targets, weights, w_batch_stride, w_light_stride, g_albedo, g_normal,
-                                         g_roughness, g_metallic, g_specular, true, g_params, loss, workspace, stream);
+    using namespace pbr;
+    return stack_loss_step<kShotCameras, true>(d, true, weighted_step_kernel,
+                                               {targets, g_albedo, g_normal, g_roughness, g_metallic, g_specular, g_params, loss, workspace, stream,
+                                                {cameras_host, cameras_device}, {static_cast<const float *>(weights), w_batch_stride, w_light_stride}});
 }
 
 }  // extern "C"

@@ -32,9 +32,11 @@ sibling modules, one per file of csrc/, and their names are imported back below,
   functional    descriptors, RenderPlan, cook_torrance, the autograd bridges, rendering_loss_mse,       csrc/ct_*.hip/.hpp, torch_ops.cpp
                 light stacks (cook_torrance_stack, rendering_loss_mse_stack)
 
-The one-pass loss steps (_MseStepFn, _MseStackStepFn, _MseStackFitFn ...; the stack classes take optional per-pixel weights) are autograd classes over one frame, said once in front of
-_MseStepFn: two predicates for the callers (_shared_by_batch, _plain_kwargs), one launch (_step_plan, _launch_loss_step), one ctx idiom
-(_keep_step, _kept_step) and the one scaling launch (_scale_step_gradients).
+The one-pass loss steps (_MseStepFn and the six light-stack classes, which take optional per-pixel weights) are autograd classes over one frame, said
+once in front of _MseStepFn: two predicates for the callers (_shared_by_batch, _plain_kwargs), one table of step kinds (_KINDS), one launch
+(_step_plan, _launch_loss_step), one ctx idiom (_keep_step, _kept_step) and the one scaling launch (_scale_step_gradients).  The six stack
+classes are built by one factory (_stack_step_class) from (name, kind, takes_params, fit, doc); one route (_route, by the family's view type)
+and one helper (_one_pass_loss) choose and apply them.
 
 Imports run one way: _native / _caches -> _dispatch -> _upload -> the family modules -> functional.
 """
@@ -833,13 +835,15 @@ class _CookTorranceFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------ the rendering-loss step as one kernel
-# The three steps -- _MseStepFn (one image per material), _MseStackStepFn (a stack of L images), _MseStackFitFn (the stack, with the gradients of
-# view / lights / intensities) -- share one frame:
+# The steps -- _MseStepFn (one image per material) and the six light-stack classes (a stack of L images under the orthographic view, one camera
+# position or one position per shot; each as a step or, with the gradients of view / lights / intensities, a fit step) -- share one frame:
 #   _shared_by_batch, _plain_kwargs   what the callers ask before they route a call to a step
-#   _step_plan, _launch_loss_step     plan without a result; targets, gradient buffers, loss, workspace and the ONE launch
+#   _KINDS                            one row per kind of step: entry point, workspace query, fit / camera / per-shot / weighted
+#   _step_plan, _launch_loss_step     plan without a result; targets, gradient buffers, loss, workspace and the ONE launch, by the kind's row
 #   _keep_step, _kept_step            forward keeps the gradients in ctx; backward hands them over, or evaluates again when they are gone
 #   _scale_step_gradients             the gradients times the upstream gradient of the loss, on the device
-# A step class is its forward (which plan, which inputs are differentiable) and what its backward returns.
+# A step class is its forward (which plan, which inputs are differentiable) and what its backward returns; the six stack classes come out of
+# one factory (_stack_step_class), are chosen by one route (_route) and applied by one helper (_one_pass_loss).
 class _StepNotServed(Exception):
     """pbr_cook_torrance_mse_step does not serve this descriptor as one pass (raised before anything is launched)."""
 
@@ -877,21 +881,27 @@ def _step_plan(maps, kwargs, params=None):
     return plan
 
 
-# kind -> (entry point, workspace query); the stack kinds take [B,L,3,H,W] targets, the fit kinds also leave the 3 + 6 L parameter gradients;
-# the camera kinds are the stack kinds of a plan with view_type="point" (the descriptor's view_dir is the camera's position)
-_STEP_KINDS = {"step": ("pbr_cook_torrance_mse_step", "pbr_mse_step_workspace_bytes"),
-               "stack": ("pbr_cook_torrance_mse_stack_step", "pbr_mse_step_workspace_bytes"),
-               "fit": ("pbr_cook_torrance_mse_stack_fit_step", "pbr_mse_stack_fit_workspace_bytes"),
-               "camera_stack": ("pbr_cook_torrance_camera_mse_stack_step", "pbr_mse_step_workspace_bytes"),
-               "camera_fit": ("pbr_cook_torrance_camera_mse_stack_fit_step", "pbr_camera_mse_stack_fit_workspace_bytes"),
-               "view_stack": ("pbr_cook_torrance_view_mse_stack_step", "pbr_mse_step_workspace_bytes"),
-               "view_fit": ("pbr_cook_torrance_view_mse_stack_fit_step", "pbr_view_mse_stack_fit_workspace_bytes")}
+# The step kinds, one row each.  The stack kinds take [B,L,3,H,W] targets.  fit: the entry point also leaves the parameter gradients.  camera:
+# the plan has view_type="point" (the descriptor's view_dir is the camera's position).  per_shot: one camera position per shot -- the positions
+# travel beside the plan, and a fit row is 9 L floats instead of 3 + 6 L.  weighted: a weight per pixel travels behind the targets.
+_StepKind = collections.namedtuple("_StepKind", "entry query fit camera per_shot weighted")
+_KINDS = {
+    "step": _StepKind("pbr_cook_torrance_mse_step", "pbr_mse_step_workspace_bytes", False, False, False, False),
+    "stack": _StepKind("pbr_cook_torrance_mse_stack_step", "pbr_mse_step_workspace_bytes", False, False, False, False),
+    "fit": _StepKind("pbr_cook_torrance_mse_stack_fit_step", "pbr_mse_stack_fit_workspace_bytes", True, False, False, False),
+    "camera_stack": _StepKind("pbr_cook_torrance_camera_mse_stack_step", "pbr_mse_step_workspace_bytes", False, True, False, False),
+    "camera_fit": _StepKind("pbr_cook_torrance_camera_mse_stack_fit_step", "pbr_camera_mse_stack_fit_workspace_bytes", True, True, False, False),
+    "view_stack": _StepKind("pbr_cook_torrance_view_mse_stack_step", "pbr_mse_step_workspace_bytes", False, True, True, False),
+    "view_fit": _StepKind("pbr_cook_torrance_view_mse_stack_fit_step", "pbr_view_mse_stack_fit_workspace_bytes", True, True, True, False)}
 # ... and the six stack kinds with a weight per pixel (kind + "_w"): the weighted entry point, the unweighted kind's workspace
-_WEIGHTED_KINDS = tuple(k + "_w" for k in _STEP_KINDS if k != "step")
-_STEP_KINDS.update({k + "_w": (e.replace("mse_stack", "weighted_mse_stack"), q) for k, (e, q) in _STEP_KINDS.items() if k != "step"})
-_FIT_KINDS = ("fit", "camera_fit", "view_fit", "fit_w", "camera_fit_w", "view_fit_w")
-_VIEW_KINDS = ("view_stack", "view_fit", "view_stack_w", "view_fit_w")      # one camera position per shot: the positions travel beside the plan, and a fit row is 9 L floats
-_POINT_KINDS = ("camera_stack", "camera_fit", "camera_stack_w", "camera_fit_w") + _VIEW_KINDS
+_KINDS.update({k + "_w": r._replace(entry=r.entry.replace("mse_stack", "weighted_mse_stack"), weighted=True)
+               for k, r in list(_KINDS.items()) if k != "step"})
+# what the tests read, derived: kind -> (entry point, workspace query), and the kinds by column
+_STEP_KINDS = {k: (r.entry, r.query) for k, r in _KINDS.items()}
+_WEIGHTED_KINDS = tuple(k for k, r in _KINDS.items() if r.weighted)
+_FIT_KINDS = tuple(k for k, r in _KINDS.items() if r.fit)
+_VIEW_KINDS = tuple(k for k, r in _KINDS.items() if r.per_shot)
+_POINT_KINDS = tuple(k for k, r in _KINDS.items() if r.camera and not r.per_shot) + _VIEW_KINDS
 
 
 def _step_kind(kind, weights):
@@ -920,8 +930,8 @@ def _launch_loss_step(kind, plan, maps, targets, wanted, cameras=None, weights=N
     `cameras`: the view kinds' [L,3] positions (the plan's own view is not read); their parameter gradients are [9 L].
     `weights`: the weighted kinds' per-pixel weights, in a shape `_stack_weights` accepts; brought to the maps' device as float32 like the
     targets (a copy for any other dtype or device) and handed over as a pointer and two strides in elements."""
-    entry, query = _STEP_KINDS[kind]
-    if (kind in _POINT_KINDS) != (plan.view_type == "point"):
+    row = _KINDS[kind]
+    if row.camera != (plan.view_type == "point"):
         raise ValueError("loss step %r does not take a plan with view_type=%r" % (kind, plan.view_type))
     d = plan.desc
     dev = plan.device                                       # the maps' device: targets handed over on the CPU, or on another GPU, are brought here
@@ -933,26 +943,25 @@ def _launch_loss_step(kind, plan, maps, targets, wanted, cameras=None, weights=N
     # it -- autograd takes ownership of such a gradient instead of cloning it (a 4096^2 fp16 albedo: 73 us per step)
     bufs = [torch.empty(tuple(maps[i].shape), dtype=gdtype, device=dev) if wanted[i] and present[i] else None for i in range(5)]
     loss = torch.empty((), dtype=torch.float32, device=dev)
-    gp = torch.empty((9 if kind in _VIEW_KINDS else 6) * d.n_lights + (0 if kind in _VIEW_KINDS else 3), dtype=torch.float32,
-                     device=dev) if kind in _FIT_KINDS else None
+    gp = torch.empty(9 * d.n_lights if row.per_shot else 3 + 6 * d.n_lights, dtype=torch.float32, device=dev) if row.fit else None
     where = ()
-    if kind in _VIEW_KINDS:
+    if row.per_shot:
         cam_host, cam_dev = _camera_rows(cameras, d.n_lights, dev)
         where = (cam_host, ptr(cam_dev))
     beside = ()
-    if kind in _WEIGHTED_KINDS:
+    if row.weighted:
         plane = d.height * d.width
         w = weights.detach().to(dev, torch.float32).reshape(d.batch, -1, d.height, d.width).contiguous()      # [B, L | 1, H, W]
         beside = (w.data_ptr(), w.shape[1] * plane, plane if w.shape[1] == d.n_lights else 0)
     lib = N.lib()
-    ws_bytes = getattr(lib, query)(ctypes.byref(d))
+    ws_bytes = getattr(lib, row.query)(ctypes.byref(d))
     if ws_bytes == 0:
         raise _StepNotServed()
     ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.float64, device=dev)      # at least the bytes asked for, 8-byte aligned
-    launch(dev, getattr(lib, entry), ctypes.byref(d), *where, tgt.data_ptr(), *beside, *[ptr(b) for b in bufs],
+    launch(dev, getattr(lib, row.entry), ctypes.byref(d), *where, tgt.data_ptr(), *beside, *[ptr(b) for b in bufs],
            *([] if gp is None else [gp.data_ptr()]), loss.data_ptr(), ws.data_ptr())
     if kind != "step":
-        STACK_LAUNCHES[entry[len("pbr_cook_torrance_"):]] += 1
+        STACK_LAUNCHES[row.entry[len("pbr_cook_torrance_"):]] += 1
     return bufs, gp, loss
 
 
@@ -962,7 +971,7 @@ _NO_VIEW = (0.0, 0.0, 1.0)      # the view of a view-stack plan: never read (the
 def _plan_and_launch(kind, maps, kwargs, params, targets, wanted, weights=None):
     """_step_plan and _launch_loss_step for any kind.  The view kinds plan with a placeholder view and hand `params[0]`, the [L,3] positions,
     to the launch."""
-    if kind in _VIEW_KINDS:
+    if _KINDS[kind].per_shot:
         plan = _step_plan(maps, kwargs, (_NO_VIEW, params[1], params[2]))
         return _launch_loss_step(kind, plan, maps, targets, wanted, cameras=params[0], weights=weights)
     return _launch_loss_step(kind, _step_plan(maps, kwargs, params), maps, targets, wanted, weights=weights)
@@ -1110,11 +1119,7 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
         want = tuple(target.shape[:-3]) + (1,) + tuple(target.shape[-2:])
         if not isinstance(weights, torch.Tensor) or tuple(weights.shape) != want or target.dim() != albedo.dim():
             raise ValueError("weights must be %s, got %s" % (want, tuple(weights.shape) if isinstance(weights, torch.Tensor) else type(weights)))
-        try:
-            one_light = _stack_lights(params[1], params[2]) == (1, 1)
-        except (ValueError, TypeError, AttributeError, RuntimeError):
-            one_light = False                                # whatever is wrong with the lights is the evaluation's to say
-        if one_light:                                        # the stack of one image: the same quantity
+        if _one_light(params):                               # the stack of one image: the same quantity
             return rendering_loss_mse_stack(albedo, normal, roughness, metallic, specular, targets=target.unsqueeze(-4),
                                             weights=weights.unsqueeze(-4), **kwargs)
         return _weighted_mse(cook_torrance(albedo, normal, roughness, metallic, specular, **kwargs), target, weights)
@@ -1125,12 +1130,7 @@ def rendering_loss_mse(albedo: torch.Tensor, normal: Optional[torch.Tensor], rou
     camera = _view_type(kwargs) == "point"
     if camera and torch.is_grad_enabled() and isinstance(target, torch.Tensor) and tuple(target.shape) == tuple(albedo.shape[:-3]) + (3,) + tuple(albedo.shape[-2:]):
         # one light: the L = 1 stack step (or fit step); several lights summed into one image have no fused camera form
-        try:
-            one_light = _stack_lights(params[1], params[2]) == (1, 1)
-        except (ValueError, TypeError, AttributeError, RuntimeError):
-            one_light = False                                # whatever is wrong with the lights is the evaluation's to say
-        route = _camera_stack_route(maps, params, target, kwargs) if one_light else None
-        loss = _camera_loss_step(route, maps, params, target, kwargs) if route is not None else None
+        loss = _one_pass_loss(maps, params, target, kwargs) if _one_light(params) else None
         if loss is not None:
             return loss
     if grad_maps and not grad_other and _plain_kwargs(kwargs, _STEP_EXCLUDED) and not shared and albedo.is_cuda and not camera:
@@ -1237,45 +1237,6 @@ def cook_torrance_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor], ro
     return torch.stack(images, dim=-4)
 
 
-class _MseStackStepFn(torch.autograd.Function):
-    """loss = mean((cook_torrance_stack(maps) - targets)^2) with the gradients of the maps, summed over the lights, from ONE kernel
-    (pbr_cook_torrance_mse_stack_step): 64 + 12 L bytes per pixel instead of L loss steps and autograd's accumulation.  Forward keeps the
-    gradients, backward hands them over scaled by the upstream gradient on the device; a second backward evaluates again -- as _MseStepFn."""
-
-    @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, targets, kwargs, weights):
-        maps, kind = (albedo, normal, roughness, metallic, specular), _step_kind("stack", weights)
-        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, _, loss = _launch_loss_step(kind, _step_plan(maps, kwargs), maps, targets, wanted, weights=weights)
-        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, None), weights=weights)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        grads, _ = _kept_step(ctx)
-        _scale_step_gradients(grads, grad_loss)
-        return (*grads, None, None, None)
-
-
-class _MseStackFitFn(torch.autograd.Function):
-    """_MseStackStepFn with view_dir / light / light_intensity as differentiable inputs: ONE kernel (pbr_cook_torrance_mse_stack_fit_step) gives
-    the loss, the map gradients and the (3 + 6 L) gradients of view, lights and intensities -- a capture whose light positions, per-shot
-    intensities or camera axis are fitted, with or without the maps.  Parameters that live on the device are read there (device_params): no
-    read-back, so a whole step captures into a graph; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
-
-    @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs, weights):
-        maps, params, kind = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity), _step_kind("fit", weights)
-        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, gp, loss = _launch_loss_step(kind, _step_plan(maps, kwargs, params), maps, targets, wanted, weights=weights)
-        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, gp), params, weights)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        return _fit_step_backward(ctx, grad_loss)
-
-
 def _fit_step_backward(ctx, grad_loss):
     """What a fit step's backward returns (_MseStackFitFn, _CameraStackFitFn, _ViewStackFitFn): the kept map gradients and the block [view |
     lights L x 3 | intensities L x 3], both scaled by the upstream gradient on the device, the block sliced and shaped like the parameters.
@@ -1285,8 +1246,9 @@ def _fit_step_backward(ctx, grad_loss):
     _scale_step_gradients(grads, grad_loss)
     k = grad_loss.detach().to(gp.device, torch.float32).reshape(1).contiguous()
     launch(gp.device, N.lib().pbr_scale_by_device_scalar, gp.data_ptr(), gp.numel(), N.F32, k.data_ptr())
-    L = gp.numel() // 9 if ctx.kind in _VIEW_KINDS else (gp.numel() - 3) // 6
-    first = 3 * L if ctx.kind in _VIEW_KINDS else 3
+    per_shot = _KINDS[ctx.kind].per_shot
+    L = gp.numel() // 9 if per_shot else (gp.numel() - 3) // 6
+    first = 3 * L if per_shot else 3
     need = [ctx.needs_input_grad[5 + i] for i in range(3)]
     host = gp.cpu() if any(n and not p.is_cuda for n, p in zip(need, ctx.params)) else None      # ONE copy for every parameter held on the CPU
 
@@ -1299,108 +1261,68 @@ def _fit_step_backward(ctx, grad_loss):
     return (*grads, *pgrads, None, None, None)
 
 
-class _CameraStackStepFn(torch.autograd.Function):
-    """_MseStackStepFn under the perspective camera (view_type="point" in `kwargs`: `view_dir` is the camera's position): ONE kernel,
-    pbr_cook_torrance_camera_mse_stack_step, gives the loss over the L images and the map gradients summed over the lights."""
+def _stack_step_class(name, kind, takes_params, fit, doc):
+    """One of the six light-stack step classes: loss = mean(w (stack - targets)^2) with its gradients from ONE kernel, the entry point of `kind`
+    (of its weighted sibling when the call carries weights: _step_kind).  Forward keeps the gradients, backward hands them over scaled by the
+    upstream gradient on the device; a second backward evaluates again -- as _MseStepFn.  `apply(*maps, [view_dir, light, light_intensity,]
+    targets, kwargs, weights)`: with `takes_params` the three parameters are inputs (else the plan reads them from `kwargs`), and with `fit`
+    backward also returns their gradients (_fit_step_backward).  Built with type(), so that autograd names the node `<name>Backward`."""
+    n_inputs = 8 if takes_params else 5
 
-    @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, targets, kwargs, weights):
-        maps, kind = (albedo, normal, roughness, metallic, specular), _step_kind("camera_stack", weights)
+    def forward(ctx, *args):
+        maps, params = args[:5], (args[5:8] if takes_params else None)
+        targets, kwargs, weights = args[n_inputs:]
+        launched = _step_kind(kind, weights)
         wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, _, loss = _launch_loss_step(kind, _step_plan(maps, kwargs), maps, targets, wanted, weights=weights)
-        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, None), weights=weights)
+        bufs, gp, loss = _plan_and_launch(launched, maps, kwargs, params, targets, wanted, weights)
+        _keep_step(ctx, launched, maps, targets, kwargs, wanted, (bufs, gp), params, weights)
         return loss
 
-    @staticmethod
     def backward(ctx, grad_loss):
+        if fit:
+            return _fit_step_backward(ctx, grad_loss)
         grads, _ = _kept_step(ctx)
         _scale_step_gradients(grads, grad_loss)
-        return (*grads, None, None, None)
+        return (*grads, *([None] * (n_inputs - 2)))
+
+    cls = type(name, (torch.autograd.Function,), {"__doc__": doc, "forward": staticmethod(forward), "backward": staticmethod(backward)})
+    cls.takes_params = takes_params
+    return cls
 
 
-class _CameraStackFitFn(torch.autograd.Function):
-    """_MseStackFitFn under the perspective camera: ONE kernel (pbr_cook_torrance_camera_mse_stack_fit_step) gives the loss, the map gradients
-    and the (3 + 6 L) gradients of the camera's position, the lights and the intensities.  The position's gradient is handed back as the
-    kernel summed it (the per-pixel normalisation is differentiated in the kernel; there is no F.normalize of the position).  Parameters on the
-    device are read there at every launch; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
-
-    @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs, weights):
-        maps, params, kind = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity), _step_kind("camera_fit", weights)
-        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, gp, loss = _launch_loss_step(kind, _step_plan(maps, kwargs, params), maps, targets, wanted, weights=weights)
-        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, gp), params, weights)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        return _fit_step_backward(ctx, grad_loss)
-
-
-class _ViewStackStepFn(torch.autograd.Function):
-    """_CameraStackStepFn with one camera position per shot (`view_dir` [L,3]): ONE kernel, pbr_cook_torrance_view_mse_stack_step, gives the
-    loss over the L images and the map gradients summed over the shots.  The positions, lights and intensities are inputs here (not
-    differentiated: that is _ViewStackFitFn) because the positions travel beside the plan."""
-
-    @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs, weights):
-        maps, params, kind = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity), _step_kind("view_stack", weights)
-        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, _, loss = _plan_and_launch(kind, maps, kwargs, params, targets, wanted, weights)
-        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, None), params, weights)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        grads, _ = _kept_step(ctx)
-        _scale_step_gradients(grads, grad_loss)
-        return (*grads, None, None, None, None, None, None)
+_MseStackStepFn = _stack_step_class("_MseStackStepFn", "stack", False, False, """The orthographic stack step (pbr_cook_torrance_mse_stack_step): the
+    gradients of the maps, summed over the lights, in 64 + 12 L bytes per pixel instead of L loss steps and autograd's accumulation.""")
+_MseStackFitFn = _stack_step_class("_MseStackFitFn", "fit", True, True, """_MseStackStepFn with view_dir / light / light_intensity as differentiable
+    inputs (pbr_cook_torrance_mse_stack_fit_step): the loss, the map gradients and the (3 + 6 L) gradients of view, lights and intensities -- a
+    capture whose light positions, per-shot intensities or camera axis are fitted, with or without the maps.  Parameters that live on the device
+    are read there (device_params): no read-back, so a whole step captures into a graph; a parameter held on the CPU receives a CPU gradient
+    (one copy of the small block).""")
+_CameraStackStepFn = _stack_step_class("_CameraStackStepFn", "camera_stack", False, False, """_MseStackStepFn under the perspective camera
+    (view_type="point" in `kwargs`: `view_dir` is the camera's position): pbr_cook_torrance_camera_mse_stack_step.""")
+_CameraStackFitFn = _stack_step_class("_CameraStackFitFn", "camera_fit", True, True, """_MseStackFitFn under the perspective camera
+    (pbr_cook_torrance_camera_mse_stack_fit_step): the (3 + 6 L) gradients are the camera position's, the lights' and the intensities'.  The
+    position's gradient is handed back as the kernel summed it (the per-pixel normalisation is differentiated in the kernel; there is no
+    F.normalize of the position).""")
+_ViewStackStepFn = _stack_step_class("_ViewStackStepFn", "view_stack", True, False, """_CameraStackStepFn with one camera position per shot
+    (`view_dir` [L,3]): pbr_cook_torrance_view_mse_stack_step.  The positions, lights and intensities are inputs here (not differentiated:
+    that is _ViewStackFitFn) because the positions travel beside the plan.""")
+_ViewStackFitFn = _stack_step_class("_ViewStackFitFn", "view_fit", True, True, """_CameraStackFitFn with one camera position per shot
+    (pbr_cook_torrance_view_mse_stack_fit_step): the 9 L gradients of the L positions, the lights and the intensities.  Positions on the device
+    are read there at every launch; host positions are re-read at every call.""")
+# (view type, one view per shot) -> (the step class, the fit class)
+_STACK_CLASSES = {("directional", False): (_MseStackStepFn, _MseStackFitFn), ("point", False): (_CameraStackStepFn, _CameraStackFitFn),
+                  ("point", True): (_ViewStackStepFn, _ViewStackFitFn)}
 
 
-class _ViewStackFitFn(torch.autograd.Function):
-    """_CameraStackFitFn with one camera position per shot: ONE kernel (pbr_cook_torrance_view_mse_stack_fit_step) gives the loss, the map
-    gradients and the 9 L gradients of the L positions, the lights and the intensities.  Positions on the device are read there at every
-    launch; host positions are re-read at every call; a parameter held on the CPU receives a CPU gradient (one copy of the small block)."""
-
-    @staticmethod
-    def forward(ctx, albedo, normal, roughness, metallic, specular, view_dir, light, light_intensity, targets, kwargs, weights):
-        maps, params, kind = (albedo, normal, roughness, metallic, specular), (view_dir, light, light_intensity), _step_kind("view_fit", weights)
-        wanted = [bool(ctx.needs_input_grad[i] and maps[i] is not None) for i in range(5)]
-        bufs, gp, loss = _plan_and_launch(kind, maps, kwargs, params, targets, wanted, weights)
-        _keep_step(ctx, kind, maps, targets, kwargs, wanted, (bufs, gp), params, weights)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        return _fit_step_backward(ctx, grad_loss)
-
-
-def _stack_route(maps, params, targets, kwargs, on_device=None, weights=None):
-    """Which one-pass form serves a rendering_loss_mse_stack call: "fit" (_MseStackFitFn: view, a light or an intensity requires grad, with or
-    without the maps), "step" (_MseStackStepFn: only maps do) or None (the composition).  Both need plain arguments, untiled maps, every map with
-    its own planes, targets that need no grad and maps on a ROCm device (`on_device`: None = ask the albedo).  No rule by L: the fit step was
-    ahead of the composition at every L measured (profiles/light_stack_fit_step.json).  `weights` (rendering_loss_mse_stack(weights=)) do
-    not change the answer -- "fit" and "step" are then the weighted siblings, _step_kind; no rule by L either: ahead of the composition at every
-    L measured in all three families (profiles/weighted_stack_probe.json) -- unless they require grad: the composition."""
-    albedo = maps[0]
-    B = albedo.shape[0] if albedo.dim() == 4 else 1
-    shared = B > 1 and any(_shared_by_batch(t, B) for t in maps)
-    if on_device is None:
-        on_device = albedo.is_cuda
-    if not on_device or shared or not _stack_plain(kwargs) or _needs_grad(targets, weights) or _view_type(kwargs) == "point":
-        return None
-    if _needs_grad(*params):
-        return "fit"
-    return "step" if _needs_grad(*maps) else None
-
-
-def _camera_stack_route(maps, params, targets, kwargs, on_device=None, weights=None):
-    """_stack_route for view_type="point" (`view_dir` is the camera's position): "fit" (_CameraStackFitFn: the position, a light or an
-    intensity requires grad, with or without the maps), "step" (_CameraStackStepFn: only maps do) or None (the composition: the stack of
-    camera renders and torch's MSE).  The same conditions -- plain arguments, untiled maps, every map with its own planes, targets that need
-    no grad, maps on a ROCm device (`on_device`: None = ask the albedo) -- and the view type itself.  No rule by L: both steps were ahead of the
-    composition at every L measured, the single photograph included (profiles/camera_stack_probe.json).  `weights`: as for _stack_route."""
-    if _view_type(kwargs) != "point":
+def _route(view_type, maps, params, targets, kwargs, on_device=None, weights=None):
+    """Which one-pass form of the family `view_type` serves a stack-loss call: "fit" (the family's fit class: view, a light or an intensity
+    requires grad, with or without the maps), "step" (its step class: only maps do) or None (the composition).  Both need the call's own view
+    type to be the family's, plain arguments, untiled maps, every map with its own planes, targets that need no grad and maps on a ROCm device
+    (`on_device`: None = ask the albedo).  No rule by L: both steps were ahead of the composition at every L measured, the single photograph
+    included (profiles/light_stack_fit_step.json, camera_stack_probe.json).  `weights` do not change the answer -- "fit" and "step" are then
+    the weighted siblings, _step_kind; ahead at every L measured in all three families (profiles/weighted_stack_probe.json) -- unless they
+    require grad: the composition."""
+    if view_type is not None and _view_type(kwargs) != view_type:      # None: the caller took the family from the call's own view type
         return None
     albedo = maps[0]
     B = albedo.shape[0] if albedo.dim() == 4 else 1
@@ -1414,33 +1336,42 @@ def _camera_stack_route(maps, params, targets, kwargs, on_device=None, weights=N
     return "step" if _needs_grad(*maps) else None
 
 
-def _view_stack_route(maps, params, targets, kwargs, on_device=None, weights=None):
-    """_camera_stack_route for `view_dir` [L,3], one camera position per shot: "fit" (_ViewStackFitFn: the positions, a light or an intensity
-    requires grad, with or without the maps), "step" (_ViewStackStepFn: only maps do) or None (the composition: L camera renders and torch's
-    MSE).  The camera stack's conditions: view_type="point", plain arguments, untiled maps, every map with its own planes, targets that need
-    no grad, maps on a ROCm device (`on_device`: None = ask the albedo).  `weights`: as for _stack_route."""
-    return _camera_stack_route(maps, params, targets, kwargs, on_device, weights)
+def _stack_route(maps, params, targets, kwargs, on_device=None, weights=None):
+    """_route for the orthographic view: _MseStackFitFn, _MseStackStepFn or None."""
+    return _route("directional", maps, params, targets, kwargs, on_device, weights)
 
 
-def _view_loss_step(route, maps, params, targets, kwargs, weights=None):
-    """The fused per-shot-camera step `_view_stack_route` chose, or None when the library does not serve the descriptor as one pass."""
-    kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED + _PARAM_KEYS}
+def _camera_stack_route(maps, params, targets, kwargs, on_device=None, weights=None):
+    """_route for view_type="point" (`view_dir` is the camera's position): _CameraStackFitFn, _CameraStackStepFn or None."""
+    return _route("point", maps, params, targets, kwargs, on_device, weights)
+
+
+_view_stack_route = _camera_stack_route      # `view_dir` [L,3], one position per shot (_ViewStackFitFn, _ViewStackStepFn): the camera stack's conditions
+
+
+def _one_pass_loss(maps, params, targets, kwargs, per_shot=False, weights=None):
+    """The loss from the one-pass class that serves the call -- the family by the call's view type and `per_shot`, "fit" or "step" by _route --
+    or None: no route (one orthographic direction per shot has no kernel at all), or the library does not serve the descriptor as one pass.
+    A class that takes the parameters as inputs gets them out of `kwargs`."""
+    view_type = _view_type(kwargs)
+    route = None if per_shot and view_type != "point" else _route(None, maps, params, targets, kwargs, None, weights)
+    if route is None:
+        return None
+    cls = _STACK_CLASSES[view_type, per_shot][route == "fit"]
+    dropped = _STACK_EXCLUDED + _PARAM_KEYS if cls.takes_params else _STACK_EXCLUDED
+    kw = {k: v for k, v in kwargs.items() if k not in dropped}
     try:
-        return (_ViewStackFitFn if route == "fit" else _ViewStackStepFn).apply(*maps, *params, targets, kw, weights)
+        return cls.apply(*maps, *(params if cls.takes_params else ()), targets, kw, weights)
     except _StepNotServed:
         return None
 
 
-def _camera_loss_step(route, maps, params, targets, kwargs, weights=None):
-    """The fused camera step `_camera_stack_route` chose, or None when the library does not serve the descriptor as one pass."""
-    kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED}
+def _one_light(params) -> bool:
+    """The call's lights are ONE light with one intensity; whatever is wrong with them is the evaluation's to say."""
     try:
-        if route == "fit":
-            kw = {k: v for k, v in kw.items() if k not in _PARAM_KEYS}
-            return _CameraStackFitFn.apply(*maps, *params, targets, kw, weights)
-        return _CameraStackStepFn.apply(*maps, targets, kw, weights)
-    except _StepNotServed:
-        return None
+        return _stack_lights(params[1], params[2]) == (1, 1)
+    except (ValueError, TypeError, AttributeError, RuntimeError):
+        return False
 
 
 def _stack_weights(weights, want) -> None:
@@ -1499,21 +1430,9 @@ def rendering_loss_mse_stack(albedo: torch.Tensor, normal: Optional[torch.Tensor
         _stack_weights(weights, want)
     maps = (albedo, normal, roughness, metallic, specular)
     params = tuple(kwargs.get(k) for k in _PARAM_KEYS)
-    if _view_type(kwargs) == "point":
-        route = (_view_stack_route if per_shot else _camera_stack_route)(maps, params, targets, kwargs, None, weights)
-        loss = (_view_loss_step if per_shot else _camera_loss_step)(route, maps, params, targets, kwargs, weights) if route is not None else None
-        if loss is not None:
-            return loss
-    route = None if per_shot else _stack_route(maps, params, targets, kwargs, None, weights)      # one orthographic direction per shot: the composition
-    if route is not None:
-        kw = {k: v for k, v in kwargs.items() if k not in _STACK_EXCLUDED}
-        try:
-            if route == "fit":
-                kw = {k: v for k, v in kw.items() if k not in _PARAM_KEYS}
-                return _MseStackFitFn.apply(albedo, normal, roughness, metallic, specular, *params, targets, kw, weights)
-            return _MseStackStepFn.apply(albedo, normal, roughness, metallic, specular, targets, kw, weights)
-        except _StepNotServed:
-            pass
+    loss = _one_pass_loss(maps, params, targets, kwargs, per_shot, weights)
+    if loss is not None:
+        return loss
     out = cook_torrance_stack(albedo, normal, roughness, metallic, specular, **kwargs)
     if weights is not None:
         return _weighted_mse(out, targets, weights)
