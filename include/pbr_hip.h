@@ -949,6 +949,66 @@ typedef struct pbr_adam_group {
 } pbr_adam_group;
 int pbr_adam_advance(const pbr_adam_group *groups, int32_t n_groups, void *coeffs_device, void *stream);
 
+/* ---- the smoothness prior of a fit (csrc/smoothness.hip; pypbr_amd.priors) ---------- */
+
+/*
+ * Vectorial total variation / Tikhonov over a table of at most PBR_MAX_SMOOTH_TENSORS maps: value and gradients of all of them in ONE
+ * launch (and one small finish launch).  No upstream counterpart; tools/smoothness_oracle.py is the definition in float64 numpy.
+ * For one entry, planes p[b][c][y][x], B x C x H x W, 1 <= C <= 4:
+ *   forward differences   dx_c(y,x) = p_c(y,x+1) - p_c(y,x),  dy_c(y,x) = p_c(y+1,x) - p_c(y,x).  wrap = 0: a difference that would reach
+ *                         outside the map is exactly 0; wrap = 1: indices modulo W and H (tileable textures; consistent with roll / tile)
+ *   channel coupling      s(y,x) = sum_c (dx_c^2 + dy_c^2)
+ *   penalty               PBR_SMOOTH_L2: phi = s.  PBR_SMOOTH_CHARBONNIER: phi = sqrt(s + eps^2) - eps, eps > 0, evaluated as
+ *                         s / (sqrt(s + eps^2) + eps) (the difference cancels in float32)
+ *   value                 R = k sum_{b,y,x} w(b,y,x) phi(s(b,y,x)); k is the caller's (lambda / (B H W) for a mean, lambda for a sum),
+ *                         w an optional float32 plane per image (weights_batch_stride 0: one shared by the batch), 1 where absent.  A
+ *                         weight multiplies, it does not skip: a NaN parameter under a weight of 0 still reaches its neighbours.
+ *   gradient              q = k w 2 phi'(s)  (2 for L2, 1 / sqrt(s + eps^2) for Charbonnier),
+ *                         g_c(y,x) = -q(y,x) (dx_c(y,x) + dy_c(y,x)) + q(y,x-1) dx_c(y,x-1) + q(y-1,x) dy_c(y-1,x), terms outside the
+ *                         map 0, or wrapped
+ * *loss receives the sum of the entries' R, terms[i] (NULL: not wanted) entry i's R.  `grad` (NULL: value only) is WRITTEN, not
+ * accumulated into, in the map's dtype (PBR_F32 | PBR_F16; arithmetic in fp32).  Rows are dense; batch and plane strides in elements.
+ * One pass: a wave walks down a strip of 63 units of a band of at most PBR_SMOOTH_BAND_ROWS rows (halved, down to
+ * PBR_SMOOTH_MIN_BAND_ROWS, while the launch has fewer than PBR_SMOOTH_MIN_BLOCKS workgroups) -- a unit is four pixels when the width,
+ * the strides and the pointers of the entry are whole quads, else one pixel -- with one halo unit on its left and one halo row above,
+ * so every (q dx_c, q dy_c) is formed once per strip and every gradient value is written once.  The value is reduced without atomics:
+ * one fp32 partial per workgroup in `workspace`, summed in fp64 in a fixed order by the finish launch: two runs give the same bits.
+ * Caller errors, before anything is launched: a NULL table, param, loss or workspace PBR_ERR_NULL_MAP; n outside
+ * [1, PBR_MAX_SMOOTH_TENSORS], batch / height / width < 1, height or width > 2^30, height * width > 2^40, more than 2^31 - 1 workgroups,
+ * a negative stride, eps <= 0 (or not finite) with Charbonnier, a k that is not finite, a pointer off its element's alignment, a
+ * workspace smaller than pbr_smoothness_workspace_bytes, a `grad` that overlaps any param, weights or other grad of the launch (tested
+ * plane by plane, as pbr_adam_check does) PBR_ERR_SHAPE; channels outside 1..4 PBR_ERR_CHANNELS; an unknown kind PBR_ERR_UNSUPPORTED; a
+ * dtype PBR_ERR_DTYPE.  (ABI 9: entry points added, nothing changed.)
+ */
+enum { PBR_SMOOTH_L2 = 0, PBR_SMOOTH_CHARBONNIER = 1 };
+#define PBR_MAX_SMOOTH_TENSORS 8
+#define PBR_SMOOTH_BLOCK 256          /* lanes of a workgroup: 4 waves, 4 adjacent strips of 63 units (+ 1 halo unit) each */
+#define PBR_SMOOTH_BAND_ROWS 32       /* rows of a band at the most (+ 1 halo row above, 1 row read below) */
+#define PBR_SMOOTH_MIN_BAND_ROWS 4    /* ... and at the least: the bands of a launch are halved while it has fewer than */
+#define PBR_SMOOTH_MIN_BLOCKS 512     /* ... this many workgroups */
+typedef struct pbr_smooth_tensor {
+    const void *param;
+    void *grad;                   /* NULL: value only */
+    const float *weights;         /* NULL: 1 everywhere */
+    int64_t param_batch_stride, param_plane_stride;
+    int64_t grad_batch_stride, grad_plane_stride;
+    int64_t weights_batch_stride; /* 0: one plane shared by the batch */
+    double k;                     /* formed in float64 by the caller; the gradient uses it rounded to fp32 */
+    float eps;                    /* CHARBONNIER */
+    int32_t dtype;                /* PBR_F32 | PBR_F16: param and grad */
+    int32_t batch, channels, height, width;
+    int32_t kind;                 /* PBR_SMOOTH_* */
+    int32_t wrap;
+} pbr_smooth_tensor;
+int pbr_smoothness_step(const pbr_smooth_tensor *tensors, int32_t n_tensors, void *loss, void *terms, void *workspace, size_t workspace_bytes,
+                        void *stream);
+/* Bytes of workspace pbr_smoothness_step needs for this table (one fp32 per workgroup); 0 for a table pbr_smoothness_check refuses. */
+size_t pbr_smoothness_workspace_bytes(const pbr_smooth_tensor *tensors, int32_t n_tensors);
+/* What pbr_smoothness_step checks about its table before it launches, alone: PBR_OK, or the caller error.  Launches nothing. */
+int pbr_smoothness_check(const pbr_smooth_tensor *tensors, int32_t n_tensors);
+/* sizeof(pbr_smooth_tensor) as compiled: bindings check their struct layout against it. */
+size_t pbr_smooth_tensor_size(void);
+
 /* ---- introspection; the process-global tuning hook (tests, benches, profiling) ------ */
 int pbr_abi_version(void);
 /* First 16 hex digits of the SHA-256 over the sources this library was built from (every .hip and .hpp file of csrc, this header, the Makefile,

@@ -60,6 +60,7 @@ EXPORTS = (
     "pbr_cook_torrance_camera_weighted_mse_stack_step", "pbr_cook_torrance_camera_weighted_mse_stack_fit_step",
     "pbr_cook_torrance_view_weighted_mse_stack_step", "pbr_cook_torrance_view_weighted_mse_stack_fit_step",
     "pbr_adam_step", "pbr_adam_check", "pbr_adam_tensor_size", "pbr_adam_advance",
+    "pbr_smoothness_step", "pbr_smoothness_workspace_bytes", "pbr_smoothness_check", "pbr_smooth_tensor_size",
 )
 
 
@@ -164,6 +165,22 @@ class AdamGroup(ctypes.Structure):
     """pbr_adam_group: one row of pbr_adam_advance (a DEVICE float counter; lr from the host value or a DEVICE float)."""
     _fields_ = [("step", ctypes.c_void_p), ("lr_device", ctypes.c_void_p), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),
                 ("beta2", ctypes.c_double), ("eps", ctypes.c_double)]
+
+
+SMOOTH_L2, SMOOTH_CHARBONNIER = 0, 1
+MAX_SMOOTH_TENSORS = 8
+SMOOTH_BLOCK, SMOOTH_BAND_ROWS = 256, 32     # PBR_SMOOTH_BLOCK, PBR_SMOOTH_BAND_ROWS: 4 waves of 63 units + 1 halo unit; rows of a band at the most
+SMOOTH_MIN_BAND_ROWS, SMOOTH_MIN_BLOCKS = 4, 512      # ... halved down to 4 while a launch has fewer than 512 workgroups
+
+
+class SmoothTensor(ctypes.Structure):
+    """pbr_smooth_tensor: one map of a pbr_smoothness_step table (strides in elements; grad NULL: value only; weights NULL: 1)."""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("weights", ctypes.c_void_p),
+                ("param_batch_stride", ctypes.c_int64), ("param_plane_stride", ctypes.c_int64),
+                ("grad_batch_stride", ctypes.c_int64), ("grad_plane_stride", ctypes.c_int64), ("weights_batch_stride", ctypes.c_int64),
+                ("k", ctypes.c_double), ("eps", ctypes.c_float), ("dtype", ctypes.c_int32),
+                ("batch", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("kind", ctypes.c_int32), ("wrap", ctypes.c_int32)]
 
 
 class RotateGeom(ctypes.Structure):
@@ -358,6 +375,14 @@ def lib():
     L.pbr_adam_tensor_size.restype = ctypes.c_size_t
     L.pbr_adam_advance.argtypes = [ctypes.POINTER(AdamGroup), i32, vp, vp]
     L.pbr_adam_advance.restype = ctypes.c_int
+    L.pbr_smoothness_step.argtypes = [ctypes.POINTER(SmoothTensor), i32, vp, vp, vp, sz, vp]
+    L.pbr_smoothness_step.restype = ctypes.c_int
+    L.pbr_smoothness_workspace_bytes.argtypes = [ctypes.POINTER(SmoothTensor), i32]
+    L.pbr_smoothness_workspace_bytes.restype = ctypes.c_size_t
+    L.pbr_smoothness_check.argtypes = [ctypes.POINTER(SmoothTensor), i32]
+    L.pbr_smoothness_check.restype = ctypes.c_int
+    L.pbr_smooth_tensor_size.argtypes = []
+    L.pbr_smooth_tensor_size.restype = ctypes.c_size_t
     L.pbr_render_desc_size.restype = ctypes.c_size_t
     L.pbr_build_id.argtypes = []
     L.pbr_build_id.restype = ctypes.c_char_p
@@ -368,6 +393,8 @@ def lib():
                                  % (L.pbr_render_desc_size(), ctypes.sizeof(RenderDesc)))
     if L.pbr_adam_tensor_size() != ctypes.sizeof(AdamTensor):
         raise NativeLibraryError("pbr_adam_tensor layout mismatch: library %d bytes, binding %d" % (L.pbr_adam_tensor_size(), ctypes.sizeof(AdamTensor)))
+    if L.pbr_smooth_tensor_size() != ctypes.sizeof(SmoothTensor):
+        raise NativeLibraryError("pbr_smooth_tensor layout mismatch: library %d bytes, binding %d" % (L.pbr_smooth_tensor_size(), ctypes.sizeof(SmoothTensor)))
     if L.pbr_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libpbr_hip.so ABI %d, binding expects %d" % (L.pbr_abi_version(), ABI_VERSION))
     for env, knob in tuple(("PBR_TUNE_" + name.upper(), index) for name, index in TUNE_NAMES.items()):      # profiling runs: knobs from the environment
