@@ -1,7 +1,7 @@
 """The populations the photometric-stereo tests run on (tests/test_photometric_host.py pins their make-up with the oracle alone,
 tests/test_gpu_photometric.py runs the kernel on them): a 24 x 36 grid -- ragged against the kernel's 16 x 16-lane tile on both axes, in
 the quad form and in the pixel form -- and its 24 x 35 sibling (the pixel form only), light_size 1, L = 8 point lights on a circle of
-radius 0.7.
+radius 0.7 (`n_lights`: the same sets under 3, 4 or 16 lights on that circle).
 
   gentle     normals of the height field with slopes hx = 0.6 sin(7x + 1) cos(5y), hy = 0.6 cos(6y) sin(4x + 2), n = normalize(-hx, -hy, 1);
              lights at heights 0.6 / 0.8 alternating; albedo uniform in [0.15, 0.9]; exactly Lambertian targets, sRGB-encoded
@@ -33,9 +33,10 @@ WELL_CONDITIONED = 0.05                 # the banded comparison is made where th
 Case = collections.namedtuple("Case", "targets weights light intensity normal albedo shadowed")
 
 
-def lights(heights) -> np.ndarray:
-    ang = 2.0 * np.pi * ((3 * np.arange(N_LIGHTS)) % N_LIGHTS + 0.25) / N_LIGHTS      # shot l hops three places on: any three consecutive shots span the circle
-    z = np.where(np.arange(N_LIGHTS) % 2 == 0, heights[0], heights[1])
+def lights(heights, n_lights=N_LIGHTS) -> np.ndarray:
+    hop = 3 if n_lights % 3 else 1                                                     # (a count 3 divides: three places on would come back to the start)
+    ang = 2.0 * np.pi * ((hop * np.arange(n_lights)) % n_lights + 0.25) / n_lights    # shot l hops three places on: any three consecutive shots span the circle
+    z = np.where(np.arange(n_lights) % 2 == 0, heights[0], heights[1])
     return np.stack([RADIUS * np.cos(ang), RADIUS * np.sin(ang), z], axis=1).astype(np.float32).astype(np.float64)
 
 
@@ -54,25 +55,25 @@ def albedo(size=SIZE, seed=31) -> np.ndarray:
     return np.random.default_rng(seed).uniform(0.15, 0.9, (3,) + tuple(size))
 
 
-def partial_weights(size=SIZE) -> np.ndarray:
+def partial_weights(size=SIZE, n_lights=N_LIGHTS) -> np.ndarray:
     H, W = size
     cols = np.arange(W)[None, None, :]
-    first = (W * (np.arange(N_LIGHTS) + 1.0) / (N_LIGHTS + 2))[:, None, None]
-    return np.broadcast_to((cols >= first).astype(np.float32), (N_LIGHTS, H, W)).copy()
+    first = (W * (np.arange(n_lights) + 1.0) / (n_lights + 2))[:, None, None]
+    return np.broadcast_to((cols >= first).astype(np.float32), (n_lights, H, W)).copy()
 
 
-def lambertian(name, size=SIZE, encode=True) -> Case:
+def lambertian(name, size=SIZE, encode=True, n_lights=N_LIGHTS) -> Case:
     """`gentle`, `shadowed` or `partial`.  targets: float32 sRGB-encoded (encode) or float64 linear; `shadowed` [L,H,W] marks the
-    observations in attached shadow (n . w_l <= 0)."""
+    observations in attached shadow (n . w_l <= 0).  `n_lights`: another count of lights on the same circle (1 ... 16)."""
     amplitude, heights, inten = SETS["gentle" if name == "partial" else name]
     inten = float(np.float32(inten))                                                # (lights and intensities travel as float32)
-    n, rho, pos = normals(amplitude, size), albedo(size), lights(heights)
+    n, rho, pos = normals(amplitude, size), albedo(size), lights(heights, n_lights)
     w, att = O.geometry(pos, size, "point", LIGHT_SIZE)
     cos = (w * n[None]).sum(axis=1)                                                  # [L,H,W]
     lin = rho[None] / np.pi * inten * (np.maximum(cos, 0.0) * att)[:, None]         # [L,3,H,W]
     assert lin.max() < 1.0, lin.max()                                                # nothing clipped: the data stay exactly Lambertian
     targets = O.linear_to_srgb(lin).astype(np.float32) if encode else lin
-    weights = partial_weights(size) if name == "partial" else None
+    weights = partial_weights(size, n_lights) if name == "partial" else None
     return Case(targets, weights, pos, np.full(3, inten), n, rho, cos <= 0)
 
 

@@ -47,10 +47,13 @@ def linspace32(size, n):
     return v.astype(np.float32)
 
 
-def geometry(light, size, light_type="point", light_size=None, dtype=np.float64):
-    """-> (w [L,3,H,W], a [L,H,W]) in `dtype`: the unit vectors towards the lights and the attenuations of step 1."""
+def geometry(light, size, light_type="point", light_size=None, dtype=np.float64, window=None):
+    """-> (w [L,3,H,W], a [L,H,W]) in `dtype`: the unit vectors towards the lights and the attenuations of step 1.  `window`
+    (y0, x0, H_total, W_total): `size` is the window [y0, y0 + H) x [x0, x0 + W) of a grid of H_total x W_total pixels (the y_offset /
+    H_total of torch_oracle.cook_torrance, on both axes)."""
     f = dtype
     H, W = size
+    y0, x0, H_total, W_total = (0, 0, H, W) if window is None else window
     light = np.asarray(light, dtype=np.float64).reshape(-1, 3)
     L = light.shape[0]
     if light_type == "directional":
@@ -60,7 +63,7 @@ def geometry(light, size, light_type="point", light_size=None, dtype=np.float64)
     if light_type != "point":
         raise ValueError("light_type")
     s = light_size or 1.0
-    xs, ys = linspace32(s, W).astype(f), linspace32(s, H).astype(f)
+    xs, ys = linspace32(s, W_total).astype(f)[x0:x0 + W], linspace32(s, H_total).astype(f)[y0:y0 + H]
     P = np.stack([np.broadcast_to(xs[None, :], (H, W)), np.broadcast_to(-ys[:, None], (H, W)), np.zeros((H, W), dtype=f)])
     d = light.astype(np.float32).astype(f)[:, :, None, None] - P[None]
     dd = (d * d).sum(axis=1)
@@ -69,8 +72,8 @@ def geometry(light, size, light_type="point", light_size=None, dtype=np.float64)
 
 
 def photometric_stereo(targets, weights, light, light_intensity, light_type="point", light_size=None, targets_srgb=True, iterations=3,
-                       shadow_cos=0.1, min_condition=1e-4, albedo_srgb=False, dtype=np.float64) -> Stereo:
-    """targets [L,3,H,W]; weights [L,H,W], [H,W] or None; light [L,3]; light_intensity [3] or [L,3].  Returns arrays of `dtype`:
+                       shadow_cos=0.1, min_condition=1e-4, albedo_srgb=False, dtype=np.float64, window=None) -> Stereo:
+    """targets [L,3,H,W]; weights [L,H,W], [H,W] or None; light [L,3]; light_intensity [3] or [L,3]; `window`: geometry()'s.  Returns arrays of `dtype`:
       normal (3,H,W), albedo (3,H,W), confidence (H,W)     steps 4 - 6
       valid (H,W) bool
       margin (H,W) float64   the smallest distance of any decision the pixel went through to its threshold: |w_l . g / |g| - tau| over the
@@ -89,7 +92,7 @@ def photometric_stereo(targets, weights, light, light_intensity, light_type="poi
         wt = np.asarray(weights)
         wt = np.broadcast_to(wt.reshape((-1, H, W)), (L, H, W)).astype(f)
     inten = np.broadcast_to(np.asarray(light_intensity, dtype=np.float64).reshape(-1, 3), (L, 3)).astype(np.float32).astype(f)
-    w, att = geometry(light, (H, W), light_type, light_size, dtype=f)
+    w, att = geometry(light, (H, W), light_type, light_size, dtype=f, window=window)
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         lin = srgb_to_linear(T, f) if targets_srgb else T.astype(f)
         r = (lin / (inten[:, :, None, None] * att[:, None])).astype(f)                              # [L,3,H,W]
