@@ -47,8 +47,18 @@ def _grad_like(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
     return g.to(like.dtype).contiguous()
 
 
+def rows_are_dense(t: torch.Tensor) -> bool:
+    """The kernels take any batch / plane strides but dense rows of non-negative strides: this is that rule, for every caller."""
+    return t.stride(-1) == 1 and (t.shape[-2] == 1 or t.stride(-2) == t.shape[-1]) and all(s >= 0 for s in t.stride())
+
+
 def _rows_dense(t: torch.Tensor) -> torch.Tensor:
-    """The kernels take any batch / plane strides but dense rows of non-negative strides."""
-    if t.stride(-1) == 1 and (t.shape[-2] == 1 or t.stride(-2) == t.shape[-1]) and all(s >= 0 for s in t.stride()):
-        return t
-    return t.contiguous()
+    """`t` as the kernels take it: itself when its rows are dense, else a contiguous copy."""
+    return t if rows_are_dense(t) else t.contiguous()
+
+
+def plane_geometry(t: torch.Tensor):
+    """(batch, channels, height, width, batch stride, plane stride) of a [C,H,W] / [B,C,H,W] view with dense rows, strides in elements as
+    they are (0 for the batch stride of a [C,H,W] view): what the entries of a launch table carry."""
+    four = t.dim() == 4
+    return (t.shape[0] if four else 1), t.shape[-3], t.shape[-2], t.shape[-1], (t.stride(0) if four else 0), t.stride(-3)

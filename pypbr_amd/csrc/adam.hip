@@ -24,13 +24,12 @@
 // the next loss step; m, v and master only by the next update.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
 #include "../../include/pbr_hip.h"
-#include "launch_util.hpp"
+#include "table_launch.hpp"
 
 #ifndef PBR_ADAM_POLICY
 #define PBR_ADAM_POLICY 14
@@ -188,56 +187,20 @@ __global__ void adam_advance_kernel(GroupTable tab, int32_t n, pbr_adam_coeffs *
     }
 }
 
-// [lo, hi): bytes a launch touches without a gap, and whether it writes them.
-struct Interval { uintptr_t lo, hi; bool written; };
-
-// The intervals of [batch] x [channels] dense planes of `pixels` elements at the given strides: one per plane, per image where an image's
-// planes are back to back, one in all where the images are too.  The views of a material-major packing interleave the maps of a batch --
-// material 0's normal lies between material 0's and material 1's albedo -- so a pointer's first-to-last span says nothing there.
-inline void add_intervals(std::vector<Interval> &out, const void *p, const pbr_adam_tensor &e, int64_t bs, int64_t ps, size_t esz, bool written) {
-    const uintptr_t base = reinterpret_cast<uintptr_t>(p);
-    const bool image_dense = e.channels == 1 || ps == e.pixels;
-    const bool all_dense = image_dense && (e.batch == 1 || bs == (int64_t)e.channels * e.pixels);
-    if (all_dense) {
-        out.push_back({base, base + (uintptr_t)((int64_t)e.batch * e.channels * e.pixels) * esz, written});
-        return;
-    }
-    for (int32_t b = 0; b < e.batch; ++b) {
-        if (image_dense) {
-            const uintptr_t lo = base + (uintptr_t)((int64_t)b * bs) * esz;
-            out.push_back({lo, lo + (uintptr_t)((int64_t)e.channels * e.pixels) * esz, written});
-            continue;
-        }
-        for (int32_t c = 0; c < e.channels; ++c) {
-            const uintptr_t lo = base + (uintptr_t)((int64_t)b * bs + (int64_t)c * ps) * esz;
-            out.push_back({lo, lo + (uintptr_t)e.pixels * esz, written});
-        }
-    }
-}
-
-// Nothing that is written may overlap anything else the launch touches (p and g of one entry included); what is only read -- gradients,
-// an expanded one's repeated planes -- may overlap itself.  Exact for strided entries: every interval is a run the kernel really touches.
+// Nothing that is written -- the parameter, m, v, the master -- may overlap anything else the launch touches (p and g of one entry
+// included); the gradients, only read, may overlap themselves (table_launch.hpp: written_overlaps).
 bool launch_overlaps(const pbr_adam_tensor *t, int32_t n) {
     std::vector<Interval> iv;
     for (int32_t i = 0; i < n; ++i) {
         const pbr_adam_tensor &e = t[i];
-        const size_t esz = e.dtype == PBR_F32 ? 4 : 2;
-        pbr_adam_tensor dense = e;                                      // state: [batch][channels][pixels], back to back
-        dense.batch = 1; dense.channels = 1; dense.pixels = (int64_t)e.batch * e.channels * e.pixels;
-        add_intervals(iv, e.param, e, e.param_batch_stride, e.param_plane_stride, esz, true);
-        add_intervals(iv, e.grad, e, e.grad_batch_stride, e.grad_plane_stride, esz, false);
-        add_intervals(iv, e.exp_avg, dense, 0, 0, sizeof(float), true);
-        add_intervals(iv, e.exp_avg_sq, dense, 0, 0, sizeof(float), true);
-        if (e.master) add_intervals(iv, e.master, dense, 0, 0, sizeof(float), true);
+        const size_t esz = elem_bytes(e.dtype);
+        const int64_t dense = (int64_t)e.batch * e.channels * e.pixels;   // state: [batch][channels][pixels], back to back
+        add_planes(iv, e.param, e.batch, e.channels, e.pixels, e.param_batch_stride, e.param_plane_stride, esz, true);
+        add_planes(iv, e.grad, e.batch, e.channels, e.pixels, e.grad_batch_stride, e.grad_plane_stride, esz, false);
+        for (const void *state : {e.exp_avg, e.exp_avg_sq, e.master})
+            if (state) add_planes(iv, state, 1, 1, dense, 0, 0, sizeof(float), true);
     }
-    std::sort(iv.begin(), iv.end(), [](const Interval &a, const Interval &b) { return a.lo < b.lo; });
-    uintptr_t end_written = 0, end_any = 0;                             // the furthest end among the intervals in front
-    for (const Interval &x : iv) {
-        if (x.lo < end_written || (x.written && x.lo < end_any)) return true;
-        if (x.written && x.hi > end_written) end_written = x.hi;
-        if (x.hi > end_any) end_any = x.hi;
-    }
-    return false;
+    return written_overlaps(iv);
 }
 
 int check_entry(const pbr_adam_tensor &e, int32_t n_groups) {
@@ -254,17 +217,14 @@ int check_entry(const pbr_adam_tensor &e, int32_t n_groups) {
     if (e.batch > 1 && e.param_batch_stride < (int64_t)(e.channels - 1) * e.param_plane_stride + e.pixels) return PBR_ERR_SHAPE;
     if (e.project == PBR_ADAM_BOX && e.lo > e.hi) return PBR_ERR_SHAPE;
     if (e.group < 0 || e.group >= n_groups) return PBR_ERR_SHAPE;
-    const size_t esz = e.dtype == PBR_F32 ? 4 : 2;
-    if (!all_aligned(esz, {e.param, e.grad}) || !all_aligned(4, {e.exp_avg, e.exp_avg_sq, e.master})) return PBR_ERR_SHAPE;
+    if (!all_aligned(elem_bytes(e.dtype), {e.param, e.grad}) || !all_aligned(4, {e.exp_avg, e.exp_avg_sq, e.master})) return PBR_ERR_SHAPE;
     return PBR_OK;
 }
 
 // Whole quads everywhere: 16-byte accesses of the fp32 planes, 8-byte ones of the fp16 planes.
 inline bool takes_quads(const pbr_adam_tensor &e) {
-    if (e.pixels % 4 != 0) return false;
-    for (int64_t s : {e.param_batch_stride, e.param_plane_stride, e.grad_batch_stride, e.grad_plane_stride})
-        if (s % 4 != 0) return false;
-    return all_aligned(quad_bytes(e.dtype), {e.param, e.grad}) && all_aligned(16, {e.exp_avg, e.exp_avg_sq, e.master});
+    return whole_quads({e.pixels, e.param_batch_stride, e.param_plane_stride, e.grad_batch_stride, e.grad_plane_stride}) &&
+           all_aligned(quad_bytes(e.dtype), {e.param, e.grad}) && all_aligned(16, {e.exp_avg, e.exp_avg_sq, e.master});
 }
 
 }  // namespace
@@ -291,17 +251,17 @@ int pbr_adam_step(const pbr_adam_tensor *tensors, int32_t n_tensors, const pbr_a
     if (!tensors || (coeffs_host == nullptr) == (coeffs_device == nullptr)) return PBR_ERR_NULL_MAP;
     const int rc = pbr_adam_check(tensors, n_tensors, n_groups);
     if (rc != PBR_OK) return rc;
-    AdamTable tab;
+    AdamTable tab{};                                                    // (the rows stay zeros when the kernel reads them from the device)
     int64_t blocks = 1;
+    pad_table(tab.t, tensors, n_tensors);
     for (int32_t i = 0; i < PBR_MAX_ADAM_TENSORS; ++i) {
-        tab.t[i] = tensors[i < n_tensors ? i : 0];
         tab.quads[i] = takes_quads(tab.t[i]) ? 1 : 0;
         const int64_t units = tab.t[i].pixels / (tab.quads[i] ? 4 : 1);
         const int64_t need = (units + PBR_ADAM_BLOCK - 1) / PBR_ADAM_BLOCK;
         if (i < n_tensors && need > blocks) blocks = need;
     }
     if (blocks > PBR_ADAM_MAX_BLOCKS) blocks = PBR_ADAM_MAX_BLOCKS;
-    for (int32_t i = 0; i < PBR_MAX_ADAM_TENSORS; ++i) tab.k[i] = coeffs_host ? coeffs_host[i < n_groups ? i : 0] : pbr_adam_coeffs{};
+    if (coeffs_host) pad_table(tab.k, coeffs_host, n_groups);
     tab.k_device = static_cast<const pbr_adam_coeffs *>(coeffs_device);
     hipLaunchKernelGGL(adam_step_kernel, dim3((uint32_t)blocks, (uint32_t)n_tensors), dim3(PBR_ADAM_BLOCK), 0, static_cast<hipStream_t>(stream), tab);
     return launch_status();
@@ -312,10 +272,9 @@ int pbr_adam_advance(const pbr_adam_group *groups, int32_t n_groups, void *coeff
     if (!groups || !coeffs_device) return PBR_ERR_NULL_MAP;
     if (n_groups < 1 || n_groups > PBR_MAX_ADAM_TENSORS) return PBR_ERR_SHAPE;
     GroupTable tab;
-    for (int32_t i = 0; i < PBR_MAX_ADAM_TENSORS; ++i) {
-        tab.g[i] = groups[i < n_groups ? i : 0];
+    pad_table(tab.g, groups, n_groups);
+    for (int32_t i = 0; i < n_groups; ++i)
         if (!tab.g[i].step) return PBR_ERR_NULL_MAP;
-    }
     hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), tab, n_groups, static_cast<pbr_adam_coeffs *>(coeffs_device));
     return launch_status();
 }

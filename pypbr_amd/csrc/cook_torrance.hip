@@ -203,7 +203,7 @@ const char *pbr_kernel_name(const pbr_render_desc *d) {
 
 int pbr_bytes_per_pixel(const pbr_render_desc *d) {
     if (pbr::validate(d) != PBR_OK) return 0;
-    const int ein = d->map_dtype == PBR_F32 ? 4 : 2, eout = d->out_dtype == PBR_F32 ? 4 : 2;
+    const int ein = (int)pbr::elem_bytes(d->map_dtype), eout = (int)pbr::elem_bytes(d->out_dtype);
     int ch = 3 + 1;                                        // albedo + roughness
     if (d->normal.data) ch += 3;
     ch += d->workflow == PBR_WORKFLOW_SPECULAR ? 3 : 1;    // specular | metallic

@@ -155,7 +155,7 @@ inline int pick_vec(const pbr_render_desc *d) {
 // 8 / 16 MiB plane strides (2048^2, 4096x1024: -2..12 %).  AUTO encodes exactly that; pbr_cook_torrance_autotune
 // measures instead of guessing.
 inline int auto_xcd_log2(const pbr_render_desc *d, int vec) {
-    const int64_t esz = d->map_dtype == PBR_F32 ? 4 : 2;
+    const int64_t esz = (int64_t)elem_bytes(d->map_dtype);
     const int64_t row_bytes = (int64_t)d->width * esz, tile_bytes = 64 * (int64_t)vec * esz;
     const int64_t plane_bytes = d->albedo.channel_stride * esz;
     if (d->map_dtype == PBR_F16) return 6;           // fp16 maps: runs are 1.5-5 % ahead on every shape tried
@@ -241,7 +241,7 @@ inline void fill_args(const pbr_render_desc *d, int vec, KArgs &k, int block_log
         d->height_total > d->map_height && k.n_tiles > 0) {
         // rows per band: the band's texels (all planes) within ~2 MiB -- 1/8 of it per XCD, beside the result streams in a 4 MiB
         // L2 -- a power of two that divides map_h, the band a whole number of XCD periods (tile_probe.py (a probe of its round, removed with its knob: git 9ce0718:tools/): "fold").
-        const int64_t esz = d->map_dtype == PBR_F32 ? 4 : 2;
+        const int64_t esz = (int64_t)elem_bytes(d->map_dtype);
         const int64_t row_bytes = (int64_t)d->map_width * esz * (3 + (d->normal.data ? 3 : 0) + 1 + (d->workflow == PBR_WORKFLOW_SPECULAR ? 3 : 1));
         int fl = 0;
         while (fl < 12 && (row_bytes << (fl + 1)) <= (2ll << 20)) ++fl;

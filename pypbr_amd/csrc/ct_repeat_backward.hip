@@ -107,7 +107,7 @@ int launch_repeat_blend_backward(const pbr_render_desc *d, const void *kblend, c
 
 static size_t folded_fallback_bytes(const pbr_render_desc *d) {
     // output-sized gradients of every map the descriptor holds, in the maps' storage type (the two-kernel form's intermediate)
-    const size_t esz = d->map_dtype == PBR_F32 ? 4 : 2;
+    const size_t esz = elem_bytes(d->map_dtype);
     const size_t planes = 3 + (d->normal.data ? 3 : 0) + 1 + (d->workflow == PBR_WORKFLOW_SPECULAR ? 3 : 1);
     return planes * (size_t)d->batch * (size_t)d->height * (size_t)d->width * esz;
 }
@@ -136,7 +136,7 @@ int pbr_cook_torrance_backward_folded(const pbr_render_desc *d, const void *grad
     if (repeat_backward_serves(d)) {
         if (repeat_thin_band(d)) {
             // the band touches only a window of the map's rows: the texels outside it have no repeat inside the band -- their partial sum is 0
-            const size_t esz = d->map_dtype == PBR_F32 ? 4 : 2, plane = (size_t)d->batch * d->map_height * d->map_width * esz;
+            const size_t esz = elem_bytes(d->map_dtype), plane = (size_t)d->batch * d->map_height * d->map_width * esz;
             void *const bufs[5] = {g_albedo, d->normal.data ? g_normal : nullptr, g_roughness, d->workflow == PBR_WORKFLOW_SPECULAR ? nullptr : g_metallic,
                                    d->workflow == PBR_WORKFLOW_SPECULAR ? g_specular : nullptr};
             const int chans[5] = {3, 3, 1, 1, 3};
@@ -151,7 +151,7 @@ int pbr_cook_torrance_backward_folded(const pbr_render_desc *d, const void *grad
     // sums (whole outputs only: a band's repeats are not whole)
     if (!workspace) return PBR_ERR_NULL_MAP;
     if (d->height != d->height_total) return PBR_ERR_UNSUPPORTED;
-    const size_t esz = d->map_dtype == PBR_F32 ? 4 : 2;
+    const size_t esz = elem_bytes(d->map_dtype);
     const size_t plane = (size_t)d->batch * d->height * d->width * esz;
     char *w = static_cast<char *>(workspace);
     void *const wanted[5] = {g_albedo, d->normal.data ? g_normal : nullptr, g_roughness,

@@ -168,7 +168,7 @@ int pbr_remap_planes(const void *src, int64_t src_batch_stride, int64_t src_plan
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
     uint32_t qpr, quads, per_image, blocks;
     if (!quad_grid(batch, h_out, w_out, qpr, quads, per_image, blocks)) return PBR_ERR_SHAPE;
-    const size_t esz = dtype == PBR_F32 ? 4 : 2;
+    const size_t esz = elem_bytes(dtype);
     const bool vst = w_out % 4 == 0 && is_aligned(dst, 4 * esz) && dst_batch_stride % 4 == 0 && dst_plane_stride % 4 == 0;
     const Axes A = {h_src, w_src, h_out, w_out, y_offset, y_step, x_offset, x_step};
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -1,8 +1,8 @@
 // launch_util.hpp -- the small things every launcher of the library shares (included through stream_shape.hpp): the mapping of a HIP
-// status to the C ABI's return codes, the pointer-alignment tests of the vector paths (is_aligned, all_aligned, quad_bytes), the
-// device's CU count, the dispatch of a runtime dtype / vector flag to a type / width tag (with_dtype, with_width), and the plane
+// status to the C ABI's return codes, the pointer-alignment tests of the vector paths (is_aligned, all_aligned, elem_bytes, quad_bytes),
+// the device's CU count, the dispatch of a runtime dtype / vector flag to a type / width tag (with_dtype, with_width), and the plane
 // accessors of the streaming kernels (map_ops.hip, blend.hip, normal_ops.hip, height_ops.hip): Elem<T>, one element, and
-// Span<T, V>, V consecutive ones.
+// Span<T, V>, V consecutive ones.  table_launch.hpp, host code only, adds what the launchers that carry a table of entries share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -34,8 +34,10 @@ inline bool all_aligned(size_t a, std::initializer_list<const void *> ptrs) {
         if (!is_aligned(p, a)) return false;
     return true;
 }
+// bytes of one element of a checked dtype: 4 (PBR_F32) | 2 (PBR_F16)
+inline size_t elem_bytes(int dtype) { return dtype == PBR_F32 ? 4 : 2; }
 // bytes of four elements, the alignment Span<T, 4> needs: 16 (PBR_F32) | 8 (PBR_F16)
-inline size_t quad_bytes(int dtype) { return dtype == PBR_F32 ? 16 : 8; }
+inline size_t quad_bytes(int dtype) { return 4 * elem_bytes(dtype); }
 
 // A launcher names its kernel once, inside a generic lambda: with_dtype hands it the element type of a dtype the entry point has
 // checked (PBR_F32 | PBR_F16), with_width the elements per lane of its vector test (4 | 1).

@@ -22,7 +22,7 @@
 #include <cstdint>
 
 #include "../../include/pbr_hip.h"
-#include "launch_util.hpp"
+#include "table_launch.hpp"
 
 namespace pbr {
 namespace {
@@ -150,8 +150,8 @@ extern "C" int pbr_pack_images(const pbr_image_pack *maps, int32_t n_maps, int32
                 return PBR_ERR_SHAPE;
     PackTable tab;
     bool any_general = false;
+    pad_table(tab.map, maps, n_maps);
     for (int32_t i = 0; i < PBR_MAX_IMAGE_PACKS; ++i) {
-        tab.map[i] = maps[i < n_maps ? i : 0];
         tab.dense[i] = takes_dense_form(tab.map[i], height, width) ? 1 : 0;
         any_general = any_general || !tab.dense[i];
     }

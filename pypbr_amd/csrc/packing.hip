@@ -25,7 +25,7 @@
 #include <cstdint>
 
 #include "../../include/pbr_hip.h"
-#include "launch_util.hpp"
+#include "table_launch.hpp"
 
 namespace pbr {
 namespace {
@@ -210,7 +210,7 @@ int plane_ops_arguments(const pbr_plane_op *ops, int32_t n_ops, int32_t batch, i
     if (!ops) return PBR_ERR_NULL_MAP;
     if (n_ops < 1 || n_ops > PBR_MAX_PLANE_OPS || batch < 1 || batch > 65535 || pixels < 1) return PBR_ERR_SHAPE;
     if (dtype != PBR_F32 && (backward || dtype != PBR_F16)) return PBR_ERR_DTYPE;
-    const size_t esz = dtype == PBR_F32 ? 4 : 2;
+    const size_t esz = elem_bytes(dtype);
     const int64_t blocks = ((pixels + 3 + 3) / 4 + 255) / 256;                     // groups of a plane shifted by up to 3 elements
     if (blocks > 0x7fffffff) return PBR_ERR_SHAPE;
     for (int32_t i = 0; i < n_ops; ++i) {
@@ -242,10 +242,6 @@ int plane_ops_arguments(const pbr_plane_op *ops, int32_t n_ops, int32_t batch, i
     return PBR_OK;
 }
 
-inline void fill_table(OpTable &tab, const pbr_plane_op *ops, int32_t n_ops) {
-    for (int32_t i = 0; i < PBR_MAX_PLANE_OPS; ++i) tab.op[i] = ops[i < n_ops ? i : 0];
-}
-
 }  // namespace
 }  // namespace pbr
 
@@ -257,7 +253,7 @@ int pbr_plane_ops(const pbr_plane_op *ops, int32_t n_ops, int32_t batch, int64_t
     const int rc = plane_ops_arguments(ops, n_ops, batch, pixels, dtype, false, grid);
     if (rc != PBR_OK) return rc;
     OpTable tab;
-    fill_table(tab, ops, n_ops);
+    pad_table(tab.op, ops, n_ops);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (dtype == PBR_F32) hipLaunchKernelGGL((plane_ops_kernel<float>), grid, dim3(256), 0, s, tab, pixels);
     else hipLaunchKernelGGL((plane_ops_kernel<_Float16>), grid, dim3(256), 0, s, tab, pixels);
@@ -270,7 +266,7 @@ int pbr_plane_ops_backward(const pbr_plane_op *ops, int32_t n_ops, int32_t batch
     const int rc = plane_ops_arguments(ops, n_ops, batch, pixels, dtype, true, grid);
     if (rc != PBR_OK) return rc;
     OpTable tab;
-    fill_table(tab, ops, n_ops);
+    pad_table(tab.op, ops, n_ops);
     hipLaunchKernelGGL(plane_ops_backward_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), tab, pixels);
     return launch_status();
 }

@@ -239,7 +239,7 @@ int pbr_rotate_planes(const void *src, int64_t src_batch_stride, int64_t src_pla
     if (dtype != PBR_F32 && dtype != PBR_F16) return PBR_ERR_DTYPE;
     uint32_t qpr, quads, per_image, blocks;
     if (!quad_grid(batch, h_out, w_out, qpr, quads, per_image, blocks)) return PBR_ERR_SHAPE;
-    const size_t esz = dtype == PBR_F32 ? 4 : 2;
+    const size_t esz = elem_bytes(dtype);
     const bool vst = w_out % 4 == 0 && is_aligned(dst, 4 * esz) && dst_batch_stride % 4 == 0 && dst_plane_stride % 4 == 0;
     const Affine M = make_affine(m00, m01, m10, m11, 1);
     const bool circ = geom->circular != 0;

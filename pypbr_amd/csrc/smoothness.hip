@@ -33,13 +33,12 @@
 // No cache hints: the gradients are read next by the optimiser, the parameters again by the next loss step.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <vector>
 
 #include "../../include/pbr_hip.h"
-#include "launch_util.hpp"
+#include "table_launch.hpp"
 
 namespace pbr {
 namespace {
@@ -252,10 +251,8 @@ __global__ __launch_bounds__(256) void smoothness_finish_kernel(FinishTable f, c
 
 // Whole quads everywhere: 16-byte accesses of fp32 planes and weights, 8-byte ones of fp16 planes.
 inline bool takes_quads(const pbr_smooth_tensor &e) {
-    if (e.width % 4 != 0) return false;
-    for (int64_t s : {e.param_batch_stride, e.param_plane_stride, e.grad_batch_stride, e.grad_plane_stride, e.weights_batch_stride})
-        if (s % 4 != 0) return false;
-    return all_aligned(quad_bytes(e.dtype), {e.param, e.grad}) && all_aligned(16, {e.weights});
+    return whole_quads({e.width, e.param_batch_stride, e.param_plane_stride, e.grad_batch_stride, e.grad_plane_stride, e.weights_batch_stride}) &&
+           all_aligned(quad_bytes(e.dtype), {e.param, e.grad}) && all_aligned(16, {e.weights});
 }
 
 // Workgroups of one entry: images x bands x strip groups.
@@ -267,29 +264,14 @@ inline int64_t entry_blocks(const pbr_smooth_tensor &e, bool quads, int32_t rows
     return (int64_t)e.batch * bands * strip_groups;
 }
 
-// [lo, hi): bytes a launch touches without a gap, and whether it writes them.
-struct Interval { uintptr_t lo, hi; bool written; };
-
-// One interval per plane of [batch] x [channels] planes of `pixels` elements (adam.hip's test: the views of a material-major packing
-// interleave the maps of a batch, so a pointer's first-to-last span says nothing).
-inline void add_planes(std::vector<Interval> &out, const void *p, int32_t batch, int32_t channels, int64_t pixels, int64_t bs, int64_t ps,
-                       size_t esz, bool written) {
-    const uintptr_t base = reinterpret_cast<uintptr_t>(p);
-    for (int32_t b = 0; b < batch; ++b) {
-        for (int32_t c = 0; c < channels; ++c) {
-            const uintptr_t lo = base + (uintptr_t)((int64_t)b * bs + (int64_t)c * ps) * esz;
-            out.push_back({lo, lo + (uintptr_t)pixels * esz, written});
-        }
-    }
-}
-
-// A gradient, which is written, may overlap nothing else the launch touches; parameters and weights, only read, may overlap each other.
+// A gradient, which is written, may overlap nothing else the launch touches; parameters and weights, only read, may overlap each other
+// (table_launch.hpp: written_overlaps).  Weights with batch stride 0 are one plane, counted once.
 bool launch_overlaps(const pbr_smooth_tensor *t, int32_t n) {
     std::vector<Interval> iv;
     bool any_grad = false;
     for (int32_t i = 0; i < n; ++i) {
         const pbr_smooth_tensor &e = t[i];
-        const size_t esz = e.dtype == PBR_F32 ? 4 : 2;
+        const size_t esz = elem_bytes(e.dtype);
         const int64_t pixels = (int64_t)e.height * e.width;
         add_planes(iv, e.param, e.batch, e.channels, pixels, e.param_batch_stride, e.param_plane_stride, esz, false);
         if (e.weights) add_planes(iv, e.weights, e.weights_batch_stride ? e.batch : 1, 1, pixels, e.weights_batch_stride, 0, sizeof(float), false);
@@ -298,15 +280,7 @@ bool launch_overlaps(const pbr_smooth_tensor *t, int32_t n) {
             any_grad = true;
         }
     }
-    if (!any_grad) return false;
-    std::sort(iv.begin(), iv.end(), [](const Interval &a, const Interval &b) { return a.lo < b.lo; });
-    uintptr_t end_written = 0, end_any = 0;                             // the furthest end among the intervals in front
-    for (const Interval &x : iv) {
-        if (x.lo < end_written || (x.written && x.lo < end_any)) return true;
-        if (x.written && x.hi > end_written) end_written = x.hi;
-        if (x.hi > end_any) end_any = x.hi;
-    }
-    return false;
+    return any_grad && written_overlaps(iv);
 }
 
 int check_entry(const pbr_smooth_tensor &e) {
@@ -320,8 +294,7 @@ int check_entry(const pbr_smooth_tensor &e) {
     if (!std::isfinite(e.k)) return PBR_ERR_SHAPE;
     if (e.param_batch_stride < 0 || e.param_plane_stride < 0 || e.grad_batch_stride < 0 || e.grad_plane_stride < 0 || e.weights_batch_stride < 0)
         return PBR_ERR_SHAPE;
-    const size_t esz = e.dtype == PBR_F32 ? 4 : 2;
-    if (!all_aligned(esz, {e.param, e.grad}) || !all_aligned(4, {e.weights})) return PBR_ERR_SHAPE;
+    if (!all_aligned(elem_bytes(e.dtype), {e.param, e.grad}) || !all_aligned(4, {e.weights})) return PBR_ERR_SHAPE;
     return PBR_OK;
 }
 
@@ -329,10 +302,8 @@ int check_entry(const pbr_smooth_tensor &e) {
 // unless that leaves the launch under PBR_SMOOTH_MIN_BLOCKS workgroups: then half as long, and so on.
 int64_t fill_table(const pbr_smooth_tensor *tensors, int32_t n, SmoothTable &tab) {
     tab.n = n;
-    for (int32_t i = 0; i < PBR_MAX_SMOOTH_TENSORS; ++i) {
-        tab.t[i] = tensors[i < n ? i : 0];
-        tab.quads[i] = takes_quads(tab.t[i]) ? 1 : 0;
-    }
+    pad_table(tab.t, tensors, n);
+    for (int32_t i = 0; i < PBR_MAX_SMOOTH_TENSORS; ++i) tab.quads[i] = takes_quads(tab.t[i]) ? 1 : 0;
     for (int32_t rows = PBR_SMOOTH_BAND_ROWS;; rows /= 2) {
         int64_t blocks = 0;
         tab.rows = rows;

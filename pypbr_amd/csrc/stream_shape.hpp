@@ -1,7 +1,8 @@
 // stream_shape.hpp -- launch shape of the streaming kernels: stream_shape with its per-kernel rules, and stream_grid, the grid of the
 // grid-stride kernels.  Every translation unit with a launcher includes it, directly or through ct_launch.hpp, and with it
-// launch_util.hpp (hip_code, launch_status, call_status, is_aligned, all_aligned, quad_bytes, resident_cus, with_dtype, with_width,
-// Elem<T>, Span<T, V>).
+// launch_util.hpp (hip_code, launch_status, call_status, is_aligned, all_aligned, elem_bytes, quad_bytes, resident_cus, with_dtype,
+// with_width, Elem<T>, Span<T, V>).  The table launchers include launch_util.hpp through table_launch.hpp instead (pad_table,
+// whole_quads, Interval, add_planes, written_overlaps).
 #pragma once
 #include <cstddef>
 

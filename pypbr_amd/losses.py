@@ -20,6 +20,31 @@ from . import functional as F_
 from .models import CookTorranceBRDF
 
 
+def _plain_maps(brdf, material):
+    """(albedo, normal, roughness, metallic, specular) of a material as the one-pass entry points can read them in place -- specular None
+    beside a metallic map -- else None: the material takes the composition through the BRDF module, which handles whatever it is handed
+    (CPU-resident maps, a lazy blend, maps not yet decoded)."""
+    a, n, r, m, s = material._stored(("albedo", "normal", "roughness", "metallic", "specular"))
+    ok = (material._is_materialised(allow_tile=brdf.view_type != "point")      # the camera renders real maps: the module materialises
+          and torch.device(material.device).type == "cuda"
+          and a is not None and r is not None and material._stores("normal")
+          and (m is not None or s is not None) and all(t is None or t.is_cuda for t in (a, n, r, m, s))
+          and brdf.override_device is None)
+    return (a, n, r, m, None if m is not None else s) if ok else None
+
+
+def _reference(ground_truth, shared, render):
+    """The reference of a loss: `ground_truth` itself when it is a tensor, else `render(ground_truth)`.  06_advanced.rst:101-102 renders
+    both materials under autograd.  Without a graph only when nothing could receive a gradient through this branch: no ground-truth map
+    and none of the `shared` light / view tensors requires grad."""
+    if isinstance(ground_truth, torch.Tensor):
+        return ground_truth
+    differentiable = torch.is_grad_enabled() and any(
+        isinstance(t, torch.Tensor) and t.requires_grad for t in ground_truth._render_inputs() + list(shared))
+    with torch.enable_grad() if differentiable else torch.no_grad():
+        return render(ground_truth)
+
+
 class RenderingLoss(nn.Module):
     def __init__(self, light_type='point', view_dir=torch.tensor([0.0, 0.0, 1.0]), light_dir=torch.tensor([0.1, 0.1, 1.0]),
                  light_intensity=torch.tensor([1.0, 1.0, 1.0]), light_size=None, view_type='directional'):
@@ -30,43 +55,21 @@ class RenderingLoss(nn.Module):
         self.light_intensity = light_intensity
         self.light_size = light_size
 
-    @staticmethod
-    def _maps(material):
-        store = material.__dict__.get("_store", {})
-        return [store.get(k) for k in ("albedo", "normal", "roughness", "metallic", "specular")]
+    def _render(self, material):
+        return self.brdf(material, self.view_dir, self.light_dir, self.light_intensity, self.light_size)
 
     def forward(self, predicted_material, ground_truth_material, weights=None):
         """`ground_truth_material`: a material, or the reference rendering itself ((3,H,W) / (B,3,H,W) tensor).  `weights` (an extension):
         one weight per pixel, (1,H,W) / (B,1,H,W); the loss is `(weights * (rendering - reference) ** 2).mean()`
         (functional.rendering_loss_mse(weights=))."""
-        if isinstance(ground_truth_material, torch.Tensor):
-            rendered_gt = ground_truth_material
-        else:
-            # 06_advanced.rst:101-102 renders both materials under autograd.  Without a graph only when nothing could receive a gradient
-            # through this branch: no ground-truth map and none of the shared light / view tensors requires grad.
-            gt_maps = list(ground_truth_material.__dict__.get("_store", {}).values())
-            pending = ground_truth_material.__dict__.get("_lazy_blend")
-            if pending is not None:
-                gt_maps += list(pending[0].values()) + [pending[1]]
-            differentiable = torch.is_grad_enabled() and any(
-                isinstance(t, torch.Tensor) and t.requires_grad for t in gt_maps + [self.view_dir, self.light_dir, self.light_intensity])
-            with torch.enable_grad() if differentiable else torch.no_grad():
-                rendered_gt = self.brdf(ground_truth_material, self.view_dir, self.light_dir, self.light_intensity, self.light_size)
-        a, n, r, m, s = self._maps(predicted_material)
-        fusable = (predicted_material.__dict__.get("_lazy_blend") is None
-                   and torch.device(predicted_material.device).type == "cuda" and not predicted_material._has_pending()
-                   and a is not None and r is not None and "normal" in predicted_material.__dict__.get("_store", {})
-                   and (m is not None or s is not None) and all(t is None or t.is_cuda for t in (a, n, r, m, s))
-                   and self.brdf.override_device is None
-                   and (self.brdf.view_type != "point" or predicted_material.lazy_tile == (1, 1)))   # the camera renders real maps: the module materialises
-        if not fusable:
-            rendered_pred = self.brdf(predicted_material, self.view_dir, self.light_dir, self.light_intensity, self.light_size)
+        rendered_gt = _reference(ground_truth_material, (self.view_dir, self.light_dir, self.light_intensity), self._render)
+        maps = _plain_maps(self.brdf, predicted_material)
+        if maps is None:
+            rendered_pred = self._render(predicted_material)
             if weights is not None:
                 return F_._weighted_mse(rendered_pred, rendered_gt, weights)
             return nn.MSELoss()(rendered_pred, rendered_gt.to(rendered_pred.device))
-        if m is not None:
-            s = None
-        return F_.rendering_loss_mse(a, n, r, m, s, target=rendered_gt.to(a.device), view_dir=self.view_dir, light=self.light_dir,
+        return F_.rendering_loss_mse(*maps, target=rendered_gt.to(maps[0].device), view_dir=self.view_dir, light=self.light_dir,
                                      light_intensity=self.light_intensity, light_type=self.brdf.light_type, light_size=self.light_size,
                                      view_type=self.brdf.view_type, **({} if weights is None else {"weights": weights}),
                                      tile=predicted_material.lazy_tile,      # a recorded tile(n): evaluated and differentiated at every repeat
@@ -109,21 +112,10 @@ class MultiLightRenderingLoss(nn.Module):
                     light_size=self.light_size, view_type=self.brdf.view_type, tile=material.lazy_tile, albedo_is_srgb=bool(material.albedo_is_srgb),
                     specular_is_srgb=bool(getattr(material, "specular_is_srgb", True)))
 
-    def _plain_maps(self, material):
-        """The five maps of a material the stack's entry points can read in place (RenderingLoss's `fusable`), else None."""
-        a, n, r, m, s = RenderingLoss._maps(material)
-        ok = (material.__dict__.get("_lazy_blend") is None
-              and torch.device(material.device).type == "cuda" and not material._has_pending()
-              and a is not None and r is not None and "normal" in material.__dict__.get("_store", {})
-              and (m is not None or s is not None) and all(t is None or t.is_cuda for t in (a, n, r, m, s))
-              and self.brdf.override_device is None
-              and (self.brdf.view_type != "point" or material.lazy_tile == (1, 1)))    # the camera renders real maps: the module materialises
-        return (a, n, r, m, None if m is not None else s) if ok else None
-
     def _render(self, material):
         """[L,3,H,W] / [B,L,3,H,W]: one launch where the maps can be read in place, else L calls of the BRDF module (CPU-resident maps,
         a lazy blend, maps not yet decoded: whatever the module handles)."""
-        maps = self._plain_maps(material)
+        maps = _plain_maps(self.brdf, material)
         if maps is not None:
             return F_.cook_torrance_stack(*maps, **self._kwargs(material))
         lt = torch.as_tensor(self.lights, dtype=torch.float32).reshape(-1, 3)
@@ -134,18 +126,8 @@ class MultiLightRenderingLoss(nn.Module):
 
     def forward(self, predicted_material, ground_truth, weights=None):
         """`ground_truth`: a material, or the stack of photographs ([L,3,H,W] / [B,L,3,H,W] tensor); `weights`: see the class."""
-        if isinstance(ground_truth, torch.Tensor):
-            targets = ground_truth
-        else:
-            gt_maps = list(ground_truth.__dict__.get("_store", {}).values())
-            pending = ground_truth.__dict__.get("_lazy_blend")
-            if pending is not None:
-                gt_maps += list(pending[0].values()) + [pending[1]]
-            differentiable = torch.is_grad_enabled() and any(
-                isinstance(t, torch.Tensor) and t.requires_grad for t in gt_maps + [self.view_dir, self.lights, self.light_intensities])
-            with torch.enable_grad() if differentiable else torch.no_grad():
-                targets = self._render(ground_truth)
-        maps = self._plain_maps(predicted_material)
+        targets = _reference(ground_truth, (self.view_dir, self.lights, self.light_intensities), self._render)
+        maps = _plain_maps(self.brdf, predicted_material)
         if maps is None:
             rendered = self._render(predicted_material)
             if weights is not None:

@@ -178,6 +178,7 @@ def _decode_remembering(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+FIT_MAPS = ("albedo", "normal", "roughness", "metallic", "specular", "height")     # the maps of a fit: MaterialBase._fit_maps
 _CALL_CACHES = ("_device_cache", "_plan_cache", "_plan_seen")     # what CookTorranceBRDF keeps in a material's __dict__ between calls
 
 
@@ -247,6 +248,31 @@ class MaterialBase:
     def _has_pending(self) -> bool:
         """Some map is not yet what the reference's dict would hold: still an image's samples, or a normal map still undecoded."""
         return bool(self.__dict__.get("_raw_normal")) or any(F_.is_encoded(t) for t in self._raw.values())
+
+    # -- what the fit path (losses.py, priors.py, optim.py) asks about the stored maps.  None of these reads `_maps`: no blend is carried
+    # out, no tile is repeated, nothing is decoded or brought home.
+    def _stored(self, names) -> list:
+        """The stored maps under `names` as they stand, None for one that is absent."""
+        store = self.__dict__.get("_store", {})
+        return [store.get(k) for k in names]
+
+    def _stores(self, name) -> bool:
+        """A map is filed under `name` (whatever its state)."""
+        return name in self.__dict__.get("_store", {})
+
+    def _render_inputs(self) -> list:
+        """Every value a rendering of this material depends on: the stored maps, a pending blend's second store and its mask (else None)."""
+        other, mask = self.__dict__.get("_lazy_blend") or ({}, None)
+        return list(self.__dict__.get("_store", {}).values()) + list(other.values()) + [mask]
+
+    def _is_materialised(self, allow_tile: bool = False) -> bool:
+        """The stored maps are the maps: no pending blend, nothing still encoded or undecoded, and no recorded tile(n) -- unless the
+        caller evaluates the stored maps at every repeat itself (`allow_tile`)."""
+        return self.__dict__.get("_lazy_blend") is None and (allow_tile or self.lazy_tile == (1, 1)) and not self._has_pending()
+
+    def _fit_maps(self) -> dict:
+        """name -> tensor of the stored floating-point maps a fit can optimise and regularise, in FIT_MAPS' order."""
+        return {k: t for k, t in zip(FIT_MAPS, self._stored(FIT_MAPS)) if isinstance(t, torch.Tensor) and t.is_floating_point()}
 
     def _samples_on_host(self):
         """Maps that are still an image's samples become float32 where they are (the host): base.py:143-164's arithmetic."""

@@ -16,7 +16,7 @@ import math
 import torch
 
 from . import _native as N
-from ._dispatch import _DTYPES, launch
+from ._dispatch import _DTYPES, launch, plane_geometry, rows_are_dense
 
 # Launches since import, by entry point (what the tests count; never reset here).
 LAUNCHES = {"adam_step": 0, "adam_advance": 0}
@@ -66,11 +66,10 @@ def _planes(t):
     """(tensor, batch, channels, pixels, batch stride, plane stride) with dense planes, or None: [C,H,W] / [B,C,H,W] views of packed maps
     keep their strides; anything else counts as one plane of numel elements when it is contiguous."""
     if t.dim() in (3, 4):
-        h, w = t.shape[-2], t.shape[-1]
-        if t.stride(-1) == 1 and (h == 1 or t.stride(-2) == w) and all(s >= 0 for s in t.stride()):
-            batch = t.shape[0] if t.dim() == 4 else 1
-            return t, batch, t.shape[-3], h * w, (t.stride(0) if t.dim() == 4 else 0), t.stride(-3)
-        return None
+        if not rows_are_dense(t):
+            return None
+        batch, channels, h, w, batch_stride, plane_stride = plane_geometry(t)
+        return t, batch, channels, h * w, batch_stride, plane_stride
     if t.is_contiguous():
         return t, 1, 1, t.numel(), 0, 0
     return None
@@ -241,11 +240,9 @@ def material_param_groups(material, lr=1e-3, lr_normal=None, roughness_min=0.05,
     bounds=(roughness_min, 1) -- below about 0.1 the GGX denominator cancels; 0.05 is the lower end of the criterion inputs -- the normal
     with project="unit" and `min_z` (at `lr_normal`, default `lr`), height without a projection.  `maps`: the names to fit (default: every
     stored map of those six).  Sets requires_grad_ on the maps it returns; the maps are the material's own tensors, updated in place."""
-    store = material.__dict__.get("_store", {})
-    names = [k for k in ("albedo", "normal", "roughness", "metallic", "specular", "height") if k in store] if maps is None else list(maps)
+    names = list(material._fit_maps()) if maps is None else list(maps)
     groups = []
-    for name in names:
-        t = store.get(name)
+    for name, t in zip(names, material._stored(names)):
         if not isinstance(t, torch.Tensor) or not t.is_floating_point():
             raise ValueError("the material has no decoded %r map to fit" % name)
         t.requires_grad_(True)

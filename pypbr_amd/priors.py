@@ -14,14 +14,14 @@ import torch
 import torch.nn.functional as TF
 
 from . import _native as N
-from ._dispatch import _DTYPES, launch, ptr
+from ._dispatch import _DTYPES, launch, plane_geometry, ptr, rows_are_dense
+from .materials import FIT_MAPS as MAP_NAMES                # the names `lambdas` may carry: what MaterialBase._fit_maps looks for
 
 # Launches since import (what the tests count; never reset here).
 LAUNCHES = {"smoothness_step": 0}
 
 KINDS = {"l2": N.SMOOTH_L2, "charbonnier": N.SMOOTH_CHARBONNIER}
 REDUCTIONS = ("mean", "sum")
-MAP_NAMES = ("albedo", "normal", "roughness", "metallic", "specular", "height")
 
 
 def _scale(lam, t, reduction):
@@ -105,20 +105,15 @@ def _composition(tensors, lambdas, kind="charbonnier", eps=1e-3, wrap=False, wei
     return terms.sum(), terms
 
 
-def _dense_rows(t):
-    return t.stride(-1) == 1 and (t.shape[-2] == 1 or t.stride(-2) == t.shape[-1]) and all(s >= 0 for s in t.stride())
-
-
 def _entry(t, grad, w, k, kind, eps, wrap):
-    """pbr_smooth_tensor of one map (dense rows), its gradient buffer (dense rows, or None) and its float32 contiguous weights (or None)."""
-    four = t.dim() == 4
-    batch = t.shape[0] if four else 1
-    plane = t.shape[-2] * t.shape[-1]
-    return N.SmoothTensor(t.data_ptr(), ptr(grad), ptr(w),
-                          t.stride(0) if four else 0, t.stride(-3),
-                          (grad.stride(0) if four else 0) if grad is not None else 0, grad.stride(-3) if grad is not None else 0,
+    """pbr_smooth_tensor of one map (dense rows), its gradient buffer (dense rows, of the map's shape, or None) and its float32 contiguous
+    weights (or None)."""
+    batch, channels, height, width, batch_stride, plane_stride = plane_geometry(t)
+    grad_strides = plane_geometry(grad)[4:] if grad is not None else (0, 0)
+    plane = height * width
+    return N.SmoothTensor(t.data_ptr(), ptr(grad), ptr(w), batch_stride, plane_stride, *grad_strides,
                           plane if (w is not None and w.numel() > plane) else 0,
-                          k, float(eps), _DTYPES[t.dtype], batch, t.shape[-3], t.shape[-2], t.shape[-1], kind, int(bool(wrap)))
+                          k, float(eps), _DTYPES[t.dtype], batch, channels, height, width, kind, int(bool(wrap)))
 
 
 def _step(tensors, grads, weights, ks, kind, eps, wrap):
@@ -224,7 +219,7 @@ def smoothness(tensors, lambdas, *, kind="charbonnier", eps=1e-3, wrap=False, we
         zero = torch.zeros((), dtype=torch.float32, device=device)
         return (zero, torch.zeros(len(tensors), dtype=torch.float32, device=device)) if return_terms else zero
     grad_on = torch.is_grad_enabled()
-    if any(not _dense_rows(tensors[i]) for i in live) or (grad_on and any(each[i] is not None and each[i].requires_grad for i in live)):
+    if any(not rows_are_dense(tensors[i]) for i in live) or (grad_on and any(each[i] is not None and each[i].requires_grad for i in live)):
         loss, some = _composition([tensors[i] for i in live], [lambdas[i] for i in live], kind, eps, wrap, [each[i] for i in live], reduction)
         loss, some = loss.float(), some.float()
     else:
@@ -259,15 +254,13 @@ class MaterialSmoothness(torch.nn.Module):
         self.kind, self.eps, self.wrap, self.reduction = kind, float(eps), bool(wrap), reduction
 
     def forward(self, material, weights=None):
-        d = material.__dict__
-        if d.get("_lazy_blend") is not None or d.get("_lazy_tile", (1, 1)) != (1, 1) or material._has_pending():
+        if not material._is_materialised():
             raise ValueError("MaterialSmoothness needs materialised maps: call materialize_blend() / materialize_tile(), or read the maps "
                              "once, before fitting a material with a pending lazy blend, a lazy tile or undecoded maps")
-        store = d.get("_store", {})
-        names = [k for k in MAP_NAMES if k in store and isinstance(store[k], torch.Tensor) and store[k].is_floating_point() and k in self.lambdas]
-        if not names:
+        maps = {k: t for k, t in material._fit_maps().items() if k in self.lambdas}
+        if not maps:
             raise ValueError("the material stores none of the maps %s" % sorted(self.lambdas))
-        return smoothness([store[k] for k in names], [self.lambdas[k] for k in names], kind=self.kind, eps=self.eps, wrap=self.wrap,
+        return smoothness(list(maps.values()), [self.lambdas[k] for k in maps], kind=self.kind, eps=self.eps, wrap=self.wrap,
                           weights=weights, reduction=self.reduction)
 
     def extra_repr(self):

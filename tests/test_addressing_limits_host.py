@@ -170,11 +170,11 @@ def test_adam_intervals_past_2_to_32_bytes(dtype, esz):
 # ---------------------------------------------------------------- the Python-side validators
 def test_python_validators_at_their_boundaries():
     """What the wrappers decide before any device work: 16 shots pass photometric_stereo's count check (and reach the device check), 17 do
-    not; optim._planes and priors._dense_rows hand on strides past 2^32 bytes as they are and refuse rows that are not dense (torch has no negative strides to hand on); _rows_dense
+    not; optim._planes and _dispatch.rows_are_dense hand on strides past 2^32 bytes as they are and refuse rows that are not dense (torch has no negative strides to hand on); _rows_dense
     keeps a view with such strides and copies one without dense rows."""
     import torch
     from pypbr_amd import capture, priors
-    from pypbr_amd._dispatch import _rows_dense
+    from pypbr_amd._dispatch import _rows_dense, rows_are_dense
     from pypbr_amd.optim import _planes
     kw = dict(light_intensity=[1.0, 1.0, 1.0])
     assert N.MAX_PHOTOMETRIC_SHOTS == 16
@@ -184,12 +184,12 @@ def test_python_validators_at_their_boundaries():
         capture.photometric_stereo(torch.zeros(17, 3, 8, 8), light=torch.tensor([[0.1, 0.2, 0.9]] * 17), **kw)
     strides = ((1 << 33) + 4, (1 << 31) + 4, 36, 1)
     far = torch.empty_strided((2, 3, 24, 36), strides, device="meta")                      # (no storage: only the geometry is read)
-    assert _planes(far) == (far, 2, 3, 864, strides[0], strides[1]) and priors._dense_rows(far) and _rows_dense(far) is far
+    assert _planes(far) == (far, 2, 3, 864, strides[0], strides[1]) and rows_are_dense(far) and _rows_dense(far) is far
     three = torch.empty_strided((3, 24, 36), strides[1:], device="meta")
     assert _planes(three) == (three, 1, 3, 864, 0, strides[1])
     t = torch.zeros(2, 3, 24, 36)
     for view in (t.transpose(-1, -2), t[..., ::2], t[:, :, ::2]):                             # rows that are not dense: refused, or copied
-        assert _planes(view) is None and not priors._dense_rows(view) and _rows_dense(view).is_contiguous()
+        assert _planes(view) is None and not rows_are_dense(view) and _rows_dense(view).is_contiguous()
     assert _planes(t.expand(4, 2, 3, 24, 36)[0]) is not None and _planes(t[:, :1].expand(2, 3, 24, 36))[5] == 0      # an expanded plane: stride 0 is forwarded
     smooth_entry = priors._entry(far, far, None, 1.0, N.SMOOTH_L2, 1e-3, False)
     assert (smooth_entry.param_batch_stride, smooth_entry.param_plane_stride, smooth_entry.grad_plane_stride) == (strides[0], strides[1], strides[1])
